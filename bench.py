@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 3-D c2c PFFT, 1024^3 complex128, forward + backward per step.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N > 1 from a plain shell re-launches itself under `torch.distributed.run` (one rank per GPU, RCCL
 over xGMI); a launch that already carries RANK / WORLD_SIZE (the driver's torchrun line) is used
@@ -9,7 +9,22 @@ as it is.  Rank 0 prints ONE JSON line.
 
 `value` = whole-job GFLOP/s with the work model of BASELINE.md section 3 (5 N log2 N flops per
 1-D line => 1.6106e11 per 1024^3 transform, fwd + bwd per step), inputs resident in HBM before the
-timed region, barrier + device sync on both sides, max over ranks.  `roofline` is for the dominant
+timed region, barrier + device sync on both sides, max over ranks; `ms_per_step` = milliseconds of
+one timed fwd + bwd step.
+
+A plain run does only what that figure needs: set up, W warm-up steps, K timed steps, the outputs
+(`--dump-outputs`), the line.  At N > 1 that includes admitting and timing the alternative plans
+(the headline is the fastest admitted one).  Everything else runs under `--full` only: the
+admission gates at N = 1, the per-kernel roofline, the copy ceiling, `cpu_baseline`, the other
+BASELINE configurations, and at N > 1 the stage breakdowns and the slab grid.
+
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed plan holds after
+the last step -- the forward output and the backward output -- as DIR/<name>.npy (float64
+[real, imag] pairs at a fixed, seeded sample of positions, 32 MiB in all; at N > 1 those of the
+plain-route plan, which is timed first).  The input is seeded too, so two builds run with the same
+arguments can be compared output for output.
+
+Under `--full`: `roofline` is for the dominant
 kernel: algorithmic bytes per launch (one read + one write of the local array per axis pass the
 launch performs -- the fused launch of DESIGN_HISTORY.md section 4.7 performs two) / its mean launch
 duration from HIP events recorded on the launch stream inside the timed region; that launch hands
@@ -590,6 +605,33 @@ def timed_steps(world, sync, step, steps):
     return world.allreduce_max(time.perf_counter() - t0)
 
 
+DUMP_SAMPLES = 1 << 20          # values per output array, all ranks together: 2 x 16 MiB of float64
+
+
+def dump_outputs(dirname, fft, world, rank, size):
+    """--dump-outputs: the forward output (spectral array) and the backward output (the physical array the step returns
+    to) of the plan's last execution, each as float64 [real, imag] pairs at DUMP_SAMPLES // size positions of every
+    rank's local block drawn by a CPU generator seeded with 4321 + rank (the whole block where it is smaller), rank 0's
+    first.  Same arguments: same positions, same inputs, so the files compare output for output.  Collective."""
+    import numpy as np
+    import torch
+    per_rank = max(1, DUMP_SAMPLES // size)
+    arrays = (('forward_output', fft.forward.output_array.tensor), ('backward_output', fft.backward.output_array.tensor))
+    for name, t in arrays:
+        if t.numel() <= per_rank:
+            vals = t.reshape(-1)
+        else:
+            g = torch.Generator().manual_seed(4321 + rank)
+            idx = [torch.randint(s, (per_rank,), generator=g).to(t.device) for s in t.shape]
+            vals = t[tuple(idx)]
+        vals = torch.view_as_real(vals) if vals.is_complex() else vals
+        part = vals.detach().to('cpu', torch.float64).numpy()
+        parts = world.allgather_obj(part) if size > 1 else [part]
+        if rank == 0:
+            os.makedirs(dirname, exist_ok=True)
+            np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(np.concatenate(parts)))
+
+
 def failure_line(args, size, why):
     """The line of a run whose headline never completed: same keys, no number, the reason and the
     wire's diagnostics."""
@@ -617,6 +659,11 @@ def main():
     ap.add_argument('--no-configs', action='store_true', help='skip the other BASELINE configurations (one GPU, a few seconds)')
     ap.add_argument('--cpu-budget', type=float, default=None,
                     help='seconds of timed CPU executions for the cpu_baseline leg (default: 300 when the host can hold the 1024^3 sample, else 25)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: admission gates (N = 1), roofline, copy ceiling, cpu_baseline, the other '
+                         'BASELINE configurations, stage breakdowns and the slab grid (N > 1); the --no-* options above apply to it')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the timed plan\'s outputs of its last step as DIR/<name>.npy (seeded sample, float64)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
@@ -716,7 +763,9 @@ def run(args, guard, state):
     for i in range(0, ur.shape[0], 64):
         sl = ur[i:i + 64]
         sl.copy_(torch.randn(sl.shape, generator=g, device=dev, dtype=torch.float64))
-    u0 = u.tensor.clone()
+    # the gates below need the input kept aside: at N = 1 only under --full, at N > 1 always (they admit the alternatives)
+    gated = args.full or size > 1
+    u0 = u.tensor.clone() if gated else None
 
     def round_trip_error(f, u0=u0):
         """north-star parity gate: forward -> backward on the planned arrays, relative l2 error"""
@@ -781,27 +830,32 @@ def run(args, guard, state):
             torch.cuda.empty_cache()
         return rep, None
 
-    gate, why_not = admit(fft)
-    assert why_not is None, why_not
-    headline_print = gate.pop('_print')
-    rt_err = gate['round_trip_rel_err']
+    gate, headline_print = None, None
+    if gated:
+        gate, why_not = admit(fft)
+        assert why_not is None, why_not
+        headline_print = gate.pop('_print')
+        fft.forward.input_array.tensor.copy_(u0)     # the timed steps start from the seeded input, gated or not
 
     for _ in range(args.warmup):
         one_step()
-    if hip:
+    profile = hip and args.full
+    if profile:
         _lib.set_option('profile', 1)
     elapsed = timed_steps(world, sync, one_step, args.steps)
-    if hip:
+    if profile:
         _lib.set_option('profile', 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fft, world, rank, size)
 
     # per-kernel launch durations inside the timed region (HIP events on the launch stream)
     kern = {}
     plans = []
-    if hip:
+    if profile:
         plans = list(fft._fused_plans) if fft._fused_plans else \
             [x.fwd for x in fft.xfftn] + [x.bck for x in fft.xfftn]
     profiles = [p.profile() for p in plans]
-    if hip:       # (slab grids: the two local stages run as one guru2 plan per direction, PFFT._fuse_pairs)
+    if profile:   # (slab grids: the two local stages run as one guru2 plan per direction, PFFT._fuse_pairs)
         eng = _lib.engine()
         profiles += [eng.plan_profile(h, eng.plan_cost(h)[2]) for h in getattr(fft, '_pair_plans', [])]
     for prof in profiles:
@@ -813,11 +867,12 @@ def run(args, guard, state):
     # HBM traffic per launch from the committed PMC profile of this same command (rocprofv3 cannot
     # run inside the timed region); only quoted when kernel and problem size match
     pmc = {}
-    try:
-        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-            pmc = json.load(f)
-    except Exception:
-        pass
+    if profile:
+        try:
+            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+                pmc = json.load(f)
+        except Exception:
+            pass
     roofline = None
     if kern:
         name = max(kern, key=lambda k: kern[k]['ms'])
@@ -856,7 +911,7 @@ def run(args, guard, state):
     # streaming-copy ceiling of this very box and run (same byte count per launch as one pass of the
     # dominant kernel when it fits): what "100 % of achievable HBM" means next to roofline.frac
     copy_ceiling = None
-    if rank == 0 and hip:
+    if rank == 0 and profile:
         try:
             nbytes = min(16 << 30, (u.tensor.numel() * 16) // 256 * 256)
             src, dst = u.tensor, fft.forward.output_array.tensor
@@ -908,24 +963,30 @@ def run(args, guard, state):
             'ms_per_step': round(ms_per_step, 3),
             'higher_is_better': True, 'scaling': 'strong', 'vs_baseline': None,
             'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'PFFT 3D c2c %d^3 complex128 forward+backward per step' % n,
-                       'grid': grid, 'exchange': exchange_report(f),
-                       'round_trip_rel_err': err['round_trip_rel_err'],
-                       'forward_rel_err': err['forward_rel_err'],
-                       'exchange_check': err['exchange_check'],
-                       'gates': dict({k: v for k, v in err.items() if not k.startswith('_')},
-                                     what='before timing: every Transfer of the plan on global linear indices, forward and '
-                                          'backward, bit-exact on the wire / route timed (tests/test_pencil.py:26-56); six lines of '
-                                          'the forward against the DFT by definition, float64 on the device, tol 2e-10 max|ref| '
-                                          '(BASELINE.md section 4); round trip tol 1e-10')},
+            'config': dict({'workload': 'PFFT 3D c2c %d^3 complex128 forward+backward per step' % n,
+                            'grid': grid, 'exchange': exchange_report(f)}, **gate_fields(err)),
             'whole_transform_hbm': whole,
         }
+
+    def gate_fields(err):
+        """the admission gates' part of `config` (none where the plan was not gated: N = 1 without --full)"""
+        if err is None:
+            return {}
+        return {'round_trip_rel_err': err['round_trip_rel_err'],
+                'forward_rel_err': err['forward_rel_err'],
+                'exchange_check': err['exchange_check'],
+                'gates': dict({k: v for k, v in err.items() if not k.startswith('_')},
+                              what='before timing: every Transfer of the plan on global linear indices, forward and '
+                                   'backward, bit-exact on the wire / route timed (tests/test_pencil.py:26-56); six lines of '
+                                   'the forward against the DFT by definition, float64 on the device, tol 2e-10 max|ref| '
+                                   '(BASELINE.md section 4); round trip tol 1e-10')}
 
     out = None
     if rank == 0:
         out = headline(fft, elapsed, gate)
-        out['roofline'] = roofline
-        out['hbm_copy_ceiling'] = copy_ceiling
+        if args.full:
+            out['roofline'] = roofline
+            out['hbm_copy_ceiling'] = copy_ceiling
         if roofline and copy_ceiling and copy_ceiling.get('gbs'):
             roofline['frac_of_copy_ceiling'] = round(roofline['achieved'] / copy_ceiling['gbs'], 4)
             roofline['frac_hbm_min_of_copy_ceiling'] = round(
@@ -933,7 +994,7 @@ def run(args, guard, state):
             wh = out['whole_transform_hbm']
             if wh.get('min_gbs'):
                 wh['min_frac_of_copy_ceiling'] = round(wh['min_gbs'] / copy_ceiling['gbs'], 4)
-        if not args.no_cpu and size == 1:
+        if args.full and not args.no_cpu and size == 1:
             cores = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else os.cpu_count()
             try:
                 out['cpu_baseline'] = cpu_baseline(cores, args.cpu_budget)
@@ -942,7 +1003,7 @@ def run(args, guard, state):
                                        'sample': 'failed: %r' % (e,)}
 
     if size == 1:
-        if hip and n == 1024 and not args.no_configs:
+        if args.full and hip and n == 1024 and not args.no_configs:
             try:
                 out['other_configs'] = other_configs(_lib, torch)
             except Exception as e:          # never lose the headline to an extra
@@ -991,12 +1052,14 @@ def run(args, guard, state):
         return comp, sum(ms for label, ms in st if not label.startswith('fft'))
 
     try:
-        # where a step spends its time, stage by stage (synchronised, max over ranks)
-        phase('stage breakdown')
-        st = {'forward': stages(fft.forward), 'backward': stages(fft.backward)}
-        cf, wf = split_ms(st['forward'])
-        cb, wb = split_ms(st['backward'])
-        staged_split = dict(compute_ms=round(cf + cb, 3), wire_ms=round(wf + wb, 3))
+        # where a step spends its time, stage by stage (synchronised, max over ranks; --full)
+        staged_split = None
+        if args.full:
+            phase('stage breakdown')
+            st = {'forward': stages(fft.forward), 'backward': stages(fft.backward)}
+            cf, wf = split_ms(st['forward'])
+            cb, wb = split_ms(st['backward'])
+            staged_split = dict(compute_ms=round(cf + cb, 3), wire_ms=round(wf + wb, 3))
 
         def overlap(step_ms):
             """How much of the shorter of (compute, wire) a plan hides behind the longer one: (compute + wire - step) /
@@ -1005,7 +1068,7 @@ def run(args, guard, state):
             c, w = staged_split['compute_ms'], staged_split['wire_ms']
             eff = (c + w - step_ms) / min(c, w) if min(c, w) > 0 else None
             return dict(staged_split, step_ms=round(step_ms, 3), overlap_eff=None if eff is None else round(eff, 3))
-        if rank == 0:
+        if rank == 0 and args.full:
             out['stages_ms'] = st
             out['overlap'] = overlap(out['ms_per_step'])
 
@@ -1061,7 +1124,8 @@ def run(args, guard, state):
                 el2 = timed_steps(world, sync, tuned_step, args.steps)
                 info['ms_per_step'] = round(el2 / args.steps * 1e3, 3)
                 info['value'] = round(flops / (el2 / args.steps) / 1e9, 1)
-                info['overlap'] = overlap(info['ms_per_step'])
+                if args.full:
+                    info['overlap'] = overlap(info['ms_per_step'])
                 if rank == 0 and el2 < best['elapsed']:
                     if 'plain_route' not in out:
                         out['plain_route'] = {'ms_per_step': out['ms_per_step'], 'value': out['value'],
@@ -1071,11 +1135,12 @@ def run(args, guard, state):
                     out.update(headline(tuned, el2, gate2))
                     out.update(keep)
                     out['config']['plan'] = label
-                    out['overlap'] = info['overlap']
+                    if args.full:
+                        out['overlap'] = info['overlap']
                     if tuned.pipeline is not None:
                         out['config']['pipeline'] = info['pipeline']
                 best['elapsed'] = min(best['elapsed'], el2)
-                if tuned.pipeline is None:
+                if tuned.pipeline is None and args.full:
                     phase('stage breakdown (%s)' % label)
                     st2 = {'forward': stages(tuned.forward), 'backward': stages(tuned.backward)}
                     if rank == 0:
@@ -1089,7 +1154,7 @@ def run(args, guard, state):
 
         # the same cube on the slab grid (N,1,1), whose single exchange spans all ranks and
         # therefore all xGMI links
-        if sum(1 for c in grid if c > 1) > 1 and n % size == 0 and not args.no_slab:
+        if args.full and sum(1 for c in grid if c > 1) > 1 and n % size == 0 and not args.no_slab:
             phase('slab grid')
             fft.destroy()
             del fft, u, ur

@@ -47,7 +47,7 @@ def _check_line(out, nranks, size):
 
 
 def test_bench_self_launch_two_ranks_gloo():
-    out = _run(os.path.join(ROOT, 'tests', 'bench_host_runner.py'), 2, 32)
+    out = _run(os.path.join(ROOT, 'tests', 'bench_host_runner.py'), 2, 32, extra_args=('--full',))
     _check_line(out, 2, 32)
     assert out['config']['grid'] == [2, 1, 1]
     assert [e['ranks'] for e in out['config']['exchange']] == [2]
@@ -66,7 +66,7 @@ def test_bench_self_launch_two_ranks_gloo():
 
 def test_bench_self_launch_four_ranks_measures_routes_and_slab():
     out = _run(os.path.join(ROOT, 'tests', 'bench_host_runner.py'), 4, 32,
-               extra_env={'GFFT_RELAY': 'measure', 'GFFT_RELAY_MIN_BYTES': '0'})
+               extra_env={'GFFT_RELAY': 'measure', 'GFFT_RELAY_MIN_BYTES': '0'}, extra_args=('--full',))
     _check_line(out, 4, 32)
     assert out['config']['grid'] == [2, 2, 1]
     rm = [a for a in out['alternatives'] if a['plan'] == 'measured routes'][0]
@@ -104,7 +104,7 @@ def test_bench_keeps_the_headline_when_an_extra_hangs():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'tests', 'bench_host_runner.py'), '--gpus', '2', '--size', '16',
-           '--no-cpu', '--steps', '1', '--warmup', '0', '--extras-deadline', '5']
+           '--no-cpu', '--steps', '1', '--warmup', '0', '--extras-deadline', '5', '--full']
     res = _launch(cmd, env, 300)
     assert res.returncode == 0, res.stderr[-3000:]
     out_lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -149,7 +149,7 @@ def test_bench_headline_deadline_prints_a_line():
 
 @pytest.mark.gpu
 def test_bench_self_launch_two_processes_share_the_gpu():
-    out = _run(os.path.join(ROOT, 'bench.py'), 2, 128)
+    out = _run(os.path.join(ROOT, 'bench.py'), 2, 128, extra_args=('--full',))
     _check_line(out, 2, 128)
     assert out['config']['grid'] == [2, 1, 1]
     assert out['roofline']['bound'] == 'hbm' and out['roofline']['achieved'] > 0
@@ -162,7 +162,7 @@ def test_bench_single_gpu_line_small():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--size', '128', '--steps', '3', '--warmup', '1',
-                          '--no-cpu'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+                          '--no-cpu', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
     assert res.returncode == 0, res.stderr[-3000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][0])
     assert out['n_gpus'] == 1 and out['roofline']['frac'] > 0 and out['config']['grid'] == [1, 1, 1]
