@@ -76,7 +76,9 @@ int gfft_device_name(int device, char *buf, size_t len);
  * 0: stand-alone passes), with "fuse2_ring" / "fuse2_lag" (slots of the hand-off ring /
  * planes the producer runs ahead; 0 = auto: about 96 MiB of lead and twice that of ring -- 12 / 6 planes of 16 MiB, 24 / 12 of
  * 8 MiB, 48 / 24 of 4 MiB --, launches with too few planes for that stay unfused), "fuse2_kinds" (bit mask of pair kinds:
- * 2 strided->rows, 4 / 16 four-step, 8 batched 2-D, 32 r2c rows->strided, 64 strided->c2r rows), "fuse2_f32" (1: complex64
+ * 2 strided->rows, 4 / 16 four-step, 8 batched 2-D, 32 r2c rows->strided, 64 strided->c2r rows, 128 / 256 the complex slab
+ * pairs of gfft_plan_create_guru2 with blocks, 512 / 1024 the real slab pairs of gfft_plan_create_guru2_real; default 2046 = all
+ * but bit 1, [rows->strided] of the one-rank 3-D schedule), "fuse2_f32" (1: complex64
  * pairs, 2: real fp32 pairs too), "fuse2_n512" (the n = 512 pairs: 0 off, 1 on 16 lines per tile, 2 [strided -> rows] on 32), "fuse2_mixed" (pairs on planes of 512 x 1024 / 1024 x 512 points), "fuse2_f32_n512" (the complex64 n = 512 pairs), "fuse2_wait_ms" (wall-clock limit of a wait inside a fused
  * launch before the launch voids itself, gfft_async_error below; default 2000); GFFT_FUSE2_DEBUG=1 prints a fused
  * launch's counters.  ("debug_tw_index" / "debug_tw_exp": TEST HOOK -- twiddle tables uploaded while debug_tw_exp > 0
@@ -200,6 +202,30 @@ int gfft_plan_create_guru_padded(gfft_plan *plan, int precision, int kind, const
 int gfft_plan_create_guru2(gfft_plan *plan, int precision, int kind, const gfft_iodim *cols, const gfft_iodim *rows,
                            const gfft_iodim *planes, int cols_first, int in_blocks, int64_t in_block_stride,
                            int out_blocks, int64_t out_block_stride);
+/* gfft_plan_create_guru2 for REAL input: the two local stages of a slab-decomposed r2c / c2r transform -- the reference's
+ * default dtype (mpifft.py:202) -- as one plan, ONE launch per direction where a fused pair exists.
+ *   kind = GFFT_R2C: [r2c rows, then cols] -- real planes in, half-spectrum planes (rows of n / 2 + 1 entries) out;
+ *   kind = GFFT_C2R: [cols, then c2r rows] -- the mirror.  The order is fixed.
+ *   rows    rows->n = the REAL length (even), contiguous on both sides (is = os = 1)
+ *   cols    the strided axis: n, is / os = distance between consecutive rows of a plane
+ *   planes  the batch: n planes, is / os = distance between consecutive planes
+ *   Strides count elements of the side they describe: reals on the real side, complex entries on the half-spectrum side
+ *   (real-side strides even: the rows are read / written as complex pairs, element 0 aligned as a pair).
+ *   in_blocks / in_block_stride, out_blocks / out_block_stride: the cols axis stored as that many equal blocks whose starts lie
+ *     that many complex entries apart -- allowed on the HALF-SPECTRUM side only (the output of R2C: the send buffer of the
+ *     redistribution behind the stage pair; the input of C2R: the receive buffer in front of it).  1 = contiguous.
+ * d_in and d_out must not overlap; the input is preserved.  GFFT_ERR_INVALID: non-positive strides, rows of a plane that
+ * overlap, blocks on the real side, more than one block with a block stride below the block's extent (n / blocks rows).
+ * GFFT_ERR_UNSUPPORTED: a length without a single-pass register kernel (rows: 32 ... 8192 reals, powers of two), a block
+ * count that does not fit (a power of two up to 8 dividing cols->n), odd real-side strides, a complex kind.
+ * Fused kernels (kinds FUSED_R2C_PLANES_B / FUSED_COLS_C2R_B, option bits 512 / 1024): fp64 with cols->n = 1024 and rows of
+ * 1024 or 2048 reals (backward 2048: option c2r_2048, on by default), fp32 1024 x 1024 under option fuse2_f32 = 2; everywhere
+ * else -- and after a fused launch gave up a wait -- the plan runs two stand-alone passes with the same results: forward r2c
+ * rows IN -> OUT placed by block, then the strided pass in place on OUT; backward the strided pass IN -> plan workspace, then
+ * the c2r rows -> OUT.  gfft_plan_cost's `launches` tells which. */
+int gfft_plan_create_guru2_real(gfft_plan *plan, int precision, int kind, const gfft_iodim *cols, const gfft_iodim *rows,
+                                const gfft_iodim *planes, int in_blocks, int64_t in_block_stride, int out_blocks,
+                                int64_t out_block_stride);
 /* Layouts of INTERNAL exchange buffers (between two stages of a distributed transform; never of a
  * caller's array, which keeps the reference's C order, pencil.py:347-354).  All three act on one-pass
  * plans (gfft_plan_create_guru, or gfft_plan_create on one axis) and return GFFT_ERR_UNSUPPORTED,

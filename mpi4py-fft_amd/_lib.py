@@ -57,6 +57,8 @@ def _declare(lib):
                                                    c.POINTER(IoDim), c.c_int, c.c_int64, c.c_int, c.c_int64]),
         'gfft_plan_create_guru2': (c.c_int, [c.POINTER(vp), c.c_int, c.c_int, c.POINTER(IoDim), c.POINTER(IoDim), c.POINTER(IoDim),
                                              c.c_int, c.c_int, c.c_int64, c.c_int, c.c_int64]),
+        'gfft_plan_create_guru2_real': (c.c_int, [c.POINTER(vp), c.c_int, c.c_int, c.POINTER(IoDim), c.POINTER(IoDim),
+                                                  c.POINTER(IoDim), c.c_int, c.c_int64, c.c_int, c.c_int64]),
         'gfft_plan_set_tiles': (c.c_int, [vp, c.c_int, c.c_int, c.c_int64]),
         'gfft_plan_set_flat': (c.c_int, [vp, c.c_int64, c.c_int64, c.c_int64]),
         'gfft_plan_set_split_slabs': (c.c_int, [vp, c.c_int, c.c_int, c.c_int64, c.c_int]),
@@ -224,6 +226,21 @@ class HipEngine:
         rc = lib().gfft_plan_create_guru2(ctypes.byref(h), int(precision), int(kind), io(cols), io(rows), io(planes),
                                           1 if cols_first else 0, int(in_blocks), int(in_block_stride), int(out_blocks),
                                           int(out_block_stride))
+        if rc == -2:
+            return None
+        check(rc)
+        return h
+
+    def plan_create_guru2_real(self, precision, kind, cols, rows, planes, in_blocks=1, in_block_stride=0, out_blocks=1,
+                               out_block_stride=0):
+        """plan_create_guru2 for real planes (gfft_plan_create_guru2_real): kind R2C = [r2c rows -> strided], C2R = [strided ->
+        c2r rows]; rows[0] is the real length; strides in reals on the real side, complex entries on the half-spectrum side,
+        blocks on the half-spectrum side only.  None when the engine has no single-pass kernels for it; `plan_cost(h)[2]`
+        tells whether it runs as one launch or two."""
+        h = ctypes.c_void_p()
+        io = lambda d: ctypes.byref(IoDim(*[int(x) for x in d]))
+        rc = lib().gfft_plan_create_guru2_real(ctypes.byref(h), int(precision), int(kind), io(cols), io(rows), io(planes),
+                                               int(in_blocks), int(in_block_stride), int(out_blocks), int(out_block_stride))
         if rc == -2:
             return None
         check(rc)

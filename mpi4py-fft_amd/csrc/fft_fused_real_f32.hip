@@ -3,6 +3,8 @@
 // schedule, [strided n = 1024 -> packed-real c2r rows] on the planes i1 of the c2r schedule -- 1024^3 real fp32, the
 // single-GPU relative of BASELINE config C5.  1024-thread workgroups: rows 16 values per thread (c2r: 8, the R = 16
 // c2r plan needs ~170 VGPRs), strided 32 values per thread on 32 columns (256-byte segments).
+// FUSED_R2C_PLANES_B / FUSED_COLS_C2R_B: the same pairs as the two local stages of a real slab-decomposed transform
+// (gfft_plan_create_guru2_real), the strided side in equal blocks of the all-to-all buffer (FLAGS 65536 output / 32768 input).
 #include "fft_fused_impl.h"
 
 namespace gfft {
@@ -12,16 +14,18 @@ typedef PassCfg<float, 512, 16, 32, false, false, 1 | 2048 | 8192, MODE_R2C_H, f
 typedef PassCfg<float, 512, 8, 16, false, false, 2 | 4096 | 8192, MODE_C2R_H, false, 8, 8, 8> C2RRows512FromRingF32;
 typedef PassCfg<float, 1024, 32, 32, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 16, 16, 4> Cols1024ToRingF32;
 typedef PassCfg<float, 1024, 32, 32, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> Cols1024FromRingF32;
+typedef PassCfg<float, 1024, 32, 32, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 16, 16, 4> Cols1024ToRingBF32;
+typedef PassCfg<float, 1024, 32, 32, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 16, 16, 4> Cols1024FromRingBF32;
 
 bool fused2_real_supported_f32(int kind, int n_a, int n_b) {
-  if (kind == FUSED_R2C_PLANES) return n_a == 512 && n_b == 1024;
-  if (kind == FUSED_COLS_C2R) return n_a == 1024 && n_b == 512;
+  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) return n_a == 512 && n_b == 1024;
+  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) return n_a == 1024 && n_b == 512;
   return false;
 }
 
 int fused2_real_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *ta, int *tb) {
-  if (kind == FUSED_R2C_PLANES) { *ta = (int)R2CRows512ToRingF32::ntiles(dA); *tb = (int)Cols1024FromRingF32::ntiles(dB); return 0; }
-  if (kind == FUSED_COLS_C2R) { *ta = (int)Cols1024ToRingF32::ntiles(dA); *tb = (int)C2RRows512FromRingF32::ntiles(dB); return 0; }
+  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) { *ta = (int)R2CRows512ToRingF32::ntiles(dA); *tb = (int)Cols1024FromRingF32::ntiles(dB); return 0; }
+  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) { *ta = (int)Cols1024ToRingF32::ntiles(dA); *tb = (int)C2RRows512FromRingF32::ntiles(dB); return 0; }
   return -1;
 }
 
@@ -29,6 +33,8 @@ hipError_t launch_fused2_real_f32(int kind, const PassDesc &dA, const PassDesc &
                                   const void *in, void *ring, void *out, hipStream_t s) {
   if (kind == FUSED_R2C_PLANES) return launch_fused2<R2CRows512ToRingF32, Cols1024FromRingF32>(dA, dB, dev, f, in, ring, out, s);
   if (kind == FUSED_COLS_C2R) return launch_fused2<Cols1024ToRingF32, C2RRows512FromRingF32>(dA, dB, dev, f, in, ring, out, s);
+  if (kind == FUSED_R2C_PLANES_B) return launch_fused2<R2CRows512ToRingF32, Cols1024FromRingBF32>(dA, dB, dev, f, in, ring, out, s);
+  if (kind == FUSED_COLS_C2R_B) return launch_fused2<Cols1024ToRingBF32, C2RRows512FromRingF32>(dA, dB, dev, f, in, ring, out, s);
   return hipErrorInvalidValue;
 }
 

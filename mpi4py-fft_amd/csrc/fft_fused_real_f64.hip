@@ -3,6 +3,9 @@
 //                     its n1 rows are contiguous in the caller's array, the half spectrum (N + 1 entries, the row's last
 //                     line completed with zeros) goes into the slot, the strided pass takes it along axis 1
 //   FUSED_COLS_C2R    [strided n -> packed-real c2r rows]                passes 2 + 3 of the c2r schedule, plane = one i1
+//   FUSED_R2C_PLANES_B / FUSED_COLS_C2R_B   the same pairs as the two LOCAL stages of a real slab-decomposed transform
+//                     (gfft_plan_create_guru2_real): the strided side is the all-to-all buffer, its axis cut into equal blocks
+//                     (FLAGS 65536 output / 32768 input, fft_pow2_body.inc), rows exactly N + 1 entries apart there
 // The reference's default dtype is `float` (mpifft.py:202), i.e. these are the transforms a PFFT runs unless told otherwise
 // (libfft.py:48-79, fftw/xfftn.py:173-326: the Hermitian axis is the last one, N / 2 + 1 entries).
 // Rows: 16 values per thread, a row inside one wave (exchanges without barriers); strided: 32 values per thread, one
@@ -26,21 +29,27 @@ typedef PassCfg<double, 512, 16, 16, false, true, 2 | 4096 | 8192, MODE_C2R_H, f
 typedef PassCfg<double, 1024, 16, 8, false, true, 2 | 4096 | 8192, MODE_C2R_H, false, 16, 16, 4> C2RRows1024FromRing;     // 2048 reals per row (option c2r_2048)
 typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 32> Cols1024ToRing;
 typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 32, 32> Cols1024FromRing;
+// the strided side of the slab pairs: the array side in equal blocks of the strided axis (the complex pairs' ColsToRingB / ColsFromRingB)
+typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 32> Cols1024ToRingB;
+typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 32, 32> Cols1024FromRingB;
 
 bool fused2_real_supported_f64(int kind, int n_a, int n_b) {
-  if (kind == FUSED_R2C_PLANES) return (n_a == 512 || n_a == 1024) && n_b == 1024;
-  if (kind == FUSED_COLS_C2R && n_a == 1024 && n_b == 1024) return g_c2r_2048 != 0;
-  if (kind == FUSED_COLS_C2R) return n_a == 1024 && n_b == 512;
+  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) return (n_a == 512 || n_a == 1024) && n_b == 1024;
+  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) {
+    if (n_a == 1024 && n_b == 1024) return g_c2r_2048 != 0;
+    return n_a == 1024 && n_b == 512;
+  }
   return false;
 }
 
 int fused2_real_tiles_f64(int kind, const PassDesc &dA, const PassDesc &dB, int *ta, int *tb) {
-  if (kind == FUSED_R2C_PLANES) {
+  // (the _B kinds: same tile shapes -- the block jump changes addresses, not tiles)
+  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) {
     *ta = (int)(dA.n == 512 ? R2CRows512ToRing::ntiles(dA) : R2CRows1024ToRing::ntiles(dA));
     *tb = (int)Cols1024FromRing::ntiles(dB);
     return 0;
   }
-  if (kind == FUSED_COLS_C2R) {
+  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) {
     *ta = (int)Cols1024ToRing::ntiles(dA);
     if (dB.n == 1024) { *tb = (int)C2RRows1024FromRing::ntiles(dB); return 0; }
     *tb = (int)C2RRows512FromRing::ntiles(dB);
@@ -58,6 +67,14 @@ hipError_t launch_fused2_real_f64(int kind, const PassDesc &dA, const PassDesc &
   if (kind == FUSED_COLS_C2R) {
     if (dB.n == 1024) return launch_fused2<Cols1024ToRing, C2RRows1024FromRing>(dA, dB, dev, f, in, ring, out, s);
     return launch_fused2<Cols1024ToRing, C2RRows512FromRing>(dA, dB, dev, f, in, ring, out, s);
+  }
+  if (kind == FUSED_R2C_PLANES_B) {
+    if (dA.n == 512) return launch_fused2<R2CRows512ToRing, Cols1024FromRingB>(dA, dB, dev, f, in, ring, out, s);
+    return launch_fused2<R2CRows1024ToRing, Cols1024FromRingB>(dA, dB, dev, f, in, ring, out, s);
+  }
+  if (kind == FUSED_COLS_C2R_B) {
+    if (dB.n == 1024) return launch_fused2<Cols1024ToRingB, C2RRows1024FromRing>(dA, dB, dev, f, in, ring, out, s);
+    return launch_fused2<Cols1024ToRingB, C2RRows512FromRing>(dA, dB, dev, f, in, ring, out, s);
   }
   return hipErrorInvalidValue;
 }

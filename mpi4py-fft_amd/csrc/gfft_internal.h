@@ -196,7 +196,14 @@ enum FusedKind { FUSED_ROWS_COLS = 0, FUSED_COLS_ROWS = 1, FUSED_FOURSTEP = 2, F
                  // the two LOCAL stages of a slab-decomposed transform, plane by plane, with the all-to-all buffer addressed by
                  // the pair itself (gfft_plan_create_guru2): [rows -> strided, output in blocks] forward, [strided, input in
                  // blocks -> rows] backward -- the kernels of 3 / 1 with the block jump of the transformed axis kept (FLAGS 65536 / 32768)
-                 FUSED_PLANES_2D_B = 7, FUSED_PLANES_CR_B = 8 };
+                 FUSED_PLANES_2D_B = 7, FUSED_PLANES_CR_B = 8,
+                 // ... of a REAL slab-decomposed transform (gfft_plan_create_guru2_real): the kernels of 5 / 6 with the block jump of the
+                 // strided axis kept on the half-spectrum side -- [r2c rows -> strided, output in blocks] forward, [strided, input in
+                 // blocks -> c2r rows] backward (fft_fused_real_f64.hip / _f32.hip)
+                 FUSED_R2C_PLANES_B = 9, FUSED_COLS_C2R_B = 10 };
+inline bool fused_kind_real(int kind) {
+  return kind == FUSED_R2C_PLANES || kind == FUSED_COLS_C2R || kind == FUSED_R2C_PLANES_B || kind == FUSED_COLS_C2R_B;
+}
 // variant: 1 = the default kernels (32 values per thread, one exchange, one 512-thread workgroup per CU); 3 = the round-3
 // kernels (16 values per thread, two exchanges, 1024 threads); 2 / 4 = (make VARIANTS=1) 8 lines per tile, two workgroups per CU
 extern int g_fuse2_n512;           // option fuse2_n512: the n = 512 pairs (fft_fused_f64.hip)
@@ -214,7 +221,7 @@ bool fused2_supported_f32(int kind, int n_a, int n_b);
 int fused2_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
 hipError_t launch_fused2_f32(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f,
                              const void *in, void *ring, void *out, hipStream_t s);
-// ... the two real kinds (n_a / n_b: the passes' lengths -- COMPLEX length of the packed-real rows)
+// ... the real kinds (n_a / n_b: the passes' lengths -- COMPLEX length of the packed-real rows)
 bool fused2_real_supported_f64(int kind, int n_a, int n_b);
 int fused2_real_tiles_f64(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
 hipError_t launch_fused2_real_f64(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f,

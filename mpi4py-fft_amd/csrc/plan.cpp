@@ -77,7 +77,7 @@ struct Options {
   int plane2d = 1;           // planes of 32^2 / 64^2 points: both passes in one launch, the plane in LDS (fft_plane2d.hip; 0: two passes, A/B)
   int fuse2 = 1;             // pass pairs in one persistent launch, handed over through the Infinity Cache (fft_fused_f64.hip)
   int fuse2_ring = 0, fuse2_lag = 0;   // slots of the hand-off ring / planes the producer runs ahead; 0 = auto (make_fused2)
-  int fuse2_kinds = 510;     // which pairs (bit = FusedKind): measured per kind, see make_fused2
+  int fuse2_kinds = 2046;    // which pairs (bit = FusedKind): measured per kind, see make_fused2 (bits 1-10; 0, [rows -> strided] of the 3-D schedule, off)
   int fuse2_f32 = 1;         // 1: complex64 pairs (fft_fused_f32.hip); 2: the real fp32 pairs too (fft_fused_real_f32.hip: measured level, off)
   int fuse2_wait_ms = 2000;  // wall-clock limit of one wait inside a fused launch before the launch is voided (0: at once -- test hook)
   int debug_tile_lg = 0, debug_tile_side = 0, debug_tile_stride = 0;   // gfft_debug_pass: tile-major lines (rows passes)
@@ -590,7 +590,7 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
     variant = 5;
   // (complex64 pairs are on by default since round 4 -- option fuse2_f32 = 1, profiles/r04_ab_fuse2_f32.txt; the real fp32
   // pairs measured level with their stand-alone passes and need fuse2_f32 = 2)
-  const bool real_kind = kind == FUSED_R2C_PLANES || kind == FUSED_COLS_C2R;
+  const bool real_kind = fused_kind_real(kind);
   const bool f32 = pl->precision == GFFT_F32;
   if (f32 && (!opts().fuse2_f32 || (real_kind && opts().fuse2_f32 < 2))) return false;
   if (f32 ? (real_kind ? !fused2_real_supported_f32(kind, dA.n, dB.n) : !fused2_supported_f32(kind, dA.n, dB.n))
@@ -1757,6 +1757,111 @@ static int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, con
   return GFFT_OK;
 }
 
+// The same for REAL planes (gfft_plan_create_guru2_real, see there): forward [packed-real r2c rows -> strided], backward
+// [strided -> packed-real c2r rows], the strided pass addressing the blocks of the half-spectrum side.  `cx` is the
+// half-spectrum side (strides in complex entries), `re` the real side (strides in reals, even: the rows are read / written
+// as complex pairs); nb / bstride: the blocks of the strided axis on the half-spectrum side.
+static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np, int64_t re_es, int64_t re_plane, int64_t cx_es,
+                             int64_t cx_plane, int nb, int64_t bstride, bool inverse) {
+  const int prec = pl->precision;
+  const int64_t esz = 2 * (int64_t)prec, m = n2 / 2, H = m + 1, per = n1 / nb;
+  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
+  // the hand-off slot (and the workspace of the stand-alone backward form): rows of H entries rounded up to whole 128-byte
+  // lines, pitched off multiples of 2 KiB and off 129 x 2^k entries (plan_fused3)
+  const int64_t seg = 128 / esz, Pu = (H + seg - 1) / seg * seg;
+  int64_t P = Pu;
+  {
+    auto odd = [](int64_t x) { while (x && !(x & 1)) x >>= 1; return x; };
+    while (odd(P) == 129 || (P * esz) % 2048 == 0) P += seg;
+  }
+  // rows: packed-real, complex length m, the real side in pairs
+  Pass pr;
+  pr.regk = true;
+  pr.logical_first = true;
+  pr.d.n = (int)m;
+  pr.d.mode = inverse ? MODE_C2R_H : MODE_R2C_H;
+  pr.d.conj_in = 0;
+  pr.d.conj_out = inverse ? 1 : 0;
+  pr.d.in_es = pr.d.out_es = 1;
+  pr.d.scale = 1.0;
+  // strided: complex length n1 along the H columns of a plane; the last tile of columns is masked by `inner` itself (the fused
+  // kernels drop inner_ld / inner_st, FLAGS 8192), so nothing is read or written beyond column H - 1 on either side
+  Pass pc;
+  pc.regk = true;
+  pc.cols = true;
+  pc.logical_first = true;
+  pc.d.n = (int)n1;
+  pc.d.mode = MODE_C2C;
+  pc.d.conj_in = pc.d.conj_out = inverse ? 1 : 0;
+  pc.d.batch = np * H;
+  pc.d.mid = 1;
+  pc.d.inner = H;
+  pc.d.in_is = pc.d.out_is = 1;
+  pc.d.scale = 1.0;
+  const int lgp = nb > 1 ? lg2(nb) : 0;
+  const int64_t jump = nb > 1 ? bstride - per * cx_es : 0;
+  if (!inverse) {
+    // IN (real) -> OUT: row r of plane o = (block r / per, row r % per of the block) placed by the block stride
+    pr.d.batch = np * n1;  pr.d.mid = nb;  pr.d.inner = per;
+    pr.d.in_os = re_plane / 2;  pr.d.in_ms = per * re_es / 2;  pr.d.in_is = re_es / 2;
+    pr.d.out_os = cx_plane;  pr.d.out_ms = nb > 1 ? bstride : per * cx_es;  pr.d.out_is = cx_es;
+    pr.src = BUF_IN;  pr.dst = BUF_OUT;
+    // ... then the strided pass in place on OUT
+    pc.d.in_os = pc.d.out_os = cx_plane;
+    pc.d.in_es = pc.d.out_es = cx_es;
+    pc.d.in_lgp = pc.d.out_lgp = lgp;  pc.d.in_jump = pc.d.out_jump = jump;
+    pc.blocks[0] = pc.blocks[1] = nb;  pc.bstride[0] = pc.bstride[1] = nb > 1 ? bstride : 0;
+    pc.src = BUF_OUT;  pc.dst = BUF_OUT;
+  } else {
+    // strided IN -> WS[plane][row][P] (the caller's input is preserved, and OUT -- real -- is smaller than the half spectrum)
+    pc.d.in_os = cx_plane;  pc.d.in_es = cx_es;  pc.d.in_lgp = lgp;  pc.d.in_jump = jump;
+    pc.d.out_os = n1 * P;  pc.d.out_es = P;
+    pc.blocks[0] = nb;  pc.bstride[0] = nb > 1 ? bstride : 0;
+    pc.src = BUF_IN;  pc.dst = BUF_WS;
+    // ... then the c2r rows WS -> OUT (real)
+    pr.d.batch = np * n1;  pr.d.mid = 1;  pr.d.inner = n1;
+    pr.d.in_os = n1 * P;  pr.d.in_is = P;
+    pr.d.out_os = re_plane / 2;  pr.d.out_is = re_es / 2;
+    pr.src = BUF_WS;  pr.dst = BUF_OUT;
+  }
+  int rc = get_twiddles(m, prec, &pr.d.tw);
+  if (!rc) rc = get_twiddles(2 * m, prec, &pr.d.rtw);
+  if (!rc) rc = get_twiddles(n1, prec, &pc.d.tw);
+  if (rc) return rc;
+  // work model (plan_fused3's): half the flops of a complex line on the real axis, one read + one write per pass
+  pl->flops = 0.5 * 5.0 * (double)n2 * std::log2((double)n2) * (double)(np * n1) + 5.0 * (double)n1 * std::log2((double)n1) * (double)(np * H);
+  pl->bytes = (double)(np * n1) * ((double)n2 * prec + (double)H * esz) + (double)(np * H) * 2.0 * (double)n1 * esz;
+  // ... as ONE persistent launch, plane by plane through the Infinity Cache: slot[row of the plane][P]
+  bool fused = false;
+  if (np < ((int64_t)1 << 30)) {
+    Pass f;
+    if (!inverse) {
+      PassDesc dA = pr.d, dB = pc.d;      // r2c rows of one plane: IN -> slot (the row's last line completed with zeros); strided: slot -> blocks
+      dA.batch = n1;  dA.mid = 1;  dA.inner = 1;  dA.in_os = re_es / 2;  dA.in_ms = 0;  dA.in_is = 0;
+      dA.out_os = P;  dA.out_ms = 0;  dA.out_is = 0;  dA.out_pad = (int)(Pu - H);
+      dB.batch = H;  dB.in_os = 0;  dB.out_os = 0;  dB.in_es = P;  dB.in_lgp = 0;  dB.in_jump = 0;
+      fused = make_fused2(pl, FUSED_R2C_PLANES_B, pr, pc, dA, dB, (int)np, re_plane * prec, cx_plane * esz, n1 * P * esz, &f);
+    } else {
+      PassDesc dA = pc.d, dB = pr.d;      // strided: blocks -> slot;  c2r rows of one plane: slot -> OUT
+      dA.batch = H;  dA.in_os = 0;  dA.out_os = 0;  dA.out_es = P;
+      dB.batch = n1;  dB.inner = 1;  dB.in_os = P;  dB.in_is = 0;  dB.out_os = re_es / 2;  dB.out_is = 0;
+      fused = make_fused2(pl, FUSED_COLS_C2R_B, pc, pr, dA, dB, (int)np, cx_plane * esz, re_plane * prec, n1 * P * esz, &f);
+      if (fused) f.alt_bytes = (size_t)(np * n1 * P * esz);     // (the workspace only the stand-alone form needs)
+    }
+    if (fused) {
+      f.bytes2 = pl->bytes;
+      pl->passes.push_back(f);
+    }
+  }
+  if (!fused) {
+    if (inverse) need(pl, BUF_WS, (size_t)(np * n1 * P * esz));
+    if (!inverse) { pl->passes.push_back(pr); pl->passes.push_back(pc); }
+    else { pl->passes.push_back(pc); pl->passes.push_back(pr); }
+  }
+  pl->passes.back().carries_scale = true;
+  return GFFT_OK;
+}
+
 extern "C" {
 
 const char *gfft_strerror(int status) {
@@ -2160,11 +2265,11 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
       }
       static const int debug = getenv("GFFT_FUSE2_DEBUG") ? atoi(getenv("GFFT_FUSE2_DEBUG")) : 0;
       if (debug) { f.wait_ticks = 100000u; f.host_flag = nullptr; f.debug = (unsigned)debug; }      // (1 ms; counters printed below)
-      if (pl->precision == GFFT_F32 && (p.fused_kind == FUSED_R2C_PLANES || p.fused_kind == FUSED_COLS_C2R))
+      if (pl->precision == GFFT_F32 && fused_kind_real(p.fused_kind))
         HIP_TRY(launch_fused2_real_f32(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
       else if (pl->precision == GFFT_F32)
         HIP_TRY(launch_fused2_f32(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
-      else if (p.fused_kind == FUSED_R2C_PLANES || p.fused_kind == FUSED_COLS_C2R)
+      else if (fused_kind_real(p.fused_kind))
         HIP_TRY(launch_fused2_real_f64(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
       else
         HIP_TRY(launch_fused2_f64(p.fused_kind, p.fused_variant, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
@@ -2226,7 +2331,8 @@ int gfft_plan_pass_info(gfft_plan pl, int i, char *buf, size_t len, double *byte
   if (p.kind == PK_FUSED2) {
     // two axis passes in one launch: the algorithmic bytes of both (one read + one write of the array each)
     static const char *fk[] = {"fused rows+cols", "fused cols+rows", "fused four-step", "fused 2-D rows+cols", "fused four-step (rows)",
-                               "fused r2c-rows+cols", "fused cols+c2r-rows", "fused 2-D rows+cols(blocks)", "fused 2-D cols(blocks)+rows"};
+                               "fused r2c-rows+cols", "fused cols+c2r-rows", "fused 2-D rows+cols(blocks)", "fused 2-D cols(blocks)+rows",
+                               "fused 2-D r2c-rows+cols(blocks)", "fused 2-D cols(blocks)+c2r-rows"};
     snprintf(buf, len, "%s n=%dx%d", fk[p.fused_kind], p.d.n, p.d2.n);
     if (bytes) *bytes = p.bytes2 > 1 ? p.bytes2 : (double)p.fused.planes * 2.0 * pl->precision *
                         ((double)p.d.batch * 2.0 * p.d.n + (double)p.d2.batch * 2.0 * p.d2.n);
@@ -2531,6 +2637,52 @@ int gfft_plan_create_guru2(gfft_plan *plan, int precision, int kind, const gfft_
   return GFFT_OK;
 }
 
+/* The two local stages of a REAL slab-decomposed transform as one plan (see include/gfft.h). */
+int gfft_plan_create_guru2_real(gfft_plan *plan, int precision, int kind, const gfft_iodim *cols, const gfft_iodim *rows,
+                                const gfft_iodim *planes, int in_blocks, int64_t in_block_stride, int out_blocks,
+                                int64_t out_block_stride) {
+  if (!plan || !cols || !rows || !planes) return fail(GFFT_ERR_INVALID, "null argument");
+  *plan = nullptr;
+  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
+  if (kind != GFFT_R2C && kind != GFFT_C2R) return fail(GFFT_ERR_UNSUPPORTED, "guru2_real plans are r2c / c2r (complex pairs: gfft_plan_create_guru2)");
+  const bool inverse = kind == GFFT_C2R;
+  const int64_t n1 = cols->n, n2 = rows->n, np = planes->n;
+  if (n1 < 1 || n2 < 1 || np < 1) return fail(GFFT_ERR_INVALID, "bad length");
+  if (rows->is != 1 || rows->os != 1) return fail(GFFT_ERR_UNSUPPORTED, "the row axis must be contiguous on both sides");
+  if (cols->is < 1 || cols->os < 1 || planes->is < 1 || planes->os < 1) return fail(GFFT_ERR_INVALID, "strides must be positive");
+  if (in_blocks < 1 || out_blocks < 1) return fail(GFFT_ERR_INVALID, "bad block count");
+  if ((inverse ? out_blocks : in_blocks) > 1) return fail(GFFT_ERR_INVALID, "blocks on the half-spectrum side only (R2C: output, C2R: input)");
+  // the two sides in their own elements: reals on the real side, complex entries on the half-spectrum side
+  const int64_t H = n2 / 2 + 1;
+  const int64_t re_es = inverse ? cols->os : cols->is, re_plane = inverse ? planes->os : planes->is;
+  const int64_t cx_es = inverse ? cols->is : cols->os, cx_plane = inverse ? planes->is : planes->os;
+  const int nb = inverse ? in_blocks : out_blocks;
+  const int64_t bstride = inverse ? in_block_stride : out_block_stride;
+  if (re_es < n2 || cx_es < H) return fail(GFFT_ERR_INVALID, "rows of a plane overlap (row stride below the row's length)");
+  if (nb > 1 && n1 % nb == 0 && bstride < (n1 / nb) * cx_es) return fail(GFFT_ERR_INVALID, "block stride smaller than the block's extent");
+  int rc = check_device();
+  if (rc) return rc;
+  if (n2 % 2 || n2 / 2 > 4096 || !real_half_supported((int)(n2 / 2)) || !regk_ok(n1, precision) || mixv_supported((int)n1))
+    return fail(GFFT_ERR_UNSUPPORTED, "no single-pass register kernel for one of the lengths");
+  const int max_blocks = is_pow2(n1) ? (n1 >= 32 ? 8 : 4) : 4;            // whole thread slots per block (gfft_plan_set_split)
+  if ((nb & (nb - 1)) || nb > max_blocks || n1 % nb) return fail(GFFT_ERR_UNSUPPORTED, "block count not supported for this length");
+  if (re_es % 2 || re_plane % 2) return fail(GFFT_ERR_UNSUPPORTED, "real-side strides must be even (rows are read as complex pairs)");
+  if ((double)np * (double)n1 >= 2147483648.0 || (double)np * (double)H >= 2147483648.0) return fail(GFFT_ERR_UNSUPPORTED, "batch exceeds 2^31");
+  gfft_plan_s *pl = new gfft_plan_s;
+  pl->ndims = 0;
+  pl->kind = kind;
+  pl->precision = precision;
+  pl->variant_rows = opts().variant_rows;
+  pl->variant_cols = opts().variant_cols;
+  pl->mixv_variant = opts().mixv_variant;
+  pl->xcd_swizzle = opts().xcd_swizzle;
+  rc = build_pair2d_real(pl, n1, n2, np, re_es, re_plane, cx_es, cx_plane, nb, bstride, inverse);
+  if (rc) { delete pl; return rc; }
+  *plan = pl;
+  ++g_live_plans;
+  return GFFT_OK;
+}
+
 /* Tile-major layouts of exchange buffers (see include/gfft.h). */
 int gfft_plan_set_tiles(gfft_plan pl, int side, int tile, int64_t tile_stride) {
   if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
@@ -2656,7 +2808,8 @@ int gfft_plan_describe(gfft_plan pl, char *buf, size_t len) {
   for (const Pass &p : pl->passes) {
     if (p.kind == PK_FUSED2) {
       static const char *fk[] = {"rows -> strided", "strided -> rows", "four-step", "2-D planes: rows -> strided", "four-step: strided -> rows, transposed on store",
-                                 "r2c rows -> strided", "strided -> c2r rows", "2-D planes: rows -> strided into blocks", "2-D planes: strided from blocks -> rows"};
+                                 "r2c rows -> strided", "strided -> c2r rows", "2-D planes: rows -> strided into blocks", "2-D planes: strided from blocks -> rows",
+                                 "2-D planes: r2c rows -> strided into blocks", "2-D planes: strided from blocks -> c2r rows"};
       if (pl->fused_off)
         snprintf(line, sizeof line, "  pair (%s) n=%d then n=%d as two stand-alone passes (a fused launch gave up a wait)%s  %s -> %s\n",
                  fk[p.fused_kind], p.d.n, p.d2.n, p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);

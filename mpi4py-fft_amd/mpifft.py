@@ -507,6 +507,9 @@ class PFFT:
         grids -- (2,1,1), (8,1,1) -- are where this applies: their first two stages are local.  The stage objects,
         `len(self.xfftn) == len(self.axes)` and the stage arrays stay; the shared middle buffer is simply not touched.
         Taken only where libgfft runs the pair as one launch (else the two stage plans are the same work).
+        Real input (the reference's default dtype): the r2c stage leads, so only the first pair can be real -- [r2c rows
+        -> strided, into the send buffer] forward, [strided, from the receive buffer -> c2r rows] backward, the order fixed
+        (gfft_plan_create_guru2_real); its complex side has rows of H = N2 / 2 + 1 entries.
         Returns ({position: callable} forward, {position: callable} backward) for the two Transforms."""
         from . import _lib
         eng = _lib.engine()
@@ -519,6 +522,11 @@ class PFFT:
             tr = self.transfer[i]
             a, b = self.xfftn[i], self.xfftn[i + 1]
             U, W, V = a.forward.input_array, a.forward.output_array, b.forward.output_array
+            pair = self._real_pair(eng, i) if i == 0 and np.dtype(U.dtype).kind == 'f' else None
+            if pair is not None:
+                fwd[i], bck[L - 2 - i] = pair
+                i += 2
+                continue
             ok = (tr.comm.Get_size() == 1 and len(U.shape) == 3 and tuple(a.axes) == (2,) and tuple(b.axes) == (1,)
                   and not a._padded and not b._padded and np.dtype(U.dtype).kind == 'c'
                   and W.data_ptr == b.forward.input_array.data_ptr and U.data_ptr != V.data_ptr
@@ -556,6 +564,49 @@ class PFFT:
             bck[L - 2 - i] = backward
             i += 2
         return fwd, bck
+
+    def _real_pair(self, eng, i):
+        """The real branch of _fuse_pairs at stage pair (i, i + 1): (forward, backward) callables, or None."""
+        from . import _lib
+        tr = self.transfer[i]
+        a, b = self.xfftn[i], self.xfftn[i + 1]
+        U, W, V = a.forward.input_array, a.forward.output_array, b.forward.output_array
+        if not hasattr(eng, 'plan_create_guru2_real') or len(U.shape) != 3:
+            return None
+        N0, N1, N2 = (int(n) for n in U.shape)
+        H = N2 // 2 + 1
+        ok = (tr.comm.Get_size() == 1 and tuple(a.axes) == (2,) and tuple(b.axes) == (1,) and not a._padded and not b._padded
+              and np.dtype(W.dtype).kind == 'c' and np.dtype(W.dtype) == np.dtype(V.dtype)
+              and _lib.precision_of(W.dtype) == _lib.precision_of(U.dtype)
+              and W.data_ptr == b.forward.input_array.data_ptr
+              and tuple(W.shape) == tuple(V.shape) == (N0, N1, H))
+        if not ok:
+            return None
+        p = 1
+        if i + 1 < len(self.transfer) and self.transfer[i + 1].packedA:
+            p = self.transfer[i + 1].comm.Get_size()
+        nb = N1 // p
+        plane_out, bstride = (nb * H, N0 * nb * H) if p > 1 else (N1 * H, 0)
+        prec = _lib.precision_of(U.dtype)
+        hf = eng.plan_create_guru2_real(prec, _lib.R2C, (N1, N2, H), (N2, 1, 1), (N0, N1 * N2, plane_out), 1, 0, p, bstride)
+        hb = None if hf is None else eng.plan_create_guru2_real(prec, _lib.C2R, (N1, H, N2), (N2, 1, 1), (N0, plane_out, N1 * N2),
+                                                                p, bstride, 1, 0)
+        if hf is None or hb is None or eng.plan_cost(hf)[2] != 1 or eng.plan_cost(hb)[2] != 1:
+            for h in (hf, hb):
+                if h is not None:
+                    eng.plan_destroy(h)
+            return None
+        self._pair_plans += [hf, hb]
+        M = a.M * b.M
+
+        def forward(src=None, dst=None, hf=hf, U=U, V=V, M=M, **kw):
+            eng.execute_ptr(hf, (U if src is None else src).data_ptr, (V if dst is None else dst).data_ptr,
+                            M if kw.pop('normalize', True) else 1.0)
+
+        def backward(src=None, dst=None, hb=hb, U=U, V=V, M=M, **kw):
+            eng.execute_ptr(hb, (V if src is None else src).data_ptr, (U if dst is None else dst).data_ptr,
+                            M if kw.pop('normalize', False) else 1.0)
+        return forward, backward
 
     def _plan_fused(self):
         """All ranks-local case (one GPU): every stage's redistribution is the identity, so the

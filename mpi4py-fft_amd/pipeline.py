@@ -274,16 +274,25 @@ class _PairStage:
     round, its strided pass storing into the blocks, is level in complex128 -- 4.73 against 4.78 ms at (512,1024,1024) --
     and 9 % behind in complex64, profiles/r06_stage_probe_slab.txt; it measured 5.5 ms while the compiler serialised its
     ring loads, which tools/scan_serial_loads.py found.)  The stage on the far side transforms axis 0 and takes the chunks
-    all at once (_FarStage)."""
-    def __init__(self, shape, p, K, E, forward, precision):
+    all at once (_FarStage).
+    `real`: the stages of an r2c / c2r transform -- [r2c rows, then the strided pass storing into the blocks] forward,
+    [strided pass reading the blocks, then c2r rows] backward (gfft_plan_create_guru2_real: the order is fixed) --, the
+    natural side real (N0c, N1, N2), the buffer side rows of N2 / 2 + 1 complex entries, E apart per plane."""
+    def __init__(self, shape, p, K, E, forward, precision, real=False):
         N0, N1, N2 = (int(v) for v in shape)
         N0c = N0 // K
         eng = _lib.engine()
         self.plan = None
         self.launches = 0
-        if not hasattr(eng, 'plan_create_guru2'):
+        if not hasattr(eng, 'plan_create_guru2_real' if real else 'plan_create_guru2'):
             return
-        if forward:
+        if real:
+            H = N2 // 2 + 1
+            if forward:
+                h = eng.plan_create_guru2_real(precision, _lib.R2C, (N1, N2, H), (N2, 1, 1), (N0c, N1 * N2, E), 1, 0, p, N0c * E)
+            else:
+                h = eng.plan_create_guru2_real(precision, _lib.C2R, (N1, H, N2), (N2, 1, 1), (N0c, E, N1 * N2), p, N0c * E, 1, 0)
+        elif forward:
             h = eng.plan_create_guru2(precision, -1, (N1, N2, N2), (N2, 1, 1), (N0c, N1 * N2, E), True, 1, 0, p, N0c * E)
         else:
             h = eng.plan_create_guru2(precision, +1, (N1, N2, N2), (N2, 1, 1), (N0c, E, N1 * N2), True, p, N0c * E, 1, 0)
@@ -294,7 +303,7 @@ class _PairStage:
         self.nchunks = K
         self.iter_side = 'out' if forward else 'in'
         isz = 2 * precision
-        nat_step, buf_step = N0c * N1 * N2 * isz, p * N0c * E * isz
+        nat_step, buf_step = N0c * N1 * N2 * (precision if real else isz), p * N0c * E * isz
         self.step_in, self.step_out = (nat_step, buf_step) if forward else (buf_step, nat_step)
         side = type('Side', (), dict(K=K, p=p))()
         natural = type('Side', (), dict(K=1, p=1))()
@@ -687,9 +696,9 @@ class Pipeline:
                              widths=[_blockdist(t.shape[a], p, r)[0] for r in range(p)] if uneven else None))
         if all(e['p'] == 1 for e in plan):
             return None
-        if (len(stages) == 3 and plan[0]['p'] == 1 and plan[1]['p'] > 1 and not real0 and not any(x._padded for x in stages)
+        if (len(stages) == 3 and plan[0]['p'] == 1 and plan[1]['p'] > 1 and not any(x._padded for x in stages)
                 and os.environ.get('GFFT_FUSE_PAIRS', '1') != '0' and (layout or os.environ.get('GFFT_PIPE_LAYOUT', 'aligned')) == 'aligned'):
-            pair = cls._build_slab_pair(pfft, plan[1], dtype)
+            pair = cls._build_slab_pair(pfft, plan[1], dtype, real0)
             if pair is not None:
                 return pair
 
@@ -842,10 +851,11 @@ class Pipeline:
         return self
 
     @classmethod
-    def _build_slab_pair(cls, pfft, e, dtype):
+    def _build_slab_pair(cls, pfft, e, dtype, real=False):
         """Slab grids -- (2,1,1), (8,1,1): the first redistribution stays on the rank -- as [axis 2 + axis 1 in one launch per
         chunk of planes] -> redistribution over all ranks -> [axis 0] (see _PairStage).  None where libgfft has no fused
-        pair for the shape (the caller then builds the stage-by-stage pipeline)."""
+        pair for the shape (the caller then builds the stage-by-stage pipeline).  `real`: an r2c chain, its first stage's
+        input real (N0, N1, N2), everything behind it rows of N2 / 2 + 1 complex entries."""
         import torch
         stages = pfft.xfftn
         eng = _lib.engine()
@@ -857,22 +867,25 @@ class Pipeline:
             return None
         sh0 = tuple(int(v) for v in s0.forward.input_array.shape)
         sh2 = tuple(int(v) for v in s2.forward.input_array.shape)
-        if tuple(int(v) for v in s1.forward.input_array.shape) != sh0 or tuple(int(v) for v in s1.forward.output_array.shape) != sh0:
-            return None
         N0, N1, N2 = sh0
+        sh1 = (N0, N1, N2 // 2 + 1) if real else sh0          # the complex planes between the pair's two passes
+        if real and tuple(int(v) for v in s0.forward.output_array.shape) != sh1:
+            return None
+        if tuple(int(v) for v in s1.forward.input_array.shape) != sh1 or tuple(int(v) for v in s1.forward.output_array.shape) != sh1:
+            return None
         M0, N1b, W = sh2
-        if M0 != p * N0 or N1 != p * N1b or W != N2:
+        if M0 != p * N0 or N1 != p * N1b or W != sh1[2]:
             return None                                     # both cut axes split evenly: every rank cuts the same slabs
         isz = dtype.itemsize
         prec = _lib.precision_of(dtype)
         E = _pitch(N1b * W, isz)
         # chunks of planes: as many as the exchange policy allows among those the pair still runs as ONE launch on
         # (a launch needs planes enough for its hand-off ring, plan.cpp fused2_ring)
-        nbytes = N0 * N1 * N2 * isz
+        nbytes = N0 * N1 * sh1[2] * isz
         cands = [k for k in range(min(cls.CHUNKS, N0), 1, -1) if N0 % k == 0 and nbytes // k >= cls.MIN_CHUNK_BYTES] + [1]
         pf = pb = None
         for K in cands:
-            pf, pb = _PairStage(sh0, p, K, E, True, prec), _PairStage(sh0, p, K, E, False, prec)
+            pf, pb = _PairStage(sh0, p, K, E, True, prec, real), _PairStage(sh0, p, K, E, False, prec, real)
             if pf.launches == 1 and pb.launches == 1:
                 break
             pf.destroy()
@@ -899,7 +912,7 @@ class Pipeline:
         e['B'] = dict(sizes=[N0c * E * isz] * p, chunk_stride=N0c * E * isz, peer_stride=N0 * E * isz)
         self.tplan = [e]
         dev = s0.forward.input_array.tensor.device
-        tdt = s0.forward.input_array.tensor.dtype
+        tdt = s2.forward.input_array.tensor.dtype           # (complex, whatever the pair's natural side is)
         send = torch.empty(K * p * N0c * E, dtype=tdt, device=dev)
         recv = torch.empty(M0 * E, dtype=tdt, device=dev)
         self.in_buf = [s0.forward.input_array.tensor, recv]

@@ -5,6 +5,8 @@ exchange buffers (pipeline._Aligned) and on the C-order ones of round 2.
 
   python tools/stage_probe.py [slab|c4|c5|c5odd|all]     (c5odd = a rank of the 513-wide grid column; slab = C3, C4 on 2 ranks
   and C4 on the (8,1,1) grid: the two local stages as two launches against one fused launch, round 6)
+  python tools/stage_probe.py realslab     (the same for REAL input: [r2c rows -> strided] / [strided -> c2r rows] as the two
+  stand-alone plans the staged path runs against gfft_plan_create_guru2_real whole and per chunk, forms alternating, round 7)
 """
 import os, sys
 from types import SimpleNamespace as NS
@@ -136,6 +138,61 @@ def run_slab(name, prec, N0, N1, N2, p, Ks=(1, 2, 4)):
     torch.cuda.empty_cache()
 
 
+def run_real_slab(name, prec, N0, N1, N2, p, Ks=(1, 2, 4), rounds=3):
+    """The per-rank local stages of a REAL transform on a slab grid: two stand-alone plans -- packed-real r2c rows natural ->
+    natural half spectrum, then the strided pass into the packed send buffer [block][plane][rows of the block][H] (what
+    _fuse_packs makes the staged path run); backward the mirror -- against the pair (pipeline._PairStage(real=True),
+    gfft_plan_create_guru2_real) whole and per chunk of planes.  Every form is timed once per round, the rounds alternate
+    the forms in one process; the best of each is reported with its ratio to the two launches."""
+    isz = 2 * prec
+    eng = _lib.engine()
+    rdt, cdt = (torch.float32, torch.complex64) if prec == 4 else (torch.float64, torch.complex128)
+    H = N2 // 2 + 1
+    N1b = N1 // p
+    E = P._pitch(N1b * H, isz)
+    rows = N0 * N1
+    x = torch.randn(rows * N2, dtype=rdt, device='cuda')
+    y = torch.empty(rows * N2, dtype=rdt, device='cuda')
+    mid = torch.empty(rows * H, dtype=cdt, device='cuda')
+    b = torch.randn(max(p * N0 * E, rows * H), dtype=cdt, device='cuda')
+    alg = rows * (N2 * prec + 3 * H * isz)          # r2c rows (real in, half spectrum out) + strided (read + write)
+    forms = {}
+    hr_f = eng.plan_create((rows, N2), (rows, H), (1,), _lib.R2C, prec)
+    hr_b = eng.plan_create((rows, H), (rows, N2), (1,), _lib.C2R, prec)
+    hc_f = eng.plan_create_guru(prec, -1, (N1, H, H), [(N0, N1 * H, N1b * H), (H, 1, 1)], 1, 0, p, N0 * N1b * H)
+    hc_b = eng.plan_create_guru(prec, +1, (N1, H, H), [(N0, N1b * H, N1 * H), (H, 1, 1)], p, N0 * N1b * H, 1, 0)
+    forms[('fwd', 'two launches')] = lambda: (eng.execute_ptr(hr_f, x.data_ptr(), mid.data_ptr(), 1.0),
+                                               eng.execute_ptr(hc_f, mid.data_ptr(), b.data_ptr(), 1.0))
+    forms[('bwd', 'two launches')] = lambda: (eng.execute_ptr(hc_b, b.data_ptr(), mid.data_ptr(), 1.0),
+                                               eng.execute_ptr(hr_b, mid.data_ptr(), y.data_ptr(), 1.0))
+    stages = []
+    for K in Ks:
+        if N0 % K:
+            continue
+        for fwd in (True, False):
+            st = P._PairStage((N0, N1, N2), p, K, E, fwd, prec, real=True)
+            if st.plan is None:
+                continue
+            stages.append(st)
+            pin, pout = (x, b) if fwd else (b, y)
+            forms[('fwd' if fwd else 'bwd', 'pair K=%d (%d launch%s per chunk)' % (K, st.launches, '' if st.launches == 1 else 'es'))] = \
+                (lambda st=st, pin=pin, pout=pout: [st.execute(eng, q, pin.data_ptr(), pout.data_ptr(), 1.0) for q in range(st.nchunks)])
+    best = {k: float('inf') for k in forms}
+    for _ in range(rounds):
+        for k, fn in forms.items():
+            best[k] = min(best[k], timeit(fn))
+    for (d, tag), t in best.items():
+        ratio = t / best[(d, 'two launches')]
+        print('%-18s %s %-34s %8.3f ms  %7.1f GB/s  %4.1f %%  %.3f x two launches' % (
+            name, d, tag, t, alg / t / 1e6, alg / t / 1e6 / 80, ratio), flush=True)
+    for h in (hr_f, hr_b, hc_f, hc_b):
+        eng.plan_destroy(h)
+    for st in stages:
+        st.destroy()
+    del x, y, mid, b
+    torch.cuda.empty_cache()
+
+
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else 'all'
     print(torch.cuda.get_device_name(0))
@@ -152,6 +209,16 @@ def main():
         run_slab('c64 (8,1,1)', 4, 128, 1024, 1024, 8)
         if what == 'slab':
             return
+    if what == 'realslab':
+        cases = [('r C4@2', 8, 512, 1024, 1024, 2), ('r (8,1,1)', 8, 128, 1024, 1024, 8), ('r 2048 (8,1,1)', 8, 64, 1024, 2048, 8),
+                 ('r f32 (8,1,1)', 4, 128, 1024, 1024, 8)]
+        only = os.environ.get('STAGE_PROBE_CASE')        # one case per process
+        for c in cases:
+            if only and only != c[0]:
+                continue
+            _lib.set_option('fuse2_f32', 2 if c[1] == 4 else 1)       # (the real fp32 pairs: option fuse2_f32 = 2)
+            run_real_slab(*c)
+        return
     if what in ('c4', 'all'):
         run_case('C4@8', 8, False, (256, 512, 1024), 1024, (256, 1024, 512), (1024, 256, 512), 2, 4, None, 4, 4)
     if what in ('c5', 'all'):
