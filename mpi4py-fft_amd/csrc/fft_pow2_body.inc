@@ -31,6 +31,13 @@
   // (32768: on the input side, 65536: on the output side -- the other side of such a pass is the hand-off ring; with both kept
   // the compiler waited for every ring load before it issued the next, tools/scan_serial_loads.py: chains of 29 / 32)
   constexpr bool BLK_IN = (FLAGS & 32768) != 0, BLK_OUT = (FLAGS & 65536) != 0;
+  // FLAGS & 131072: the order IN TIME of a tile's rows follows PassDesc::order (see there) -- which thread takes which
+  // row, and from which slot q0 on a thread issues its loads and stores.  Addresses, values and operations per element
+  // are those of the plain order.  Plain strided complex passes on natural lines only.
+  constexpr bool ORDER = (FLAGS & 131072) != 0;
+  static_assert(!ORDER || (COLS && !BIGTW && GEO::UNIFORM && MODE == MODE_C2C && !(FLAGS & (16 | 32 | 128 | 2048 | 4096)) &&
+                           (NTL & (NTL - 1)) == 0 && RL % 4 == 0 && RL == RS),
+                "row orders: plain strided complex passes");
   // Conjugation-on-load applied once, BEHIND the loads, in the unequal-width stage kernels where -- applied to each value as it
   // arrives -- the compiler waited for every load before it issued the next (serial_loads_f64, fft_pow2_impl.h).  Packed-real
   // rows never conjugate on load (conj_in = 0: half_desc, plan_fused3 rows): no sign at all there.
@@ -85,6 +92,12 @@
     // (twiddle-table offsets k*step, LDS slots, mirrored c2r offsets) is loop invariant, and
     // hoisted it sits in -- or spills from -- 2 VGPRs per use for the whole kernel.
     int tl = t;
+    [[maybe_unused]] int ord_q0 = 0;      // (ORDER: the slot the tile's loads and stores start from, in quarters of RL; uniform)
+    if constexpr (ORDER) {
+      const unsigned rot = ((unsigned)d.order >> 14) & 3u, ways = ((unsigned)d.order >> 12) & 3u;
+      if (rot) tl = (int)(((unsigned)t + ord_hash * (rot == 1 ? 5u : 4u)) & (unsigned)(NTL - 1));
+      ord_q0 = ways == 2 ? (int)(ord_hash & 3u) : (ways == 1 ? (int)((ord_hash & 1u) * 2u) : 0);
+    }
     asm volatile("" : "+v"(tl));
     bool valid, valid_st;
     unsigned o, m, i;
@@ -136,7 +149,29 @@
     const int seg_in = RL >> L_in_lgp, seg_out = RS >> L_out_lgp;
     if constexpr (NTL < NT) valid = valid && t < NTL;               // (thread rows beyond the load / store geometry)
     if constexpr (NTS < NT) valid_st = valid_st && t < NTS;
-    if (valid) {
+    if constexpr (ORDER) {
+      // (every slot index a constant: one unrolled copy of the loop per rotation, picked by a uniform branch)
+      if (valid) {
+        const int64_t idx0 = in0 + (int64_t)tl * d.in_es;
+        auto issue = [&](auto q0c) {
+          constexpr int Q0 = decltype(q0c)::value;
+#pragma unroll
+          for (int i = 0; i < RL; ++i) {
+            const int q = (i + Q0) % RL;
+            v[q] = tile_load<real, IOMODE, (FLAGS & 1) != 0>(d, in, in0, idx0 + (int64_t)q * q_in, tl + q * NTL, sy_in);
+          }
+        };
+        switch (ord_q0) {
+          default: issue(std::integral_constant<int, 0>()); break;
+          case 1: issue(std::integral_constant<int, RL / 4>()); break;
+          case 2: issue(std::integral_constant<int, RL / 2>()); break;
+          case 3: issue(std::integral_constant<int, 3 * RL / 4>()); break;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < R; ++q) v[q] = {0, 0};
+      }
+    } else if (valid) {
       int64_t idx = in0 + t_in;
       int cnt = 0;
 #pragma unroll
@@ -340,6 +375,24 @@
       // (barrier-free exchanges: a wave running ahead must not start the next tile's exchange in a region the
       // others are still reading)
       if constexpr (WL) __syncthreads();
+    } else if constexpr (ORDER) {
+      if (valid_st) {
+        const int64_t idx0 = out0 + (int64_t)tl * d.out_es;
+        auto issue = [&](auto q0c) {
+          constexpr int Q0 = decltype(q0c)::value;
+#pragma unroll
+          for (int i = 0; i < RS; ++i) {
+            const int q = (i + Q0) % RS;
+            tile_store<real, IOMODE, false, (FLAGS & 2) != 0>(d, out, idx0 + (int64_t)q * q_out, tl + q * NTS, m, v[q], sx_out, sy_out);
+          }
+        };
+        switch (ord_q0) {
+          default: issue(std::integral_constant<int, 0>()); break;
+          case 1: issue(std::integral_constant<int, RS / 4>()); break;
+          case 2: issue(std::integral_constant<int, RS / 2>()); break;
+          case 3: issue(std::integral_constant<int, 3 * RS / 4>()); break;
+        }
+      }
     } else if (valid_st) {
       int64_t idx = out0 + t_out;
       int cnt = 0;

@@ -160,7 +160,11 @@ hipError_t launch_pow2_f64(const PassDesc &d, bool cols, int variant, const void
           // (profiles/r04_ab_cols_r32.txt); the C4-on-8-GPUs stages (256,1024,512) axis 1 0.87 -> 0.80-0.82 ms and
           // (1024,256,512) axis 0 0.98-1.01 -> 0.85-0.91 ms (54 -> 59-63 % of 8 TB/s; profiles/r04_variant_cols_r32.txt).
           // Under REAL 3-D schedules it loses 1.5-3 % (profiles/r04_real_pairs.txt): plan_fused3 asks for 17 there.
-          default: return P64F(1024, 32, 16, true, 2, 8 | 3, 32, 32);
+          // (d.order, PassDesc: the same kernel with its tiles and rows re-ordered in time -- a kernel of its own, so that the plain
+          // order keeps its code; plan.cpp run_pass sets it for the stand-alone pass of the complex 3-D schedule only)
+          default:
+            if (d.order) return P64F(1024, 32, 16, true, 2, 8 | 3 | 131072, 32, 32);
+            return P64F(1024, 32, 16, true, 2, 8 | 3, 32, 32);
           case 15: return P64F(1024, 32, 16, true, 2, 8, 32, 32);     // ... with plain loads and stores
           case 17: return P64F(1024, 16, 16, true, 4, 8, 16, 16, 4);  // 16 values per thread, radices 16.16.4, 1024 threads, <= 128 VGPRs (rounds 1-3)
 #ifdef GFFT_VARIANTS
@@ -171,6 +175,7 @@ hipError_t launch_pow2_f64(const PassDesc &d, bool cols, int variant, const void
           case 5: return P64F(1024, 8, 8, true, 1, 4, 8, 8, 8, 2);      // access pattern only, T=8
           case 6: return P64F(1024, 8, 8, true, 1, 7, 8, 8, 8, 2);      // ... with nt loads/stores
           case 10: return P64F(1024, 16, 16, true, 4, 4, 16, 16, 4);    // access pattern only, T=16
+          case 11: return P64F(1024, 32, 16, true, 2, 4 | 8 | 3 | 131072, 32, 32);   // access pattern only of the DEFAULT kernel (512 threads, non-temporal), in the order d.order (tools/tile_order_probe.py)
           case 12: return P64F(1024, 16, 16, true, 4, 8, 8, 8, 8, 2);
           case 13: return P64F(1024, 16, 16, true, 4, 8 | 2, 16, 16, 4);   // non-temporal stores
           case 14: return P64F(1024, 16, 16, true, 4, 8 | 3, 16, 16, 4);   // non-temporal loads and stores

@@ -1146,7 +1146,7 @@ __device__ __forceinline__ void pow2_body(const PassDesc &d, const void *__restr
                                           unsigned xcd_base, double scale, HOOK &&after_loads = HOOK()) {
 #define GFFT_SCALE scale
 #define GFFT_TILE_LOOP for (unsigned k = k_first; k < k_end; k += k_step)
-#define GFFT_TILE_INDEX const unsigned tile = xcd_base + k;
+#define GFFT_TILE_INDEX const unsigned tile = xcd_base + k; [[maybe_unused]] const unsigned ord_hash = 0;
 #define GFFT_AFTER_LOADS after_loads();
 #include "fft_pow2_body.inc"
 #undef GFFT_TILE_LOOP
@@ -1167,7 +1167,27 @@ fft_pow2_kernel(PassDesc d, const void *__restrict__ in, void *__restrict__ out)
   const unsigned per_xcd = (pow2_ntiles<T, COLS, BIGTW>(d) + 7) / 8;
   const unsigned kstep = d.swizzle ? gridDim.x / 8 : gridDim.x;
 #define GFFT_TILE_LOOP for (unsigned k = d.swizzle ? blockIdx.x / 8 : blockIdx.x; k < (d.swizzle ? per_xcd : ntiles); k += kstep)
-#define GFFT_TILE_INDEX const unsigned tile = d.swizzle ? (blockIdx.x % 8) * per_xcd + k : k;
+  // Kernels built with FLAGS & 131072 re-order the XCD-contiguous walk IN TIME by d.order (PassDesc::order; the host sets it
+  // only where the walk covers whole planes of `chunks` tiles, launch_pow2_one): the eight XCDs otherwise work, at every
+  // moment, on tiles exactly ntiles / 8 apart -- 2 GiB at 1024^3 complex128 -- and on the same rows of them.
+  // `ord_hash` drives the row orders of the tile (fft_pow2_body.inc).
+#define GFFT_TILE_INDEX                                                                                              \
+  unsigned tile = d.swizzle ? (blockIdx.x % 8) * per_xcd + k : k;                                                    \
+  [[maybe_unused]] unsigned ord_hash = 0;                                                                            \
+  if constexpr ((FLAGS & 131072) != 0) {                                                                             \
+    if (d.order && d.swizzle) {                                                                                      \
+      const unsigned x = blockIdx.x % 8, il = 1u << (((unsigned)d.order >> 16) & 3u);                                \
+      const unsigned apart = (((unsigned)d.order >> 19) & 127u) ? (((unsigned)d.order >> 19) & 127u) : 37u;          \
+      unsigned kk = k;                                                                                               \
+      if (il > 1) {                                                                                                  \
+        const unsigned g = k % il, r = k / il, j = r % chunks, s = (r / chunks) * il + g;                            \
+        kk = ((s * apart) % (per_xcd / chunks)) * chunks + j;                                                        \
+      }                                                                                                              \
+      kk = (kk + x * ((unsigned)d.order & 4095u)) % per_xcd;                                                         \
+      tile = x * per_xcd + kk;                                                                                       \
+      ord_hash = (((unsigned)d.order >> 18) & 1u) ? x + k : x;                                                       \
+    }                                                                                                                \
+  }
 #define GFFT_AFTER_LOADS
 #define GFFT_SCALE d.scale
 #include "fft_pow2_body.inc"
@@ -1496,6 +1516,17 @@ hipError_t launch_pow2_one(const PassDesc &d, const void *in, void *out, hipStre
   PassDesc dd = d;
   if (dd.swizzle) {
     if (grid >= 64) grid = grid / 8 * 8; else dd.swizzle = 0;
+  }
+  // tile / row orders (PassDesc::order): XCD-contiguous walks over whole planes of a natural-layout batch only
+  if constexpr ((FLAGS & 131072) != 0 && COLS && !BIGTW) {
+    const int64_t chunks = (d.inner + T - 1) / T, il = (int64_t)1 << ((d.order >> 16) & 3);
+    const int64_t apart = ((d.order >> 19) & 127) ? ((d.order >> 19) & 127) : 37;
+    int64_t a = ntiles / 8 / chunks, b = apart;        // (the planes of an XCD are walked in steps of `apart`: coprime, or the walk is no permutation)
+    while (b) { const int64_t r = a % b; a = b; b = r; }
+    if (!dd.swizzle || d.flat || d.in_lgp || d.out_lgp || ntiles % 8 || (ntiles / 8) % (il * chunks) || (il > 1 && a != 1))
+      dd.order = 0;
+  } else {
+    dd.order = 0;
   }
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, dd, in, out);
   return hipGetLastError();

@@ -41,6 +41,13 @@ struct PassDesc {
   int conj_in;    // conjugate on load   (inverse transform = conj . forward . conj)
   int conj_out;   // conjugate on store
   int swizzle;    // XCD-contiguous tile order (speed only)
+  // Order IN TIME of the tiles of an XCD-contiguous walk and of the rows of a tile (speed only: no byte, address or
+  // operation changes -- kernels built with FLAGS & 131072, fft_pow2_impl.h; 0 = the plain order).  Bits 0-11: XCD x starts
+  // x * (these bits) tiles into its eighth and wraps; bits 12-13: a tile issues its loads / stores from slot q0 on, one of
+  // 2 (1) or 4 (2) rotations by the tile's hash; bits 14-15: thread rows rotate by 5 (1) or 4 (2) times the hash; bits
+  // 16-17: the tiles an XCD runs together come from 2 (1), 4 (2) or 8 (3) planes, bits 19-25 (0 = 37) planes apart; bit 18:
+  // the hash is XCD + position in the walk instead of the XCD alone
+  int order;
   // fused 3/2-rule adapters (register kernels): 0 none, 1 truncate on store, 2 zero-pad on load
   int tr_dir, tr_n, tr_N, tr_even;
   // ... with the TRUNCATED side being an all-to-all buffer of 2^k equal blocks of the kept entries

@@ -67,6 +67,7 @@ struct Options {
   int variant_cols = 0;
   int force_generic = 0;
   int xcd_swizzle = -1;      // XCD-contiguous tile order in the pow2 kernels: 0 off, 1 on, -1 auto
+  int tile_order = -1;       // order in time of tiles and rows inside an XCD-contiguous walk (PassDesc::order): -1 = each plan's own, >= 0: this one (0 = plain); read at launch time (A/B on one plan)
   int profile = 0;           // record HIP events around every pass (bench.py roofline leg)
   int fused3 = 1;            // reorder + padded-pitch workspace for 3-D all-axes plans
   int debug_flat = 0;        // gfft_debug_pass: tiles over the flattened (mid, inner) index
@@ -402,6 +403,7 @@ struct gfft_plan_s {
   size_t region_bytes[BUF_COUNT] = {0, 0, 0, 0, 0, 0, 0};   // WS / FS / AUX / RING / FS2 sizes
   double flops = 0, bytes = 0;
   int variant_rows = 0, variant_cols = 0, xcd_swizzle = 0;
+  int tile_order = -1;                         // plan_fused3: PassDesc::order of the stand-alone strided passes; -1 = not a schedule that takes one
   bool fused3 = false;
   int mixv_variant = 0;                        // option mixv_variant at plan time (fft_mixv_*.hip: measured alternatives)
   int64_t ws_pitch = 0;                        // plan_fused3: entries between consecutive rows of the workspace
@@ -1593,6 +1595,16 @@ int plan_fused3(gfft_plan_s *pl) {
   // 19.00, 512^3 c128 4.17 -> 4.07, 1024^3 r2c f64 18.65 -> 18.48; level for real fp32 and 512^3 c64, +0.8 % at 768^3
   // (3^b 2^k kernels: left on automatic).  On natural-stride stage arrays (C4 on 8 GPUs) it LOSES 2-8 %: only here.
   if (pl->xcd_swizzle < 0 && is_pow2(n0) && is_pow2(n1) && is_pow2(n2) && !(real && prec == GFFT_F32)) pl->xcd_swizzle = 1;
+  // The order IN TIME of that walk (PassDesc::order, option tile_order): complex fp64 power-of-two schedules may take one
+  // (their stand-alone pass at n = 1024 has the kernel for it, fft_pow2_f64.hip); 0 = the plain order.  Measured at 1024^3
+  // (tools/tile_order_probe.py, profiles/r08_tile_order_probe.txt: orders alternating on the same arrays, ten array sets, both
+  // directions): the tiles an XCD runs together taken from TWO planes three planes apart instead of one -- the pass 5.99 -> 5.74 ms
+  // forward, 5.92 -> 5.72 ms backward, better on every array set (-0.16 ... -0.26 ms); 37 / 63 / 127 planes apart -0.13 ... -0.22,
+  // neighbouring planes -0.05, four or eight planes level or worse.  XCD start offsets and rotated row orders: level or worse
+  // (+-0.03, +0.04 ... +0.13 ms).  The kernel's ACCESS PATTERN ALONE loses under the same order (+0.13 ms): the gain is not in
+  // the placement of the requests.  Only that shape was measured: only it takes the order by default.
+  if (prec == GFFT_F64 && !real && !tr && is_pow2(n0) && is_pow2(n1) && is_pow2(n2))
+    pl->tile_order = (n0 == 1024 && n1 == 1024 && n2 == 1024) ? ((1 << 16) | (3 << 19)) : 0;
   // Workgroups per launch.  Each walks tiles block, block + grid, ...; more, shorter walks balance the
   // tail better, too many lose the overlap of one tile's stores with the next one's loads.  Clean A/B
   // on fixed caller arrays (tools/ab_option_probe.py grid_cap ...), fwd + bwd per step: 1024^3 c128
@@ -1633,6 +1645,8 @@ hipError_t run_pass(const gfft_plan_s *pl, const Pass &p, const PassDesc &d0, co
   if (!d.grid_cap && p.regk && p.cols && !pl->fused3 && opts().grid_cap <= 0 && d.mid == 1 && !d.flat && !d.in_lgp &&
       d.in_es >= ((int64_t)1 << 16) && (d.in_es & (d.in_es - 1)) == 0) d.grid_cap = 16384;
   d.swizzle = pl->xcd_swizzle >= 0 ? pl->xcd_swizzle : (p.cols && !d.flat && ((d.out_es * esz_out) % 128 != 0) ? 1 : 0);
+  // (the order in time of that walk: the plan's own, or option tile_order -- read here, at launch time, so that one plan runs both forms)
+  d.order = (pl->tile_order >= 0 && p.regk && p.cols && d.swizzle) ? (opts().tile_order >= 0 ? opts().tile_order : pl->tile_order) : 0;
   if ((d.mode == MODE_R2C_H || d.mode == MODE_C2R_H) && real_half_supported(d.n))
     return pl->precision == 8 ? launch_real_half_f64(d, pl->variant_rows, in, out, s)
                               : launch_real_half_f32(d, pl->variant_rows, in, out, s);
@@ -1932,6 +1946,7 @@ int gfft_set_option(const char *key, int value) {
   else if (!strcmp(key, "debug_tw_index")) opts().debug_tw_index = value;
   else if (!strcmp(key, "debug_tw_exp")) opts().debug_tw_exp = value;
   else if (!strcmp(key, "xcd_swizzle")) opts().xcd_swizzle = value;
+  else if (!strcmp(key, "tile_order")) opts().tile_order = value;
   else if (!strcmp(key, "fused3_min_mib")) opts().fused3_min_bytes = (int64_t)value << 20;
   else return fail(GFFT_ERR_INVALID, std::string("unknown option ") + key);
   return GFFT_OK;

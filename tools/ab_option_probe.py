@@ -11,7 +11,7 @@ opt = sys.argv[1]
 values = [int(x) for x in sys.argv[2].split(',')]
 dt = sys.argv[3] if len(sys.argv) > 3 else 'D'
 n = int(sys.argv[4]) if len(sys.argv) > 4 else 1024
-default = {'grid_cap': 0, 'xcd_swizzle': -1}.get(opt, 0)
+default = {'grid_cap': 0, 'xcd_swizzle': -1, 'tile_order': -1}.get(opt, 0)
 print(torch.cuda.get_device_name(0), opt, dt, n)
 ffts = {}
 for v in values:
@@ -24,7 +24,7 @@ tot = {v: [] for v in values}
 for rnd in range(5):
     for v in values:
         f = ffts[v]
-        if opt == 'grid_cap':
+        if opt in ('grid_cap', 'tile_order'):
             _lib.set_option(opt, v)          # read at launch time
         f.forward(u, w); f.backward(w, u)
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
