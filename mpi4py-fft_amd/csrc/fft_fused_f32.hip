@@ -9,8 +9,8 @@
 namespace gfft {
 
 //                          real   N     R   T   COLS   SPLIT  FLAGS                  MODE      BIGTW  radices
-typedef PassCfg<float, 1024, 32, 32, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 16, 16, 4> ColsToRingF32;      // 32 columns = 256-byte segments
-typedef PassCfg<float, 1024, 16, 16, false, false, 2 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> RowsFromRingF32;    // a row per wave
+typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 16, 16, 4> ColsToRingF32;      // 32 columns = 256-byte segments
+typedef PassCfg<float, 1024, 16, 16, false, false, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 16, 16, 4> RowsFromRingF32;    // a row per wave
 
 // Round 5: the other kinds on the same two tile shapes -- 32 adjacent columns on 32 values per thread (256-byte hand-off
 // segments), 16 rows with a row inside one wave --: the four-step pair of a length-2^20 transform and the batched 2-D pair
@@ -22,12 +22,12 @@ typedef PassCfg<float, 1024, 16, 16, false, false, 2 | 4096 | 8192, MODE_C2C, fa
 // Half the bytes per butterfly of complex128: the LDS exchanges (4-byte planes, twice the DS instructions per byte) and the
 // butterflies weigh twice as much in a tile, and one resident workgroup per CU cannot overlap them with its memory phases.
 struct Fused1024F32 {
-  typedef PassCfg<float, 1024, 16, 16, false, false, 1 | 2048 | 8192, MODE_C2C, false, 16, 16, 4> RowsToRing;
-  typedef PassCfg<float, 1024, 32, 32, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> ColsFromRing;
-  typedef PassCfg<float, 1024, 32, 32, true, true, 1 | 32 | 2048 | 8192, MODE_C2C, true, 16, 16, 4> FourStepFirst;
-  // the strided side of the slab pairs: the array side is an all-to-all buffer of equal blocks (FLAGS 32768 input / 65536 output, FUSED_PLANES_2D_B / _CR_B)
-  typedef PassCfg<float, 1024, 32, 32, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 16, 16, 4> ColsToRingB;
-  typedef PassCfg<float, 1024, 32, 32, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 16, 16, 4> ColsFromRingB;
+  typedef PassCfg<float, 1024, 16, 16, false, false, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 16, 16, 4> RowsToRing;
+  typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 16, 16, 4> ColsFromRing;
+  typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_LOAD | PF_TRANSPOSE_STORE | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 16, 16, 4> FourStepFirst;
+  // the strided side of the slab pairs: the array side is an all-to-all buffer of equal blocks (PF_BLOCKS_IN / PF_BLOCKS_OUT, FUSED_PLANES_2D_B / _CR_B)
+  typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 16, 16, 4> ColsToRingB;
+  typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 16, 16, 4> ColsFromRingB;
 };
 
 // Round 6: n = 512, [strided -> rows], both tiles on 32 values per thread / radices 32 x 16 = ONE exchange, 512 threads of up to 256 VGPRs (167, no
@@ -37,9 +37,9 @@ struct Fused1024F32 {
 // fwd + bwd step 2.436 -> 2.172 ms.  (First form, not kept: 8 rows per tile with a row inside one wave on 8 values per thread -- 32 KiB row
 // tiles, four times the tickets: the pair LOST 5-26 %.)  Option fuse2_f32_n512.
 struct Fused512F32 {
-  typedef PassCfg<float, 512, 32, 32, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 16> ColsToRing;
-  typedef PassCfg<float, 512, 32, 32, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 16> ColsToRingB;
-  typedef PassCfg<float, 512, 32, 32, false, false, 2 | 4096 | 8192, MODE_C2C, false, 32, 16> RowsFromRing;
+  typedef PassCfg<float, 512, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 16> ColsToRing;
+  typedef PassCfg<float, 512, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 16> ColsToRingB;
+  typedef PassCfg<float, 512, 32, 32, false, false, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 16> RowsFromRing;
 };
 int g_fuse2_f32_n512 = 1;
 

@@ -10,7 +10,7 @@
 namespace gfft {
 
 //                                  real   N     R   T   COLS   SPLIT FLAGS                 MODE      BIGTW  radices
-// (FLAGS 1 / 2: the streams that are NOT the hand-off -- A's loads, B's stores -- are non-temporal, so that
+// (PF_NT_LOAD / PF_NT_STORE: the streams that are NOT the hand-off -- A's loads, B's stores -- are non-temporal, so that
 // they do not push the ring out of the Infinity Cache: 1024^3 per step 37.35 -> 36.26 ms, clean A/B)
 // Measured and NOT kept (tools/ab_option_probe.py fuse2 0,1 <dtype> <n>, fwd + bwd per step): fp64 n = 512
 // (512^3: 5.03 ms unfused, 7.01 fused; four-step 2^18: 0.90 -> 1.32 ms) -- a 128 KiB tile is over in ~10 us, so
@@ -23,24 +23,24 @@ namespace gfft {
 // CU leaves between load, butterflies and store; measured slower (21.0 / 20.4 ms against 18.5 / 19.1 per
 // 1024^3 direction: its hand-off accesses are 128-byte pieces at system scope)
 struct Fused1024x8 {
-  typedef PassCfg<double, 1024, 16, 8, false, true, 1 | 2048 | 8192, MODE_C2C, false, 16, 16, 4> RowsToRing;
-  typedef PassCfg<double, 1024, 16, 8, false, true, 2 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> RowsFromRing;
-  typedef PassCfg<double, 1024, 16, 8, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 16, 16, 4> ColsToRing;
-  typedef PassCfg<double, 1024, 16, 8, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> ColsFromRing;
-  typedef PassCfg<double, 1024, 16, 8, true, true, 1 | 32 | 2048 | 8192, MODE_C2C, true, 16, 16, 4> FourStepFirst;
-  typedef PassCfg<double, 1024, 16, 8, true, true, 1 | 2048 | 8192, MODE_C2C, true, 16, 16, 4> FourStepFirstNat;
-  typedef PassCfg<double, 1024, 16, 8, false, true, 2 | 32 | 4096 | 8192, MODE_C2C, false, 16, 16, 4> RowsFromRingT;
+  typedef PassCfg<double, 1024, 16, 8, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 16, 16, 4> RowsToRing;
+  typedef PassCfg<double, 1024, 16, 8, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 16, 16, 4> RowsFromRing;
+  typedef PassCfg<double, 1024, 16, 8, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 16, 16, 4> ColsToRing;
+  typedef PassCfg<double, 1024, 16, 8, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 16, 16, 4> ColsFromRing;
+  typedef PassCfg<double, 1024, 16, 8, true, true, PF_NT_LOAD | PF_TRANSPOSE_STORE | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 16, 16, 4> FourStepFirst;
+  typedef PassCfg<double, 1024, 16, 8, true, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 16, 16, 4> FourStepFirstNat;
+  typedef PassCfg<double, 1024, 16, 8, false, true, PF_NT_STORE | PF_TRANSPOSE_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 16, 16, 4> RowsFromRingT;
 };
 // variant 4: the two ideas together -- 8 lines per tile AND one exchange (32 values per thread): 256-thread workgroups of
 // up to 256 VGPRs, two per CU
 struct Fused1024x8R32 {
-  typedef PassCfg<double, 1024, 32, 8, false, true, 1 | 2048 | 8192, MODE_C2C, false, 32, 32> RowsToRing;
-  typedef PassCfg<double, 1024, 32, 8, false, true, 2 | 4096 | 8192, MODE_C2C, false, 32, 32> RowsFromRing;
-  typedef PassCfg<double, 1024, 32, 8, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 32> ColsToRing;
-  typedef PassCfg<double, 1024, 32, 8, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 32, 32> ColsFromRing;
-  typedef PassCfg<double, 1024, 32, 8, true, true, 1 | 32 | 2048 | 8192, MODE_C2C, true, 32, 32> FourStepFirst;
-  typedef PassCfg<double, 1024, 32, 8, true, true, 1 | 2048 | 8192, MODE_C2C, true, 32, 32> FourStepFirstNat;
-  typedef PassCfg<double, 1024, 32, 8, false, true, 2 | 32 | 4096 | 8192, MODE_C2C, false, 32, 32> RowsFromRingT;
+  typedef PassCfg<double, 1024, 32, 8, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 32> RowsToRing;
+  typedef PassCfg<double, 1024, 32, 8, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> RowsFromRing;
+  typedef PassCfg<double, 1024, 32, 8, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 32> ColsToRing;
+  typedef PassCfg<double, 1024, 32, 8, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> ColsFromRing;
+  typedef PassCfg<double, 1024, 32, 8, true, true, PF_NT_LOAD | PF_TRANSPOSE_STORE | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 32> FourStepFirst;
+  typedef PassCfg<double, 1024, 32, 8, true, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 32> FourStepFirstNat;
+  typedef PassCfg<double, 1024, 32, 8, false, true, PF_NT_STORE | PF_TRANSPOSE_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> RowsFromRingT;
 };
 #endif
 
@@ -48,40 +48,40 @@ struct Fused1024x8R32 {
 // barriers on the strided tiles instead of 8), on 512-thread workgroups (8 waves, up to 256 VGPRs each); same 16 lines
 // per tile, same 256-byte hand-off segments
 struct Fused1024R32 {
-  typedef PassCfg<double, 1024, 32, 16, false, true, 1 | 2048 | 8192, MODE_C2C, false, 32, 32> RowsToRing;
-  typedef PassCfg<double, 1024, 32, 16, false, true, 2 | 4096 | 8192, MODE_C2C, false, 32, 32> RowsFromRing;
-  typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 32> ColsToRing;
-  typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 32, 32> ColsFromRing;
-  typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 32 | 2048 | 8192, MODE_C2C, true, 32, 32> FourStepFirst;
-  typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 2048 | 8192, MODE_C2C, true, 32, 32> FourStepFirstNat;
-  typedef PassCfg<double, 1024, 32, 16, false, true, 2 | 32 | 4096 | 8192, MODE_C2C, false, 32, 32> RowsFromRingT;
-  // the strided side of the slab pairs: the array side is an all-to-all buffer of equal blocks (FLAGS 32768 input / 65536 output, FUSED_PLANES_2D_B / _CR_B)
-  typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 32> ColsToRingB;
-  typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 32, 32> ColsFromRingB;
+  typedef PassCfg<double, 1024, 32, 16, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 32> RowsToRing;
+  typedef PassCfg<double, 1024, 32, 16, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> RowsFromRing;
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 32> ColsToRing;
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> ColsFromRing;
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_TRANSPOSE_STORE | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 32> FourStepFirst;
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 32> FourStepFirstNat;
+  typedef PassCfg<double, 1024, 32, 16, false, true, PF_NT_STORE | PF_TRANSPOSE_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> RowsFromRingT;
+  // the strided side of the slab pairs: the array side is an all-to-all buffer of equal blocks (PF_BLOCKS_IN / PF_BLOCKS_OUT, FUSED_PLANES_2D_B / _CR_B)
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 32> ColsToRingB;
+  typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 32, 32> ColsFromRingB;
 };
 
 // n = 512: 32 values per thread, radices 32 x 16, 256-thread workgroups on 16 lines -- 128 KiB tiles, TWO workgroups per CU
 // (round 3 measured the n = 512 pairs on 1024-thread workgroups of 8 values per thread and found them 40 % slower than
 // their stand-alone passes)
 struct Fused512R32 {
-  typedef PassCfg<double, 512, 32, 16, false, true, 1 | 2048 | 8192, MODE_C2C, false, 32, 16> RowsToRing;
-  typedef PassCfg<double, 512, 32, 16, false, true, 2 | 4096 | 8192, MODE_C2C, false, 32, 16> RowsFromRing;
-  typedef PassCfg<double, 512, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 16> ColsToRing;
-  typedef PassCfg<double, 512, 32, 16, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 32, 16> ColsFromRing;
-  typedef PassCfg<double, 512, 32, 16, true, true, 1 | 32 | 2048 | 8192, MODE_C2C, true, 32, 16> FourStepFirst;
-  typedef PassCfg<double, 512, 32, 16, true, true, 1 | 2048 | 8192, MODE_C2C, true, 32, 16> FourStepFirstNat;
-  typedef PassCfg<double, 512, 32, 16, false, true, 2 | 32 | 4096 | 8192, MODE_C2C, false, 32, 16> RowsFromRingT;
-  typedef PassCfg<double, 512, 32, 16, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 16> ColsToRingB;
-  typedef PassCfg<double, 512, 32, 16, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 32, 16> ColsFromRingB;
+  typedef PassCfg<double, 512, 32, 16, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 16> RowsToRing;
+  typedef PassCfg<double, 512, 32, 16, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 16> RowsFromRing;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 16> ColsToRing;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 16> ColsFromRing;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_LOAD | PF_TRANSPOSE_STORE | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 16> FourStepFirst;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_C2C, true, 32, 16> FourStepFirstNat;
+  typedef PassCfg<double, 512, 32, 16, false, true, PF_NT_STORE | PF_TRANSPOSE_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 16> RowsFromRingT;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 16> ColsToRingB;
+  typedef PassCfg<double, 512, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 32, 16> ColsFromRingB;
 };
 
 // Unequal pairs (round 6): planes of 512 x 1024 or 1024 x 512 points -- non-cubic grids, e.g. (512,1024,1024) on one rank or as the
 // slabs of a distributed transform.  Both passes share one 512-thread workgroup shape: the n = 1024 side is Fused1024R32's (16 lines
 // per tile), the n = 512 side takes 32 lines per tile (512-byte hand-off segments, the same 256 KiB of values per tile).
 struct Fused512T32 {
-  typedef PassCfg<double, 512, 32, 32, false, true, 2 | 4096 | 8192, MODE_C2C, false, 32, 16> RowsFromRing;
-  typedef PassCfg<double, 512, 32, 32, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 16> ColsToRing;
-  typedef PassCfg<double, 512, 32, 32, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 16> ColsToRingB;
+  typedef PassCfg<double, 512, 32, 32, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 16> RowsFromRing;
+  typedef PassCfg<double, 512, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 16> ColsToRing;
+  typedef PassCfg<double, 512, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 16> ColsToRingB;
 };
 
 // variant: 1 = the default, 32 values per thread / one exchange (Fused1024R32; the round-3 kernels -- 16 values per thread / two
@@ -96,12 +96,12 @@ struct Fused512T32 {
 // 8.11 / 8.19 -> 7.80 / 7.83 ms (profiles/r05_ab_mixv_variants.txt).  (The STAND-ALONE strided kernels of these lengths lose 3-16 % on
 // 32 values per thread, same file: they keep 16.)
 struct Fused960 {
-  typedef PassCfg<double, 960, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 15, 16, 4> ColsToRing;
-  typedef PassCfg<double, 960, 32, 16, false, true, 2 | 4096 | 8192, MODE_C2C, false, 15, 16, 4> RowsFromRing;
+  typedef PassCfg<double, 960, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 15, 16, 4> ColsToRing;
+  typedef PassCfg<double, 960, 32, 16, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 15, 16, 4> RowsFromRing;
 };
 struct Fused896 {
-  typedef PassCfg<double, 896, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 7, 16, 8> ColsToRing;
-  typedef PassCfg<double, 896, 32, 16, false, true, 2 | 4096 | 8192, MODE_C2C, false, 7, 16, 8> RowsFromRing;
+  typedef PassCfg<double, 896, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 7, 16, 8> ColsToRing;
+  typedef PassCfg<double, 896, 32, 16, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 7, 16, 8> RowsFromRing;
 };
 int g_fuse2_mixv = 1;          // option fuse2_mixv
 

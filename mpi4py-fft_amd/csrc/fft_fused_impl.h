@@ -6,9 +6,8 @@
 
 namespace gfft {
 
-// FLAGS of the hand-off sides: 2048 = stores at system scope, 4096 = loads at system scope, 8192 = natural
-// layouts (descriptor layout fields are compile-time zeros); 8 = plain complex strided pass, 32 = first
-// four-step pass (twiddle + transposing store)
+// (FLAGS of the hand-off sides: PF_SYS_STORE / PF_SYS_LOAD on PF_NATURAL layouts; PF_C2C_ONLY = plain complex strided pass,
+// PF_TRANSPOSE_STORE = first four-step pass -- gfft_internal.h)
 template <typename real, int N> struct FusedCfgs;
 
 template <typename C>

@@ -5,7 +5,7 @@
 //   FUSED_COLS_C2R    [strided n -> packed-real c2r rows]                passes 2 + 3 of the c2r schedule, plane = one i1
 //   FUSED_R2C_PLANES_B / FUSED_COLS_C2R_B   the same pairs as the two LOCAL stages of a real slab-decomposed transform
 //                     (gfft_plan_create_guru2_real): the strided side is the all-to-all buffer, its axis cut into equal blocks
-//                     (FLAGS 65536 output / 32768 input, fft_pow2_body.inc), rows exactly N + 1 entries apart there
+//                     (PF_BLOCKS_OUT / PF_BLOCKS_IN, fft_pow2_body.inc), rows exactly N + 1 entries apart there
 // The reference's default dtype is `float` (mpifft.py:202), i.e. these are the transforms a PFFT runs unless told otherwise
 // (libfft.py:48-79, fftw/xfftn.py:173-326: the Hermitian axis is the last one, N / 2 + 1 entries).
 // Rows: 16 values per thread, a row inside one wave (exchanges without barriers); strided: 32 values per thread, one
@@ -23,15 +23,15 @@ namespace gfft {
 int g_c2r_2048 = 1;
 
 //                            real    N    R   T  COLS   SPLIT FLAGS                 MODE        BIGTW  radices
-typedef PassCfg<double, 512, 16, 16, false, true, 1 | 2048 | 8192, MODE_R2C_H, false, 16, 8, 4> R2CRows512ToRing;      // 1024 reals per row
-typedef PassCfg<double, 1024, 16, 8, false, true, 1 | 2048 | 8192, MODE_R2C_H, false, 16, 16, 4> R2CRows1024ToRing;    // 2048 reals per row
-typedef PassCfg<double, 512, 16, 16, false, true, 2 | 4096 | 8192, MODE_C2R_H, false, 16, 8, 4> C2RRows512FromRing;
-typedef PassCfg<double, 1024, 16, 8, false, true, 2 | 4096 | 8192, MODE_C2R_H, false, 16, 16, 4> C2RRows1024FromRing;     // 2048 reals per row (option c2r_2048)
-typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192, MODE_C2C, false, 32, 32> Cols1024ToRing;
-typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192, MODE_C2C, false, 32, 32> Cols1024FromRing;
+typedef PassCfg<double, 512, 16, 16, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_R2C_H, false, 16, 8, 4> R2CRows512ToRing;      // 1024 reals per row
+typedef PassCfg<double, 1024, 16, 8, false, true, PF_NT_LOAD | PF_SYS_STORE | PF_NATURAL, MODE_R2C_H, false, 16, 16, 4> R2CRows1024ToRing;    // 2048 reals per row
+typedef PassCfg<double, 512, 16, 16, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2R_H, false, 16, 8, 4> C2RRows512FromRing;
+typedef PassCfg<double, 1024, 16, 8, false, true, PF_NT_STORE | PF_SYS_LOAD | PF_NATURAL, MODE_C2R_H, false, 16, 16, 4> C2RRows1024FromRing;     // 2048 reals per row (option c2r_2048)
+typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL, MODE_C2C, false, 32, 32> Cols1024ToRing;
+typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL, MODE_C2C, false, 32, 32> Cols1024FromRing;
 // the strided side of the slab pairs: the array side in equal blocks of the strided axis (the complex pairs' ColsToRingB / ColsFromRingB)
-typedef PassCfg<double, 1024, 32, 16, true, true, 1 | 8 | 2048 | 8192 | 32768, MODE_C2C, false, 32, 32> Cols1024ToRingB;
-typedef PassCfg<double, 1024, 32, 16, true, true, 2 | 8 | 4096 | 8192 | 65536, MODE_C2C, false, 32, 32> Cols1024FromRingB;
+typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 32> Cols1024ToRingB;
+typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 32, 32> Cols1024FromRingB;
 
 bool fused2_real_supported_f64(int kind, int n_a, int n_b) {
   if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) return (n_a == 512 || n_a == 1024) && n_b == 1024;

@@ -26,23 +26,23 @@ fft_plane2d_kernel(PassDesc dA, PassDesc dB, int planes, int64_t in_plane, int64
   }
 }
 
-//                real  N   R   T  COLS   SPLIT  FLAGS        MODE      BIGTW radices       (FLAGS 8192: natural layouts; 1 / 2: non-temporal HBM side)
+//                real  N   R   T  COLS   SPLIT  FLAGS        MODE      BIGTW radices       (PF_NATURAL layouts; PF_NT_LOAD / PF_NT_STORE: the HBM side)
 template <typename real, int N> struct PlaneCfg;
 template <> struct PlaneCfg<double, 64> {
-  typedef PassCfg<double, 64, 8, 64, false, true, 1 | 8192, MODE_C2C, false, 8, 8> Rows;
-  typedef PassCfg<double, 64, 8, 64, true, true, 2 | 8 | 8192, MODE_C2C, false, 8, 8> Cols;
+  typedef PassCfg<double, 64, 8, 64, false, true, PF_NT_LOAD | PF_NATURAL, MODE_C2C, false, 8, 8> Rows;
+  typedef PassCfg<double, 64, 8, 64, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_NATURAL, MODE_C2C, false, 8, 8> Cols;
 };
 template <> struct PlaneCfg<double, 32> {
-  typedef PassCfg<double, 32, 8, 32, false, true, 1 | 8192, MODE_C2C, false, 8, 4> Rows;
-  typedef PassCfg<double, 32, 8, 32, true, true, 2 | 8 | 8192, MODE_C2C, false, 8, 4> Cols;
+  typedef PassCfg<double, 32, 8, 32, false, true, PF_NT_LOAD | PF_NATURAL, MODE_C2C, false, 8, 4> Rows;
+  typedef PassCfg<double, 32, 8, 32, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_NATURAL, MODE_C2C, false, 8, 4> Cols;
 };
 template <> struct PlaneCfg<float, 64> {
-  typedef PassCfg<float, 64, 8, 64, false, false, 1 | 8192, MODE_C2C, false, 8, 8> Rows;
-  typedef PassCfg<float, 64, 8, 64, true, false, 2 | 8 | 8192, MODE_C2C, false, 8, 8> Cols;
+  typedef PassCfg<float, 64, 8, 64, false, false, PF_NT_LOAD | PF_NATURAL, MODE_C2C, false, 8, 8> Rows;
+  typedef PassCfg<float, 64, 8, 64, true, false, PF_NT_STORE | PF_C2C_ONLY | PF_NATURAL, MODE_C2C, false, 8, 8> Cols;
 };
 template <> struct PlaneCfg<float, 32> {
-  typedef PassCfg<float, 32, 8, 32, false, false, 1 | 8192, MODE_C2C, false, 8, 4> Rows;
-  typedef PassCfg<float, 32, 8, 32, true, false, 2 | 8 | 8192, MODE_C2C, false, 8, 4> Cols;
+  typedef PassCfg<float, 32, 8, 32, false, false, PF_NT_LOAD | PF_NATURAL, MODE_C2C, false, 8, 4> Rows;
+  typedef PassCfg<float, 32, 8, 32, true, false, PF_NT_STORE | PF_C2C_ONLY | PF_NATURAL, MODE_C2C, false, 8, 4> Cols;
 };
 
 bool plane2d_supported(int n, int precision) { return (n == 32 || n == 64) && (precision == 4 || precision == 8); }

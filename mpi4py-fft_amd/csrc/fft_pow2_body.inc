@@ -6,44 +6,45 @@
 // = ...;`) and GFFT_AFTER_LOADS (a statement run once per tile behind its loads, or nothing); names in scope:
 // d, in, out, smem, GFFT_SCALE (the pass's scale factor), and the template parameters real, N, R, T, COLS, SPLIT, FLAGS, MODE, BIGTW, RADS.
   static_assert(SPLIT || sizeof(real) == 4, "fp64 exchanges split planes");
+  // the FLAGS bits (gfft_internal.h has the table), each decoded once
+  constexpr bool NT_LD = (FLAGS & PF_NT_LOAD) != 0, NT_ST = (FLAGS & PF_NT_STORE) != 0, ACCESS_ONLY = (FLAGS & PF_ACCESS_ONLY) != 0;
+  constexpr bool TRUNC = (FLAGS & PF_TRUNC) != 0, TRUNC_LOAD = (FLAGS & PF_TRUNC_LOAD) != 0, TRANSPOSE = (FLAGS & PF_TRANSPOSE_STORE) != 0;
+  constexpr bool UNEVEN = (FLAGS & PF_UNEVEN_BLOCKS) != 0, NO_PIN = (FLAGS & PF_NO_PIN) != 0;
+  constexpr bool SYS_ST = (FLAGS & PF_SYS_STORE) != 0, SYS_LD = (FLAGS & PF_SYS_LOAD) != 0;
+  constexpr bool PLAIN = (FLAGS & PF_NATURAL) != 0, BLK_IN = (FLAGS & PF_BLOCKS_IN) != 0, BLK_OUT = (FLAGS & PF_BLOCKS_OUT) != 0;
+  constexpr bool ORDER = (FLAGS & PF_ORDER) != 0;
+  static_assert(!(FLAGS & (TF_NO_FOURSTEP | TF_NO_TRUNC)), "table-only bits: launch_pow2_inst strips them");
+  static_assert(!TRUNC_LOAD || TRUNC, "PF_TRUNC_LOAD needs PF_TRUNC");
+  static_assert(!(BLK_IN || BLK_OUT) || PLAIN, "PF_BLOCKS_IN / PF_BLOCKS_OUT need PF_NATURAL");
   // (Geo, fft_pow2_impl.h: RL / RS values per thread on the load / store side, NTL / NTS threads per column that hold them,
   // NT threads per column in the workgroup -- all of them N / R unless a stage's radix does not divide R)
   using GEO = Geo<N, R, RADS...>;
   constexpr int NT = GEO::TPC, RL = GEO::RL, RS = GEO::RS, NTL = N / RL, NTS = N / RS;
-  // rows no wider than a wavefront: exchanges without barriers (tile_sync, fft_pow2_impl.h); FLAGS & 16384 = A/B: keep the barriers
-  constexpr bool WL = GEO::UNIFORM && WaveLocal<N, R, COLS>::value && !(FLAGS & 16384);
+  // rows no wider than a wavefront: exchanges without barriers (tile_sync, fft_pow2_impl.h)
+  constexpr bool WL = GEO::UNIFORM && WaveLocal<N, R, COLS>::value;
   constexpr int WORD = SPLIT ? sizeof(real) : 2 * sizeof(real);
   constexpr int CS = Lds<N, COLS, T, WORD == 4, FirstRadix<RADS...>::value>::CS;
   constexpr int PADSH = pad_shift<N, FirstRadix<RADS...>::value, COLS>();      // slot padding of the LDS exchanges (fft_pow2_impl.h)
   // packed-real modes move complex pairs on both sides; the Hermitian pass is in the kernel body
   constexpr bool HALF = MODE == MODE_R2C_H || MODE == MODE_C2R_H;
   constexpr int IOMODE = HALF ? MODE_C2C : MODE;
-  static_assert(!HALF || (!COLS && !BIGTW && !(FLAGS & 32)), "packed-real modes: contiguous axis only");
-  static_assert(GEO::UNIFORM || ((MODE == MODE_C2C || HALF) && !BIGTW && !(FLAGS & (32 | 128))), "stages of unequal width: complex passes and packed-real rows on natural layouts (fused truncation / padding included)");
-  static_assert(!(FLAGS & (2048 | 4096)) || ((MODE == MODE_C2C || HALF) && !(FLAGS & (16 | 128))), "hand-off buffers: plain complex passes and plain packed-real rows");
-  // FLAGS & 8192: natural layouts on both sides (fused pairs) -- the exchange-buffer layout fields of the
-  // descriptor (blocks, tile-major lines / columns, flat tiles, masked columns) are compile-time zeros, so
-  // neither their loads nor the arithmetic on them survive (the fused kernels hold TWO descriptors)
-  constexpr bool PLAIN = (FLAGS & 8192) != 0;
-  // FLAGS & 32768 / 65536 (with 8192): ... except the equal blocks of the transformed axis (in_lgp / in_jump, out_lgp / out_jump) --
-  // the fused pair of a slab-decomposed transform's two local stages writes / reads the all-to-all buffer itself
-  // (gfft_plan_create_guru2; the step between thread slots is workgroup uniform, so the jump is scalar work)
-  // (32768: on the input side, 65536: on the output side -- the other side of such a pass is the hand-off ring; with both kept
-  // the compiler waited for every ring load before it issued the next, tools/scan_serial_loads.py: chains of 29 / 32)
-  constexpr bool BLK_IN = (FLAGS & 32768) != 0, BLK_OUT = (FLAGS & 65536) != 0;
-  // FLAGS & 131072: the order IN TIME of a tile's rows follows PassDesc::order (see there) -- which thread takes which
-  // row, and from which slot q0 on a thread issues its loads and stores.  Addresses, values and operations per element
-  // are those of the plain order.  Plain strided complex passes on natural lines only.
-  constexpr bool ORDER = (FLAGS & 131072) != 0;
-  static_assert(!ORDER || (COLS && !BIGTW && GEO::UNIFORM && MODE == MODE_C2C && !(FLAGS & (16 | 32 | 128 | 2048 | 4096)) &&
+  static_assert(!HALF || (!COLS && !BIGTW && !TRANSPOSE), "packed-real modes: contiguous axis only");
+  static_assert(!UNEVEN || HALF, "PF_UNEVEN_BLOCKS: packed-real rows");
+  static_assert(GEO::UNIFORM || ((MODE == MODE_C2C || HALF) && !BIGTW && !(TRANSPOSE || UNEVEN)), "stages of unequal width: complex passes and packed-real rows on natural layouts (fused truncation / padding included)");
+  static_assert(!(SYS_ST || SYS_LD) || ((MODE == MODE_C2C || HALF) && !(TRUNC || UNEVEN)), "hand-off buffers: plain complex passes and plain packed-real rows");
+  // (PLAIN: the layout fields below are compile-time zeros; BLK_IN / BLK_OUT keep the equal blocks of the transformed axis -- the
+  // step between thread slots is workgroup uniform, so the jump is scalar work.  With both kept on one pass the compiler waited
+  // for every ring load before it issued the next, tools/scan_serial_loads.py: chains of 29 / 32)
+  // ORDER: which thread takes which row, and from which slot q0 on a thread issues its loads and stores, follow PassDesc::order
+  static_assert(!ORDER || (COLS && !BIGTW && GEO::UNIFORM && MODE == MODE_C2C && !(TRUNC || TRANSPOSE || UNEVEN || SYS_ST || SYS_LD) &&
                            (NTL & (NTL - 1)) == 0 && RL % 4 == 0 && RL == RS),
                 "row orders: plain strided complex passes");
   // Conjugation-on-load applied once, BEHIND the loads, in the unequal-width stage kernels where -- applied to each value as it
   // arrives -- the compiler waited for every load before it issued the next (serial_loads_f64, fft_pow2_impl.h).  Packed-real
   // rows never conjugate on load (conj_in = 0: half_desc, plan_fused3 rows): no sign at all there.
-  constexpr bool NO_SIGN = !GEO::UNIFORM && HALF && !(FLAGS & (64 | 128 | 4096));
-  constexpr bool DEFER_SIGN = NO_SIGN || (!GEO::UNIFORM && MODE == MODE_C2C && !(FLAGS & (64 | 128 | 4096)) && sizeof(real) == 8 &&
-                                          serial_loads_f64(N, COLS, (FLAGS & 16) != 0));
+  constexpr bool NO_SIGN = !GEO::UNIFORM && HALF && !(TRUNC_LOAD || UNEVEN || SYS_LD);
+  constexpr bool DEFER_SIGN = NO_SIGN || (!GEO::UNIFORM && MODE == MODE_C2C && !(TRUNC_LOAD || UNEVEN || SYS_LD) && sizeof(real) == 8 &&
+                                          serial_loads_f64(N, COLS, TRUNC));
   const auto L_in_tlg = PLAIN ? decltype(d.in_tlg)(0) : d.in_tlg;
   const auto L_out_tlg = PLAIN ? decltype(d.out_tlg)(0) : d.out_tlg;
   const auto L_in_lgp = (PLAIN && !BLK_IN) ? decltype(d.in_lgp)(0) : d.in_lgp;
@@ -80,8 +81,8 @@
   const int64_t t_in = (!COLS && L_in_tlg) ? (int64_t)(t >> L_in_tlg) * d.in_tS + (t & ((1 << L_in_tlg) - 1)) : (int64_t)t * d.in_es;
   const int64_t t_out = (!COLS && L_out_tlg) ? (int64_t)(t >> L_out_tlg) * d.out_tS + (t & ((1 << L_out_tlg) - 1)) : (int64_t)t * d.out_es;
   // fused padding / truncation: distance between the two halves of the padded spectrum (uniform)
-  const int64_t pad_shift_in = (FLAGS & 16) ? (int64_t)(d.n - d.tr_N) * d.in_es : 0;
-  const int64_t pad_shift_out = (FLAGS & 16) ? (int64_t)(d.n - d.tr_N) * d.out_es : 0;
+  const int64_t pad_shift_in = TRUNC ? (int64_t)(d.n - d.tr_N) * d.in_es : 0;
+  const int64_t pad_shift_out = TRUNC ? (int64_t)(d.n - d.tr_N) * d.out_es : 0;
   const int64_t q_in = (!COLS && L_in_tlg) ? (int64_t)(NTL >> L_in_tlg) * d.in_tS : (int64_t)NTL * d.in_es;     // uniform steps
   const int64_t q_out = (!COLS && L_out_tlg) ? (int64_t)(NTS >> L_out_tlg) * d.out_tS : (int64_t)NTS * d.out_es;
 
@@ -94,7 +95,7 @@
     int tl = t;
     [[maybe_unused]] int ord_q0 = 0;      // (ORDER: the slot the tile's loads and stores start from, in quarters of RL; uniform)
     if constexpr (ORDER) {
-      const unsigned rot = ((unsigned)d.order >> 14) & 3u, ways = ((unsigned)d.order >> 12) & 3u;
+      const unsigned rot = order_row_rot(d.order), ways = order_q0_ways(d.order);
       if (rot) tl = (int)(((unsigned)t + ord_hash * (rot == 1 ? 5u : 4u)) & (unsigned)(NTL - 1));
       ord_q0 = ways == 2 ? (int)(ord_hash & 3u) : (ways == 1 ? (int)((ord_hash & 1u) * 2u) : 0);
     }
@@ -139,9 +140,9 @@
       in0 += (int64_t)i * d.in_is;
       out0 += (int64_t)i * d.out_is;
     }
-    [[maybe_unused]] const unsigned row_ub = o * inner + i;     // FLAGS & 128: row of the exchange buffer
+    [[maybe_unused]] const unsigned row_ub = o * inner + i;     // UNEVEN: row of the exchange buffer
     // (... whose blocks are all at least a thread group wide: the group form of the block look-up, fft_pow2_impl.h; uniform)
-    [[maybe_unused]] const bool ub_group = (FLAGS & 128) != 0 && d.ub_minw >= (NTL > NTS ? NTL : NTS);
+    [[maybe_unused]] const bool ub_group = UNEVEN && d.ub_minw >= (NTL > NTS ? NTL : NTS);
     cx<real> v[R];
     // Split layouts: thread slots e = t + q*NT advance by NT, and a block of the cut axis holds
     // (R >> lgp) * NT entries, so block boundaries fall between the same q for every thread: a
@@ -158,7 +159,7 @@
 #pragma unroll
           for (int i = 0; i < RL; ++i) {
             const int q = (i + Q0) % RL;
-            v[q] = tile_load<real, IOMODE, (FLAGS & 1) != 0>(d, in, in0, idx0 + (int64_t)q * q_in, tl + q * NTL, sy_in);
+            v[q] = tile_load<real, IOMODE, NT_LD>(d, in, in0, idx0 + (int64_t)q * q_in, tl + q * NTL, sy_in);
           }
         };
         switch (ord_q0) {
@@ -176,21 +177,21 @@
       int cnt = 0;
 #pragma unroll
       for (int q = 0; q < RL; ++q) {
-        if constexpr ((FLAGS & 16) != 0) {
-          if constexpr (HALF && (FLAGS & 64) != 0) {
+        if constexpr (TRUNC) {
+          if constexpr (HALF && TRUNC_LOAD) {
             // zero-padded half spectrum (libfft.py:298-311): entries >= tr_n are zero, the last kept
             // entry of an even truncated length is a real Nyquist value taken at half weight
             const int e = tl + q * NTL;
             const bool ok = e < d.tr_n, nyq = d.tr_even && e == d.tr_n - 1;
-            if constexpr ((FLAGS & 128) != 0) v[q] = reinterpret_cast<const cx<real> *>(in)[uneven_offset(d, row_ub, o, i, ok ? e : 0)];
+            if constexpr (UNEVEN) v[q] = reinterpret_cast<const cx<real> *>(in)[uneven_offset(d, row_ub, o, i, ok ? e : 0)];
             else v[q] = reinterpret_cast<const cx<real> *>(in)[ok ? idx : in0];
             v[q].x *= ok ? (nyq ? (real)0.5 : (real)1) : (real)0;
             v[q].y *= (ok && !nyq) ? (real)1 : (real)0;
-          } else if constexpr ((FLAGS & 64) != 0) v[q] = tile_load_pad<real, IOMODE>(d, in, in0, idx, pad_shift_in, tl + q * NTL, sy_in);
+          } else if constexpr (TRUNC_LOAD) v[q] = tile_load_pad<real, IOMODE>(d, in, in0, idx, pad_shift_in, tl + q * NTL, sy_in);
           else v[q] = tile_load<real, IOMODE, false>(d, in, in0, idx, tl + q * NTL, DEFER_SIGN ? (real)1 : sy_in);
-        } else if constexpr (MODE == MODE_C2R_H && (FLAGS & 128) != 0) {
+        } else if constexpr (MODE == MODE_C2R_H && UNEVEN) {
           v[q] = reinterpret_cast<const cx<real> *>(in)[ub_group ? uneven_offset_group<NTL>(d, row_ub, o, i, tl, q) : uneven_offset(d, row_ub, o, i, tl + q * NTL)];
-        } else if constexpr ((FLAGS & 4096) != 0) {
+        } else if constexpr (SYS_LD) {
           v[q] = sys_in.template ld<real>(idx);
           // (packed-real rows never conjugate on load -- conj_in = 0, half_desc / plan_fused3 rows -- and with the sign applied
           // here the compiler waited for every load of the c2r rows before it issued the next: 16 round trips to the ring per tile)
@@ -198,7 +199,7 @@
         } else {
           // (unequal-width stage kernels: the sign of the imaginary parts goes on behind ALL the loads, below -- applied to
           // each value as it arrives, under their register pressure, the compiler waited for every load before issuing the next)
-          v[q] = tile_load<real, IOMODE, (FLAGS & 1) != 0>(d, in, in0, idx, tl + q * NTL, DEFER_SIGN ? (real)1 : sy_in);
+          v[q] = tile_load<real, IOMODE, NT_LD>(d, in, in0, idx, tl + q * NTL, DEFER_SIGN ? (real)1 : sy_in);
         }
         int64_t step = q_in;
         if (++cnt == seg_in) {
@@ -231,11 +232,11 @@
       // c2r does.
       cx<real> top = {0, 0};
       if (tl == 0) {
-        if constexpr ((FLAGS & 128) != 0 && !(FLAGS & 16)) {
+        if constexpr (UNEVEN && !TRUNC) {
           if (valid) top.x = reinterpret_cast<const cx<real> *>(in)[uneven_offset(d, row_ub, o, i, N)].x;
-        } else if constexpr ((FLAGS & 4096) != 0) {
+        } else if constexpr (SYS_LD) {
           if (valid) top.x = sys_in.template ld<real>(in0 + (int64_t)N * d.in_es).x;
-        } else if constexpr (!(FLAGS & 64)) {
+        } else if constexpr (!TRUNC_LOAD) {
           if (valid) top.x = reinterpret_cast<const cx<real> *>(in)[in0 + (int64_t)N * d.in_es].x;
         }
         v[0].y = 0;
@@ -255,11 +256,11 @@
     }
     // (the row index `tl` is laundered for the same reason: fp32 n=1024 R=32 104 bytes of scratch
     // -> none; fp64 n=1024 R=16 T=16 127 -> 107 VGPRs)
-    if constexpr (!(FLAGS & 4)) {
+    if constexpr (!ACCESS_ONLY) {
       if constexpr (GEO::UNIFORM) Stage<real, N, R, SPLIT, WL, PADSH, 1, RADS...>::run(v, tl, col, twl);
       else StageV<real, N, R, SPLIT, 1, RADS...>::run(v, tl, col, twl);
     }
-    if constexpr (!HALF && !(FLAGS & 256)) {      // (FLAGS & 256: A/B switch, no pin)
+    if constexpr (!HALF && !NO_PIN) {
       // pin the line between the last stage and the stores: interleaved by the scheduler the two
       // keep extra copies alive (fp32 n = 1024 R = 32 with the truncating store: 145 spilled VGPRs
       // -> 11; the plain fp32 R = 32 pass: 127 VGPRs + 4 spilled -> 121, none)
@@ -280,7 +281,7 @@
         v[q] = {a.x + wb.y, a.y - wb.x};                           // a - i w b
       }, NTS == NT || tl < NTS);
     }
-    if constexpr ((FLAGS & 16) != 0 && !(FLAGS & 64) && MODE == MODE_C2C && !HALF) {
+    if constexpr (TRUNC && !TRUNC_LOAD && MODE == MODE_C2C && !HALF) {
       // complex truncation with even N: entries h = N/2 and n - h of the padded spectrum both land
       // on truncated entry h (libfft.py:281-284).  They live in different threads: pass the upper
       // one through LDS.  (uniform branch: every thread of the workgroup takes it or none does)
@@ -300,7 +301,7 @@
         if constexpr (WL) __syncthreads();
       }
     }
-    if constexpr (BIGTW && (FLAGS & (32 | 2048)) != 0) {
+    if constexpr (BIGTW && (TRANSPOSE || SYS_ST)) {
       // four-step twiddle W^(m e), e = t + q NT: two table look-ups per THREAD -- W^(m t) and
       // W^(m NT) -- and the powers of the second by squaring (q is a compile-time index, so entry q
       // costs at most log2 R multiplications); one look-up pair per ELEMENT tripled the load
@@ -326,7 +327,7 @@
         v[q] = cmul(v[q], w);
       }
     }
-    if constexpr ((FLAGS & 32) != 0) {
+    if constexpr (TRANSPOSE) {
       // Transposing store.  Loads ran with lanes along T adjacent columns (T*16-byte segments of the
       // strided input); the output of each column is one contiguous line, so storing in the same
       // mapping would write T short runs per instruction.  Finish the element-wise work here
@@ -367,8 +368,8 @@
                       (int64_t)t2 * d.out_es;
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-          if constexpr ((FLAGS & 2048) != 0) sys_out.template st<real>(idx, v[q]);
-          else stc<real, (FLAGS & 2) != 0>(reinterpret_cast<cx<real> *>(out) + idx, v[q]);
+          if constexpr (SYS_ST) sys_out.template st<real>(idx, v[q]);
+          else stc<real, NT_ST>(reinterpret_cast<cx<real> *>(out) + idx, v[q]);
           idx += q_out;
         }
       }
@@ -383,7 +384,7 @@
 #pragma unroll
           for (int i = 0; i < RS; ++i) {
             const int q = (i + Q0) % RS;
-            tile_store<real, IOMODE, false, (FLAGS & 2) != 0>(d, out, idx0 + (int64_t)q * q_out, tl + q * NTS, m, v[q], sx_out, sy_out);
+            tile_store<real, IOMODE, false, NT_ST>(d, out, idx0 + (int64_t)q * q_out, tl + q * NTS, m, v[q], sx_out, sy_out);
           }
         };
         switch (ord_q0) {
@@ -398,25 +399,25 @@
       int cnt = 0;
 #pragma unroll
       for (int q = 0; q < RS; ++q) {
-        if constexpr ((FLAGS & 16) != 0) {
-          if constexpr (HALF && !(FLAGS & 64)) {
+        if constexpr (TRUNC) {
+          if constexpr (HALF && !TRUNC_LOAD) {
             // truncated half spectrum (libfft.py:286-296): keep entries < tr_n; the last one of an
             // even truncated length becomes a real Nyquist value of twice the weight
             const int e = tl + q * NTS;
             if (e < d.tr_n) {
               const bool nyq = d.tr_even && e == d.tr_n - 1;
               int64_t at = idx;
-              if constexpr ((FLAGS & 128) != 0) at = uneven_offset(d, row_ub, o, i, e);
+              if constexpr (UNEVEN) at = uneven_offset(d, row_ub, o, i, e);
               reinterpret_cast<cx<real> *>(out)[at] = {v[q].x * (nyq ? 2 * sx_out : sx_out), nyq ? (real)0 : v[q].y * sy_out};
             }
-          } else if constexpr (!(FLAGS & 64)) tile_store_trunc<real, IOMODE>(d, out, idx, pad_shift_out, tl + q * NTS, v[q], sx_out, sy_out);
+          } else if constexpr (!TRUNC_LOAD) tile_store_trunc<real, IOMODE>(d, out, idx, pad_shift_out, tl + q * NTS, v[q], sx_out, sy_out);
           else tile_store<real, IOMODE, false, false>(d, out, idx, tl + q * NTS, m, v[q], sx_out, sy_out);
-        } else if constexpr (MODE == MODE_R2C_H && (FLAGS & 128) != 0) {
+        } else if constexpr (MODE == MODE_R2C_H && UNEVEN) {
           reinterpret_cast<cx<real> *>(out)[ub_group ? uneven_offset_group<NTS>(d, row_ub, o, i, tl, q) : uneven_offset(d, row_ub, o, i, tl + q * NTS)] = {v[q].x * sx_out, v[q].y * sy_out};
-        } else if constexpr ((FLAGS & 2048) != 0) {
+        } else if constexpr (SYS_ST) {
           sys_out.template st<real>(idx, cx<real>{v[q].x * sx_out, v[q].y * sy_out});
         } else {
-          tile_store<real, IOMODE, BIGTW, (FLAGS & 2) != 0>(d, out, idx, tl + q * NTS, m, v[q], sx_out, sy_out);
+          tile_store<real, IOMODE, BIGTW, NT_ST>(d, out, idx, tl + q * NTS, m, v[q], sx_out, sy_out);
         }
         int64_t step = q_out;
         if (++cnt == seg_out) {
@@ -425,15 +426,15 @@
         }
         idx += step;
       }
-      if constexpr (MODE == MODE_R2C_H && (FLAGS & 128) != 0 && !(FLAGS & 16)) {
+      if constexpr (MODE == MODE_R2C_H && UNEVEN && !TRUNC) {
         if (tl == 0)
           reinterpret_cast<cx<real> *>(out)[uneven_offset(d, row_ub, o, i, N)] = {(z0.x - z0.y) * 2 * sx_out, 0};
-      } else if constexpr (MODE == MODE_R2C_H && !(FLAGS & 16)) {
+      } else if constexpr (MODE == MODE_R2C_H && !TRUNC) {
         // X[N] from thread 0, followed by L_out_pad zeros from its neighbours: one coalesced store
         // that completes the row's last 128-byte line when the output rows are pitched
         if (tl <= L_out_pad) {
           const cx<real> last = {tl == 0 ? (z0.x - z0.y) * 2 * sx_out : (real)0, 0};
-          if constexpr ((FLAGS & 2048) != 0) sys_out.template st<real>(out0 + (int64_t)(N + tl) * d.out_es, last);
+          if constexpr (SYS_ST) sys_out.template st<real>(out0 + (int64_t)(N + tl) * d.out_es, last);
           else reinterpret_cast<cx<real> *>(out)[out0 + (int64_t)(N + tl) * d.out_es] = last;
         }
       }

@@ -33,10 +33,10 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
       // 512^3), n = 1024 on 4 rows per workgroup instead of 1 ((512,1024,1024) 1.678 -> 1.518 ms); n = 2048 level (profiles/r06_rows_probe.txt).
       // variant 16 = the former table.
       case 512:
-        if (plain) return P32F(512, 16, 8, false, false, 1, 8 | 3, 16, 8, 4);
+        if (plain) return P32F(512, 16, 8, false, false, 1, PF_C2C_ONLY | PF_NT, 16, 8, 4);
         return P32(512, 8, 1, false, false, 1, 8, 8, 8);
       case 1024:
-        if (plain) return P32F(1024, 16, 4, false, false, 1, 8 | 3, 16, 16, 4);
+        if (plain) return P32F(1024, 16, 4, false, false, 1, PF_C2C_ONLY | PF_NT, 16, 16, 4);
         return P32(1024, 16, 1, false, false, 1, 16, 16, 4);
       case 2048: return P32(2048, 16, 1, false, false, 1, 16, 16, 8);
       case 4096: return P32(4096, 16, 1, false, false, 1, 16, 16, 16);
@@ -46,10 +46,10 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
     // that each output line is written in whole rows (as in fft_pow2_f64.hip; measured on 128 x 2^20
     // c64 under rocprofv3: this pass took 934 us with the plain store, the second pass 501 us)
     switch (d.n) {
-      case 512: return P32F(512, 16, 32, true, true, 1, 32, 16, 8, 4);
-      case 1024: return P32F(1024, 16, 16, true, true, 1, 32, 16, 16, 4);
-      case 2048: return P32F(2048, 16, 8, true, true, 4, 32, 16, 16, 8);
-      case 4096: return P32F(4096, 16, 4, true, true, 4, 32, 16, 16, 16);
+      case 512: return P32F(512, 16, 32, true, true, 1, PF_TRANSPOSE_STORE, 16, 8, 4);
+      case 1024: return P32F(1024, 16, 16, true, true, 1, PF_TRANSPOSE_STORE, 16, 16, 4);
+      case 2048: return P32F(2048, 16, 8, true, true, 4, PF_TRANSPOSE_STORE, 16, 16, 8);
+      case 4096: return P32F(4096, 16, 4, true, true, 4, PF_TRANSPOSE_STORE, 16, 16, 16);
     }
   } else if (d.mode == MODE_C2C && d.tr_dir && !d.tw_hi && (d.n == 512 || (GFFT_HAS_VARIANTS && variant == 7 && d.n >= 1024))) {
     // complex strided passes with fused truncation (store side) / zero padding (load side) on the
@@ -59,8 +59,8 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
     // table's 128-byte tiles -- (1024,1024,2048) c64, padded axis 1: 7.9 / 10.2 ms forward /
     // backward against 7.2 / 7.0 ms -- so they stay behind variant 7 (A/B runs).
 #define P32T(N, R, T, ...)                                                                                          \
-  (d.tr_dir == 1 ? launch_pow2_one<float, N, R, T, true, true, 1, 16, MODE_C2C, false, __VA_ARGS__>(d, in, out, s) \
-                 : launch_pow2_one<float, N, R, T, true, true, 1, 16 | 64, MODE_C2C, false, __VA_ARGS__>(d, in, out, s))
+  (d.tr_dir == 1 ? launch_pow2_one<float, N, R, T, true, true, 1, PF_TRUNC, MODE_C2C, false, __VA_ARGS__>(d, in, out, s) \
+                 : launch_pow2_one<float, N, R, T, true, true, 1, PF_TRUNC | PF_TRUNC_LOAD, MODE_C2C, false, __VA_ARGS__>(d, in, out, s))
     switch (d.n) {
       case 512: return P32T(512, 16, 32, 16, 8, 4);
 #ifdef GFFT_VARIANTS   // (variant 7 only: measured slower, see above)
@@ -107,10 +107,10 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
     // plain c2c along a strided axis: 32 adjacent columns = 256-byte segments up to n = 512
     // (measured on (2048,512,1024) c64: 3.88 -> 3.35 ms; n = 256: 3.53 -> 3.37 ms).
     switch (d.n) {
-      case 16: return P32F(16, 4, 32, true, false, 1, 8, 4, 4);
-      case 32: return P32F(32, 8, 32, true, false, 1, 8, 8, 4);
-      case 64: return P32F(64, 8, 32, true, false, 1, 8, 8, 8);
-      case 128: return P32F(128, 8, 32, true, false, 1, 8, 8, 8, 2);
+      case 16: return P32F(16, 4, 32, true, false, 1, PF_C2C_ONLY, 4, 4);
+      case 32: return P32F(32, 8, 32, true, false, 1, PF_C2C_ONLY, 8, 4);
+      case 64: return P32F(64, 8, 32, true, false, 1, PF_C2C_ONLY, 8, 8);
+      case 128: return P32F(128, 8, 32, true, false, 1, PF_C2C_ONLY, 8, 8, 2);
       case 256:
         // Round 6: 32 values per thread = ONE exchange (radices 32 x 8), the same 32 columns = 256-byte segments, 256 threads.  Half the bytes
         // per butterfly of complex128: the exchange phase is what complex64 tiles wait on, and this halves it.  Plans
@@ -119,10 +119,10 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
         // (64 columns on 512 or 1024 threads: measured behind except on the smallest array.)  Odd widths keep the three-stage tile: see n = 512.
         // Inside one-rank 3-D schedules (plan_fused3 asks for variant 2 there) too: 256^3 c64 per step 0.363 -> 0.320 ms; the n = 512 lines of
         // such schedules keep variant 2 (512^3 c64: 2.442 ms against 2.547 with this tile shape).
-        if ((variant == 0 || variant == 2) && d.inner % 32 == 0 && whole && 2.0 * (double)d.batch * 256 * 8 >= 268435456.0) return P32F(256, 32, 32, true, true, 2, 8 | 3, 32, 8);      // (non-temporal: arrays beyond the Infinity Cache)
+        if ((variant == 0 || variant == 2) && d.inner % 32 == 0 && whole && 2.0 * (double)d.batch * 256 * 8 >= 268435456.0) return P32F(256, 32, 32, true, true, 2, PF_C2C_ONLY | PF_NT, 32, 8);      // (non-temporal: arrays beyond the Infinity Cache)
         switch (variant) {
-          default: return P32F(256, 8, 32, true, false, 1, 8, 8, 8, 4);
-          case 22: return P32F(256, 32, 32, true, true, 2, 8 | 3, 32, 8);     // (the automatic choice above, whatever the array: for A/B)
+          default: return P32F(256, 8, 32, true, false, 1, PF_C2C_ONLY, 8, 8, 4);
+          case 22: return P32F(256, 32, 32, true, true, 2, PF_C2C_ONLY | PF_NT, 32, 8);     // (the automatic choice above, whatever the array: for A/B)
 #ifdef GFFT_VARIANTS
           case 1: return P32(256, 16, 16, true, false, 1, 16, 16);
 #endif
@@ -132,14 +132,14 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
         // 0.435 / 0.449 ms, (1024,512,1024) axis 1 1.862 -> 1.795 ms, (512,1024,1024) axis 0 2.409 -> 2.080 ms -- where rows are whole
         // multiples of the tile.  On 513-wide rows (the half spectra of real transforms) it LOSES: (2048,512,513) axis 1 2.353 -> 2.936 ms.
         // (64 columns = 512-byte segments on 1024 threads: measured behind the default everywhere.)
-        if (variant == 0 && d.inner % 32 == 0 && whole && 2.0 * (double)d.batch * 512 * 8 >= 268435456.0) return P32F(512, 32, 32, true, true, 2, 8 | 3, 32, 16);
+        if (variant == 0 && d.inner % 32 == 0 && whole && 2.0 * (double)d.batch * 512 * 8 >= 268435456.0) return P32F(512, 32, 32, true, true, 2, PF_C2C_ONLY | PF_NT, 32, 16);
         switch (variant) {
-          default: return P32F(512, 16, 32, true, true, 1, 8, 16, 8, 4);
-          case 22: return P32F(512, 32, 32, true, true, 2, 8 | 3, 32, 16);    // (the automatic choice above, whatever the array: for A/B)
+          default: return P32F(512, 16, 32, true, true, 1, PF_C2C_ONLY, 16, 8, 4);
+          case 22: return P32F(512, 32, 32, true, true, 2, PF_C2C_ONLY | PF_NT, 32, 16);    // (the automatic choice above, whatever the array: for A/B)
 #ifdef GFFT_VARIANTS
           case 1: return P32(512, 8, 16, true, true, 1, 8, 8, 8);
 #endif
-          case 2: return P32F(512, 16, 16, true, true, 4, 8, 16, 8, 4);           // A/B as for n = 1024: 0.95 / 1.26 ms against 0.91 / 1.04
+          case 2: return P32F(512, 16, 16, true, true, 4, PF_C2C_ONLY, 16, 8, 4);           // A/B as for n = 1024: 0.95 / 1.26 ms against 0.91 / 1.04
         }
       // n >= 1024: R = 32 elements per thread (the 64 data VGPRs R = 16 costs in fp64) doubles the
       // columns per workgroup at the same 1024 threads: 256-byte segments at n = 1024, 128 at 2048.
@@ -147,14 +147,14 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
       // 5.83 -> 4.13 ms, n=4096 (x512) 4.85 -> 3.37 ms; variant 1 = the R = 16 plans.
       case 1024:
         switch (variant) {
-          case 0: if (nt_ok) return P32F(1024, 32, 32, true, true, 1, 8 | 3, 16, 16, 4);      // (falls through to the plain streams otherwise)
+          case 0: if (nt_ok) return P32F(1024, 32, 32, true, true, 1, PF_C2C_ONLY | PF_NT, 16, 16, 4);      // (falls through to the plain streams otherwise)
           // (R6, measured and NOT kept: ONE exchange -- radices 32 x 32 -- on 16 columns = 128-byte segments, 512 threads of 182 VGPRs, two workgroups per CU,
           // non-temporal: near strides -2 ... -3.5 % ((256,1024,1024) axis 1 0.972 -> 0.938 ms), far strides +13 ... +15 % ((1024,256,1024) axis 0 1.058 -> 1.212 ms):
           // where the exchange halves, the segment width costs more)
-          default: return P32F(1024, 32, 32, true, true, 1, 8, 16, 16, 4);
+          default: return P32F(1024, 32, 32, true, true, 1, PF_C2C_ONLY, 16, 16, 4);
 #ifdef GFFT_VARIANTS
           case 1: return P32(1024, 16, 16, true, true, 1, 16, 16, 4);
-          case 8: return P32F(1024, 32, 32, true, true, 1, 8 | 256, 16, 16, 4);   // A/B: line not pinned before the stores
+          case 8: return P32F(1024, 32, 32, true, true, 1, PF_C2C_ONLY | PF_NO_PIN, 16, 16, 4);   // A/B: line not pinned before the stores
 #endif
           // A/B: two 512-thread workgroups per CU (one computes while the other loads) on 128-byte
           // segments: 1024^3 c64 axis 1 3.60 ms (default 3.58), axis 0 5.38 (4.43) -- segment width wins.
@@ -162,7 +162,7 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
           // exchanges had been the conflicting ones): pitched rows near 3.40 (3.55) / far 3.90 (3.99),
           // natural rows near 3.50 (3.53) / far 4.94 (4.15) -- ahead by 2-4 % only where both sides are
           // pitched, behind by 19 % on natural far strides: still not the default.
-          case 2: return P32F(1024, 32, 16, true, true, 4, 8, 16, 16, 4);
+          case 2: return P32F(1024, 32, 16, true, true, 4, PF_C2C_ONLY, 16, 16, 4);
           // (R4: non-temporal loads and stores on either form, as the fp64 strided default has them: 1024^3 c64 per step 19.61 ->
           // 19.57 ms on variant 2, 20.43 on the wide tile; 1024^3 r2c f32 11.65 -> 12.12 / 12.87 ms -- not adopted)
 #ifdef GFFT_VARIANTS
@@ -170,9 +170,9 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
           // (256-byte segments) -- what paid in fp64 (32 values, fft_pow2_f64.hip) does not here: 64 complex64 are 128 VGPRs of
           // data alone, the kernels take all 256 plus 130-160 bytes of scratch, and (1024,1024,1024) axis 1 goes 3.82 -> 4.72 ms
           // (4.50 with non-temporal streams), axis 0 4.8-4.9 -> 6.44 / 4.93 ms (profiles/r04_variant_cols_f32_r64.txt)
-          case 5: return P32F(1024, 64, 32, true, true, 2, 8, 64, 16);
-          case 6: return P32F(1024, 64, 32, true, true, 2, 8 | 3, 64, 16);     // ... with non-temporal loads and stores
-          case 10: return P32F(1024, 32, 32, true, true, 1, 8 | 4, 16, 16, 4);    // R6: the ACCESS PATTERN ALONE of the default tile (tools/strided_bound_probe_f32.py)
+          case 5: return P32F(1024, 64, 32, true, true, 2, PF_C2C_ONLY, 64, 16);
+          case 6: return P32F(1024, 64, 32, true, true, 2, PF_C2C_ONLY | PF_NT, 64, 16);     // ... with non-temporal loads and stores
+          case 10: return P32F(1024, 32, 32, true, true, 1, PF_C2C_ONLY | PF_ACCESS_ONLY, 16, 16, 4);    // R6: the ACCESS PATTERN ALONE of the default tile (tools/strided_bound_probe_f32.py)
           // (R6, measured and NOT kept: touches of the NEXT tile's lines issued behind this tile's loads -- one dword per element into a VGPR nobody reads --
           // so that HBM works during the exchange phase: near strides +8 ... +10 % SLOWER, far strides +-1 %: the touches cross the L2 boundary too,
           // which is what the launch is short of; profiles/r06_touch_probe.txt)
@@ -181,19 +181,19 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
           // A/B: two radix-32 stages = ONE exchange instead of two (LDS cycles and barriers halved), but the
           // 32-point butterfly with its 31 stage twiddles does not fit 128 VGPRs at 1024 threads
           // (116 B of scratch per lane): pitched near 4.33 ms against 3.61, far 5.18 against 4.02
-          case 3: return P32F(1024, 32, 32, true, true, 1, 8, 32, 32);
+          case 3: return P32F(1024, 32, 32, true, true, 1, PF_C2C_ONLY, 32, 32);
 #endif
         }
       case 2048:
         switch (variant) {
-          case 0: if (nt_ok) return P32F(2048, 32, 16, true, true, 1, 8 | 3, 16, 16, 8);      // (falls through to the plain streams otherwise)
-          default: return P32F(2048, 32, 16, true, true, 1, 8, 16, 16, 8);
+          case 0: if (nt_ok) return P32F(2048, 32, 16, true, true, 1, PF_C2C_ONLY | PF_NT, 16, 16, 8);      // (falls through to the plain streams otherwise)
+          default: return P32F(2048, 32, 16, true, true, 1, PF_C2C_ONLY, 16, 16, 8);
 #ifdef GFFT_VARIANTS
           // R4, measured and NOT kept (as at n = 1024): radices 64 x 32 = ONE exchange, 512 threads on 16 columns -- the C5 stages
           // (512,2048,513) axis 1 2.53 -> 2.80 ms (3.81 with non-temporal streams), (2048,512,513) axis 0 2.38 -> 2.65 / 2.36 ms
-          case 5: return P32F(2048, 64, 16, true, true, 2, 8, 64, 32);
-          case 6: return P32F(2048, 64, 16, true, true, 2, 8 | 3, 64, 32);
-          case 10: return P32F(2048, 32, 16, true, true, 1, 8 | 4, 16, 16, 8);    // R6: access pattern alone
+          case 5: return P32F(2048, 64, 16, true, true, 2, PF_C2C_ONLY, 64, 32);
+          case 6: return P32F(2048, 64, 16, true, true, 2, PF_C2C_ONLY | PF_NT, 64, 32);
+          case 10: return P32F(2048, 32, 16, true, true, 1, PF_C2C_ONLY | PF_ACCESS_ONLY, 16, 16, 8);    // R6: access pattern alone
 #endif
 #ifdef GFFT_VARIANTS
           case 1: return P32(2048, 16, 8, true, true, 4, 16, 16, 8);
@@ -201,7 +201,7 @@ hipError_t launch_pow2_f32(const PassDesc &d, bool cols, int variant, const void
         }
       case 4096:
         switch (variant) {
-          default: return P32F(4096, 32, 8, true, true, 1, 8, 16, 16, 16);
+          default: return P32F(4096, 32, 8, true, true, 1, PF_C2C_ONLY, 16, 16, 16);
 #ifdef GFFT_VARIANTS
           case 1: return P32(4096, 16, 4, true, true, 4, 16, 16, 16);
 #endif

@@ -1020,7 +1020,7 @@ __device__ __forceinline__ void mirror_pass(cx<real> *v, int t, void *col, cx<re
   }
 }
 
-// Uneven all-to-all blocks on the half-spectrum side of a packed-real row pass (FLAGS & 128, see
+// Uneven all-to-all blocks on the half-spectrum side of a packed-real row pass (PF_UNEVEN_BLOCKS, see
 // PassDesc::ub_*): element offset of entry e of row `row`.  The block of e comes from a chain of at
 // most seven compares against scalar boundaries; no divisions, no table look-ups.
 __device__ __forceinline__ int64_t uneven_offset(const PassDesc &d, unsigned row, unsigned slab, unsigned srow, int e) {
@@ -1125,18 +1125,9 @@ constexpr bool serial_loads_f64(int n, bool cols, bool trunc) {
               : (trunc ? in_lengths(n, rows_trunc, sizeof rows_trunc / sizeof(int)) : in_lengths(n, rows_plain, sizeof rows_plain / sizeof(int)));
 }
 
-// FLAGS: 1 = non-temporal loads, 2 = non-temporal stores, 4 = skip the transform (access-pattern
-// probe), 8 = c2c only, 16 = fused truncation / padding adapters (d.tr_dir: 1 store, 2 load),
-// 32 = transposing store (strided kernels whose OUTPUT is contiguous along the transform axis:
-// the first pass of a four-step transform), 64 = with 16: the adapter is the zero-padding LOAD
-// (backward direction) instead of the truncating STORE (a run-time direction switch inside the load
-// loop serialises the loads), 128 = packed-real rows whose half-spectrum side is an all-to-all buffer
-// of uneven blocks
+// FLAGS: the PF_* bits of gfft_internal.h.
 // The pass over tiles  xcd_base + k,  k = k_first, k_first + k_step, ... < k_end  (the kernel below walks
 // its share of all tiles; the fused two-pass kernel, fft_fused2_kernel, hands it one tile per ticket).
-// FLAGS & 2048 / 4096: the output / input array is a hand-off buffer between workgroups of ONE launch
-// (fused kernels): stored with / loaded at SYSTEM scope (sc0 sc1: written through to the memory side,
-// never served from a possibly stale L2 line), plain complex accesses only; see fft_fused2_kernel.
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // `after_loads`: called once per tile by every thread, after the tile's loads have been issued and before its
 // first butterfly (the fused kernel settles the previous tile's hand-off there, behind the new loads)
@@ -1167,25 +1158,24 @@ fft_pow2_kernel(PassDesc d, const void *__restrict__ in, void *__restrict__ out)
   const unsigned per_xcd = (pow2_ntiles<T, COLS, BIGTW>(d) + 7) / 8;
   const unsigned kstep = d.swizzle ? gridDim.x / 8 : gridDim.x;
 #define GFFT_TILE_LOOP for (unsigned k = d.swizzle ? blockIdx.x / 8 : blockIdx.x; k < (d.swizzle ? per_xcd : ntiles); k += kstep)
-  // Kernels built with FLAGS & 131072 re-order the XCD-contiguous walk IN TIME by d.order (PassDesc::order; the host sets it
+  // PF_ORDER kernels re-order the XCD-contiguous walk IN TIME by d.order (PassDesc::order; the host sets it
   // only where the walk covers whole planes of `chunks` tiles, launch_pow2_one): the eight XCDs otherwise work, at every
   // moment, on tiles exactly ntiles / 8 apart -- 2 GiB at 1024^3 complex128 -- and on the same rows of them.
   // `ord_hash` drives the row orders of the tile (fft_pow2_body.inc).
 #define GFFT_TILE_INDEX                                                                                              \
   unsigned tile = d.swizzle ? (blockIdx.x % 8) * per_xcd + k : k;                                                    \
   [[maybe_unused]] unsigned ord_hash = 0;                                                                            \
-  if constexpr ((FLAGS & 131072) != 0) {                                                                             \
+  if constexpr ((FLAGS & PF_ORDER) != 0) {                                                                           \
     if (d.order && d.swizzle) {                                                                                      \
-      const unsigned x = blockIdx.x % 8, il = 1u << (((unsigned)d.order >> 16) & 3u);                                \
-      const unsigned apart = (((unsigned)d.order >> 19) & 127u) ? (((unsigned)d.order >> 19) & 127u) : 37u;          \
+      const unsigned x = blockIdx.x % 8, il = 1u << order_planes_log2(d.order), apart = order_planes_apart(d.order); \
       unsigned kk = k;                                                                                               \
       if (il > 1) {                                                                                                  \
         const unsigned g = k % il, r = k / il, j = r % chunks, s = (r / chunks) * il + g;                            \
         kk = ((s * apart) % (per_xcd / chunks)) * chunks + j;                                                        \
       }                                                                                                              \
-      kk = (kk + x * ((unsigned)d.order & 4095u)) % per_xcd;                                                         \
+      kk = (kk + x * order_xcd_offset(d.order)) % per_xcd;                                                           \
       tile = x * per_xcd + kk;                                                                                       \
-      ord_hash = (((unsigned)d.order >> 18) & 1u) ? x + k : x;                                                       \
+      ord_hash = order_walk_hash(d.order) ? x + k : x;                                                               \
     }                                                                                                                \
   }
 #define GFFT_AFTER_LOADS
@@ -1212,7 +1202,7 @@ fft_pow2_kernel(PassDesc d, const void *__restrict__ in, void *__restrict__ out)
 // Coherence between workgroups on different XCDs (whose L2s are not coherent within a launch) is per access:
 // A stores the hand-off data at system scope (written through the L2), waits for the acknowledgements and
 // only then raises the plane's counter; B spins on the counter with device-scope loads and reads the slot
-// at system scope (FLAGS 2048 / 4096 of pow2_body).  Whole-L2 write-backs / invalidates (what an acquire /
+// at system scope (PF_SYS_STORE / PF_SYS_LOAD of pow2_body).  Whole-L2 write-backs / invalidates (what an acquire /
 // release pair compiles to) measured 2x SLOWER than two launches; this form 1.3-1.4x faster on a copy pair
 // (tools/probes/mall_ring_probe.hip, profiles/r03_mall_ring_probe_*.txt).
 // (struct FusedDesc: gfft_internal.h)
@@ -1478,11 +1468,12 @@ template <typename real, int N, int R, int T, bool COLS, bool SPLIT, int MINW, i
 hipError_t launch_pow2_one(const PassDesc &d, const void *in, void *out, hipStream_t s) {
   constexpr int NT = Geo<N, R, RADS...>::TPC;
   constexpr int threads = T * NT;
+  constexpr bool TRUNC = (FLAGS & PF_TRUNC) != 0, TRUNC_LOAD = (FLAGS & PF_TRUNC_LOAD) != 0, TRANSPOSE = (FLAGS & PF_TRANSPOSE_STORE) != 0, ORDER = (FLAGS & PF_ORDER) != 0;
   // (plans whose stages keep different numbers of values per thread: plain natural-layout complex passes only)
   if (!Geo<N, R, RADS...>::UNIFORM && (d.in_lgp || d.out_lgp || d.in_tlg || d.out_tlg || d.tw_hi || d.tr_jump)) return hipErrorInvalidValue;
   static_assert(threads >= 64 && threads <= 1024, "workgroup size");
-  constexpr size_t lds_x = (sizeof...(RADS) > 1 || (FLAGS & 32) || MODE == MODE_R2C_H || MODE == MODE_C2R_H) ? (size_t)T * Lds<N, COLS, T, (SPLIT && sizeof(real) == 4), FirstRadix<RADS...>::value>::CS * (SPLIT ? sizeof(real) : 2 * sizeof(real)) : 0;
-  constexpr size_t lds_f = (FLAGS & 16) ? (size_t)T * 2 * sizeof(real) : 0;
+  constexpr size_t lds_x = (sizeof...(RADS) > 1 || TRANSPOSE || MODE == MODE_R2C_H || MODE == MODE_C2R_H) ? (size_t)T * Lds<N, COLS, T, (SPLIT && sizeof(real) == 4), FirstRadix<RADS...>::value>::CS * (SPLIT ? sizeof(real) : 2 * sizeof(real)) : 0;
+  constexpr size_t lds_f = TRUNC ? (size_t)T * 2 * sizeof(real) : 0;
   constexpr size_t lds = lds_x > lds_f ? lds_x : lds_f;
   static_assert(lds <= 160 * 1024, "LDS budget");
   // split layouts: whole thread slots per block, plain complex passes only
@@ -1491,7 +1482,7 @@ hipError_t launch_pow2_one(const PassDesc &d, const void *in, void *out, hipStre
     if (((R >> lg) << lg) != R || MODE != MODE_C2C || BIGTW) return hipErrorInvalidValue;
     // (next to a fused truncation / padding the blocks sit on the PLAIN side only; the truncated side's
     // are PassDesc::tr_jump)
-    if ((FLAGS & 16) && ((FLAGS & 64) ? d.in_lgp : d.out_lgp)) return hipErrorInvalidValue;
+    if (TRUNC && (TRUNC_LOAD ? d.in_lgp : d.out_lgp)) return hipErrorInvalidValue;
   }
   // tile-major lines (ROWS): thread slots advance by NT entries = whole tiles
   if (!COLS && ((d.in_tlg && (NT & ((1 << d.in_tlg) - 1))) || (d.out_tlg && (NT & ((1 << d.out_tlg) - 1)))))
@@ -1518,10 +1509,9 @@ hipError_t launch_pow2_one(const PassDesc &d, const void *in, void *out, hipStre
     if (grid >= 64) grid = grid / 8 * 8; else dd.swizzle = 0;
   }
   // tile / row orders (PassDesc::order): XCD-contiguous walks over whole planes of a natural-layout batch only
-  if constexpr ((FLAGS & 131072) != 0 && COLS && !BIGTW) {
-    const int64_t chunks = (d.inner + T - 1) / T, il = (int64_t)1 << ((d.order >> 16) & 3);
-    const int64_t apart = ((d.order >> 19) & 127) ? ((d.order >> 19) & 127) : 37;
-    int64_t a = ntiles / 8 / chunks, b = apart;        // (the planes of an XCD are walked in steps of `apart`: coprime, or the walk is no permutation)
+  if constexpr (ORDER && COLS && !BIGTW) {
+    const int64_t chunks = (d.inner + T - 1) / T, il = (int64_t)1 << order_planes_log2(d.order);
+    int64_t a = ntiles / 8 / chunks, b = order_planes_apart(d.order);        // (the planes of an XCD are walked in steps of `apart`: coprime, or the walk is no permutation)
     while (b) { const int64_t r = a % b; a = b; b = r; }
     if (!dd.swizzle || d.flat || d.in_lgp || d.out_lgp || ntiles % 8 || (ntiles / 8) % (il * chunks) || (il > 1 && a != 1))
       dd.order = 0;
@@ -1547,7 +1537,7 @@ hipError_t half_launch(const PassDesc &d, const void *in, void *out, hipStream_t
   if constexpr (R == 20 && !kFusedPadMix5) {
     // 5^c 2^k lengths: plain and uneven-block kernels only
     if (d.tr_dir) return hipErrorInvalidValue;
-    if (d.ub_p > 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 128, MODE, false, RADS...>(d, in, out, s);
+    if (d.ub_p > 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_UNEVEN_BLOCKS, MODE, false, RADS...>(d, in, out, s);
     return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 0, MODE, false, RADS...>(d, in, out, s);
   } else {
     return half_launch_all<real, MODE, N, R, T, SPLIT, RADS...>(d, in, out, s);
@@ -1556,43 +1546,40 @@ hipError_t half_launch(const PassDesc &d, const void *in, void *out, hipStream_t
 template <typename real, int MODE, int N, int R, int T, bool SPLIT, int... RADS>
 hipError_t half_launch_all(const PassDesc &d, const void *in, void *out, hipStream_t s) {
   if (d.ub_p > 1 && d.tr_dir == 0)
-    return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 128, MODE, false, RADS...>(d, in, out, s);
+    return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_UNEVEN_BLOCKS, MODE, false, RADS...>(d, in, out, s);
   if (d.ub_p > 1) {
     // ... of the KEPT entries of a truncated half spectrum (3/2-rule transforms on several ranks)
     if constexpr (MODE == MODE_R2C_H) {
-      if (d.tr_dir == 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 16 | 128, MODE, false, RADS...>(d, in, out, s);
+      if (d.tr_dir == 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_TRUNC | PF_UNEVEN_BLOCKS, MODE, false, RADS...>(d, in, out, s);
     } else {
-      if (d.tr_dir == 2) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 16 | 64 | 128, MODE, false, RADS...>(d, in, out, s);
+      if (d.tr_dir == 2) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_TRUNC | PF_TRUNC_LOAD | PF_UNEVEN_BLOCKS, MODE, false, RADS...>(d, in, out, s);
     }
     return hipErrorInvalidValue;
   }
   if (d.tr_dir == 0) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 0, MODE, false, RADS...>(d, in, out, s);
   if constexpr (MODE == MODE_R2C_H) {
-    if (d.tr_dir == 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 16, MODE, false, RADS...>(d, in, out, s);
+    if (d.tr_dir == 1) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_TRUNC, MODE, false, RADS...>(d, in, out, s);
   } else {
-    if (d.tr_dir == 2) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, 16 | 64, MODE, false, RADS...>(d, in, out, s);
+    if (d.tr_dir == 2) return launch_pow2_one<real, N, R, T, false, SPLIT, 1, PF_TRUNC | PF_TRUNC_LOAD, MODE, false, RADS...>(d, in, out, s);
   }
   return hipErrorInvalidValue;
 }
 
 // runtime (mode, four-step twiddle) -> instantiation
-// TABLE_FLAGS = kernel FLAGS, plus 512: this table entry is never picked for a four-step pass (the
-// caller's condition excludes d.tw_hi), so its four-step-twiddle kernel is not instantiated; plus 1024: no
-// fused truncation / zero-padding kernels for this entry (plan.cpp fused_pad_ok keeps such plans on the
-// separate gfft_truncate / gfft_pad kernels)
+// TABLE_FLAGS = kernel FLAGS plus the TF_* bits (gfft_internal.h)
 template <typename real, int N, int R, int T, bool COLS, bool SPLIT, int MINW, int TABLE_FLAGS, int... RADS>
 hipError_t launch_pow2_inst(const PassDesc &d, const void *in, void *out, hipStream_t s) {
-  constexpr int FLAGS = TABLE_FLAGS & ~(512 | 1024);
-  constexpr bool BIG_OK = COLS && !(TABLE_FLAGS & 512);     // (four-step passes always run strided, plan.cpp plan_fourstep)
-  if constexpr ((TABLE_FLAGS & 1024) != 0) {
+  constexpr int FLAGS = TABLE_FLAGS & ~(TF_NO_FOURSTEP | TF_NO_TRUNC);
+  constexpr bool BIG_OK = COLS && !(TABLE_FLAGS & TF_NO_FOURSTEP);     // (four-step passes always run strided, plan.cpp plan_fourstep)
+  constexpr bool TRUNC_OK = !(TABLE_FLAGS & TF_NO_TRUNC);
+  if constexpr (!TRUNC_OK) {
     if (d.tr_dir) return hipErrorInvalidValue;
   }
-  // FLAGS & 8: complex-to-complex, no four-step twiddle (fewer instantiations of fat configurations)
-  if constexpr ((FLAGS & 32) != 0) {
+  if constexpr ((FLAGS & PF_TRANSPOSE_STORE) != 0) {
     // transposing store: complex strided pass, with or without the four-step twiddle
     if (d.mode != MODE_C2C || d.tr_dir || d.in_lgp || d.out_lgp || !d.tw_hi) return hipErrorInvalidValue;
     return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, FLAGS, MODE_C2C, true, RADS...>(d, in, out, s);
-  } else if constexpr (FLAGS != 0) {
+  } else if constexpr (FLAGS != 0) {      // (any other bit, PF_C2C_ONLY where nothing else is wanted: one complex kernel, no four-step twiddle)
     if (d.tw_hi) return hipErrorInvalidValue;
     if (d.mode != MODE_C2C || d.tr_dir) return hipErrorInvalidValue;
     return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, FLAGS, MODE_C2C, false, RADS...>(d, in, out, s);
@@ -1604,11 +1591,11 @@ hipError_t launch_pow2_inst(const PassDesc &d, const void *in, void *out, hipStr
         return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, FLAGS, MODE_C2C, true, RADS...>(d, in, out, s);
       }
     }
-    if constexpr (!(TABLE_FLAGS & 1024)) {
-      if (d.tr_dir == 1 && d.mode == MODE_C2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, 16, MODE_C2C, false, RADS...>(d, in, out, s);
-      if (d.tr_dir == 1 && d.mode == MODE_R2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, 16, MODE_R2C, false, RADS...>(d, in, out, s);
-      if (d.tr_dir == 2 && d.mode == MODE_C2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, 16 | 64, MODE_C2C, false, RADS...>(d, in, out, s);
-      if (d.tr_dir == 2 && d.mode == MODE_C2R) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, 16 | 64, MODE_C2R, false, RADS...>(d, in, out, s);
+    if constexpr (TRUNC_OK) {
+      if (d.tr_dir == 1 && d.mode == MODE_C2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, PF_TRUNC, MODE_C2C, false, RADS...>(d, in, out, s);
+      if (d.tr_dir == 1 && d.mode == MODE_R2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, PF_TRUNC, MODE_R2C, false, RADS...>(d, in, out, s);
+      if (d.tr_dir == 2 && d.mode == MODE_C2C) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, PF_TRUNC | PF_TRUNC_LOAD, MODE_C2C, false, RADS...>(d, in, out, s);
+      if (d.tr_dir == 2 && d.mode == MODE_C2R) return launch_pow2_one<real, N, R, T, COLS, SPLIT, MINW, PF_TRUNC | PF_TRUNC_LOAD, MODE_C2R, false, RADS...>(d, in, out, s);
     }
     if (d.tr_dir) return hipErrorInvalidValue;
     switch (d.mode) {

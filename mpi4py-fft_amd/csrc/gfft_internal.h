@@ -35,18 +35,54 @@ template <typename T> __device__ __forceinline__ cx<T> cswap(cx<T> a) { return {
 // registers (fft_pow2_impl.h); the real side is addressed as complex pairs (strides in pairs).
 enum PassMode { MODE_C2C = 0, MODE_R2C = 1, MODE_C2R = 2, MODE_R2R = 3, MODE_R2C_H = 4, MODE_C2R_H = 5 };
 
+// ---- the FLAGS template parameter of the register-resident pass kernels (fft_pow2_impl.h, fft_pow2_body.inc) ----
+// An int, so that a kernel's name carries the plain number; the values are fixed.  Each bit, and what it needs:
+//   PF_NT_LOAD / PF_NT_STORE  non-temporal loads / stores (PF_NT: both) -- in the fused pairs, the streams that are not the hand-off
+//   PF_ACCESS_ONLY       skip the transform: the access pattern alone (probes, make VARIANTS=1)
+//   PF_C2C_ONLY          complex-to-complex only, no four-step twiddle: launch_pow2_inst builds one kernel for the table entry
+//                        instead of one per mode (so does any other bit; this one changes nothing else)
+//   PF_TRUNC             fused 3/2-rule adapter (PassDesc::tr_*): the truncating STORE (forward) ...
+//   PF_TRUNC_LOAD        ... or, with this bit, the zero-padding LOAD (backward); a switch at run time inside the load loop
+//                        serialises the loads.  Needs PF_TRUNC
+//   PF_TRANSPOSE_STORE   transposing store through LDS: a strided pass whose OUTPUT is contiguous along the transform axis (first
+//                        four-step pass, with its twiddle), or the mirror-image row pass.  Complex split-plane passes only
+//   PF_UNEVEN_BLOCKS     packed-real rows whose half-spectrum side is an all-to-all buffer of uneven blocks (PassDesc::ub_*).
+//                        Needs MODE_R2C_H / MODE_C2R_H
+//   PF_NO_PIN            A/B switch: the line is not pinned between the last stage and the stores
+//   PF_SYS_STORE / PF_SYS_LOAD  the output / input array is a hand-off buffer between workgroups of ONE launch (fused kernels):
+//                        stored with / loaded at SYSTEM scope (sc0 sc1: written through to the memory side, never served from a
+//                        possibly stale L2 line); see fft_fused2_kernel.  Plain complex passes and plain packed-real rows only:
+//                        exclude PF_TRUNC and PF_UNEVEN_BLOCKS
+//   PF_NATURAL           natural layouts on both sides (fused pairs): the exchange-buffer layout fields of the descriptor (blocks,
+//                        tile-major lines / columns, flat tiles, masked columns) are compile-time zeros, so neither their loads nor
+//                        the arithmetic on them survive (the fused kernels hold TWO descriptors)
+//   PF_BLOCKS_IN / PF_BLOCKS_OUT  ... except the equal blocks of the transformed axis on the input / output side (in_lgp / in_jump,
+//                        out_lgp / out_jump): the pair of a slab-decomposed transform's two local stages addresses the all-to-all
+//                        buffer itself (gfft_plan_create_guru2); the other side of such a pass is the hand-off ring.  Need PF_NATURAL
+//   PF_ORDER             tiles and rows are taken in the order IN TIME of PassDesc::order; addresses, values and operations per
+//                        element are those of the plain order.  Plain strided complex passes on natural lines only: excludes
+//                        PF_TRUNC, PF_TRANSPOSE_STORE, PF_UNEVEN_BLOCKS, PF_SYS_STORE, PF_SYS_LOAD
+// The rules are static_asserts at the top of fft_pow2_body.inc.
+enum : int {
+  PF_NT_LOAD = 1, PF_NT_STORE = 2, PF_NT = PF_NT_LOAD | PF_NT_STORE, PF_ACCESS_ONLY = 4, PF_C2C_ONLY = 8, PF_TRUNC = 16,
+  PF_TRANSPOSE_STORE = 32, PF_TRUNC_LOAD = 64, PF_UNEVEN_BLOCKS = 128, PF_NO_PIN = 256, PF_SYS_STORE = 2048, PF_SYS_LOAD = 4096,
+  PF_NATURAL = 8192, PF_BLOCKS_IN = 32768, PF_BLOCKS_OUT = 65536, PF_ORDER = 131072,
+  // TABLE_FLAGS of launch_pow2_inst = kernel FLAGS plus these two, which it strips: bits of a launch-table entry, not of a kernel.
+  //   TF_NO_FOURSTEP  the entry is never picked for a four-step pass (the caller's condition excludes d.tw_hi), so its
+  //                   four-step-twiddle kernel is not instantiated
+  //   TF_NO_TRUNC     no PF_TRUNC kernels for the entry: a pass with d.tr_dir is an error (plan.cpp fused_pad_ok keeps such plans
+  //                   on the separate gfft_truncate / gfft_pad kernels)
+  TF_NO_FOURSTEP = 512, TF_NO_TRUNC = 1024
+};
+
 struct PassDesc {
   int n;          // logical transform length
   int mode;       // PassMode
   int conj_in;    // conjugate on load   (inverse transform = conj . forward . conj)
   int conj_out;   // conjugate on store
   int swizzle;    // XCD-contiguous tile order (speed only)
-  // Order IN TIME of the tiles of an XCD-contiguous walk and of the rows of a tile (speed only: no byte, address or
-  // operation changes -- kernels built with FLAGS & 131072, fft_pow2_impl.h; 0 = the plain order).  Bits 0-11: XCD x starts
-  // x * (these bits) tiles into its eighth and wraps; bits 12-13: a tile issues its loads / stores from slot q0 on, one of
-  // 2 (1) or 4 (2) rotations by the tile's hash; bits 14-15: thread rows rotate by 5 (1) or 4 (2) times the hash; bits
-  // 16-17: the tiles an XCD runs together come from 2 (1), 4 (2) or 8 (3) planes, bits 19-25 (0 = 37) planes apart; bit 18:
-  // the hash is XCD + position in the walk instead of the XCD alone
+  // Order IN TIME of the tiles of an XCD-contiguous walk and of the rows of a tile (speed only: no byte, address or operation
+  // changes -- PF_ORDER kernels; 0 = the plain order).  A packed word: the order_*() accessors below are its layout
   int order;
   // fused 3/2-rule adapters (register kernels): 0 none, 1 truncate on store, 2 zero-pad on load
   int tr_dir, tr_n, tr_N, tr_even;
@@ -128,6 +164,21 @@ struct PassDesc {
   int tw_L;
 };
 
+// PassDesc::order field by field.  The word is public (gfft_set_option("tile_order", ...)): the layout does not move.
+enum : int { ORD_Q0_WAYS = 12, ORD_ROW_ROT = 14, ORD_PLANES_LOG2 = 16, ORD_WALK_HASH = 18, ORD_PLANES_APART = 19 };   // first bit of each field
+// bits 0-11: XCD x starts x * (this many) tiles into its eighth and wraps
+__host__ __device__ constexpr unsigned order_xcd_offset(int o) { return (unsigned)o & 4095u; }
+// bits 12-13: a tile issues its loads / stores from slot q0 on, one of 2 (1) or 4 (2) rotations by the tile's hash
+__host__ __device__ constexpr unsigned order_q0_ways(int o) { return ((unsigned)o >> ORD_Q0_WAYS) & 3u; }
+// bits 14-15: thread rows rotate by 5 (1) or 4 (2) times the hash
+__host__ __device__ constexpr unsigned order_row_rot(int o) { return ((unsigned)o >> ORD_ROW_ROT) & 3u; }
+// bits 16-17: the tiles an XCD runs together come from 2 (1), 4 (2) or 8 (3) planes ...
+__host__ __device__ constexpr unsigned order_planes_log2(int o) { return ((unsigned)o >> ORD_PLANES_LOG2) & 3u; }
+// bit 18: the hash is XCD + position in the walk instead of the XCD alone
+__host__ __device__ constexpr bool order_walk_hash(int o) { return (((unsigned)o >> ORD_WALK_HASH) & 1u) != 0; }
+// bits 19-25: ... this many planes apart (0 = 37)
+__host__ __device__ constexpr unsigned order_planes_apart(int o) { return (((unsigned)o >> ORD_PLANES_APART) & 127u) ? (((unsigned)o >> ORD_PLANES_APART) & 127u) : 37u; }
+
 // pointwise helpers of the embedding fallbacks (Bluestein, long real transforms): lines of the
 // array [outer][nin|nout][inner] are copied into / out of a complex scratch [outer][Lw][inner]
 struct PointDesc {
@@ -202,7 +253,7 @@ enum FusedKind { FUSED_ROWS_COLS = 0, FUSED_COLS_ROWS = 1, FUSED_FOURSTEP = 2, F
                  FUSED_R2C_PLANES = 5, FUSED_COLS_C2R = 6,
                  // the two LOCAL stages of a slab-decomposed transform, plane by plane, with the all-to-all buffer addressed by
                  // the pair itself (gfft_plan_create_guru2): [rows -> strided, output in blocks] forward, [strided, input in
-                 // blocks -> rows] backward -- the kernels of 3 / 1 with the block jump of the transformed axis kept (FLAGS 65536 / 32768)
+                 // blocks -> rows] backward -- the kernels of 3 / 1 with the block jump of the transformed axis kept (PF_BLOCKS_OUT / PF_BLOCKS_IN)
                  FUSED_PLANES_2D_B = 7, FUSED_PLANES_CR_B = 8,
                  // ... of a REAL slab-decomposed transform (gfft_plan_create_guru2_real): the kernels of 5 / 6 with the block jump of the
                  // strided axis kept on the half-spectrum side -- [r2c rows -> strided, output in blocks] forward, [strided, input in

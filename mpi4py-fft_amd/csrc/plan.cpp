@@ -271,7 +271,7 @@ bool real_half_mixv_ok(int64_t m) { return !opts().force_generic && opts().mixv 
 
 // lengths whose kernels carry the fused 3/2-rule truncation / zero-padding adapters: every register-kernel
 // length except 5^c 2^k, whose adapters only a `make VARIANTS=1` library instantiates (fft_pow2_impl.h
-// TABLE_FLAGS & 1024, kFusedPadMix5) -- plans on those lengths keep the separate gfft_truncate / gfft_pad
+// TF_NO_TRUNC, kFusedPadMix5) -- plans on those lengths keep the separate gfft_truncate / gfft_pad
 // kernels.  `n_axis`: transformed length of a complex axis, or the COMPLEX length (half) of a packed-real row.
 bool fused_pad_ok(int64_t n_axis) {
 #ifdef GFFT_VARIANTS
@@ -1523,7 +1523,7 @@ int plan_fused3(gfft_plan_s *pl) {
       dB.batch = n0; dB.inner = 1; dB.in_is = 0; dB.out_is = 0; dB.in_os = P; dB.out_os = n1 * n2;
       int64_t a_plane = w_i1 * esz;
       if (wtile) {
-        // the pair's kernels take natural-layout descriptors only (FLAGS 8192): the tile-major columns as (tile, column in tile)
+        // the pair's kernels take natural-layout descriptors only (PF_NATURAL): the tile-major columns as (tile, column in tile)
         dA.mid = Pu / TWc; dA.inner = TWc;
         dA.in_ms = wtS; dA.in_is = 1; dA.in_ilg = 0; dA.in_iS = 0;
         dA.out_ms = TWc;     dA.out_is = 1; dA.out_ilg = 0; dA.out_iS = 0;
@@ -1604,7 +1604,7 @@ int plan_fused3(gfft_plan_s *pl) {
   // (+-0.03, +0.04 ... +0.13 ms).  The kernel's ACCESS PATTERN ALONE loses under the same order (+0.13 ms): the gain is not in
   // the placement of the requests.  Only that shape was measured: only it takes the order by default.
   if (prec == GFFT_F64 && !real && !tr && is_pow2(n0) && is_pow2(n1) && is_pow2(n2))
-    pl->tile_order = (n0 == 1024 && n1 == 1024 && n2 == 1024) ? ((1 << 16) | (3 << 19)) : 0;
+    pl->tile_order = (n0 == 1024 && n1 == 1024 && n2 == 1024) ? ((1 << ORD_PLANES_LOG2) | (3 << ORD_PLANES_APART)) : 0;      // (two planes together, 3 apart)
   // Workgroups per launch.  Each walks tiles block, block + grid, ...; more, shorter walks balance the
   // tail better, too many lose the overlap of one tile's stores with the next one's loads.  Clean A/B
   // on fixed caller arrays (tools/ab_option_probe.py grid_cap ...), fwd + bwd per step: 1024^3 c128
@@ -1799,7 +1799,7 @@ static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np
   pr.d.in_es = pr.d.out_es = 1;
   pr.d.scale = 1.0;
   // strided: complex length n1 along the H columns of a plane; the last tile of columns is masked by `inner` itself (the fused
-  // kernels drop inner_ld / inner_st, FLAGS 8192), so nothing is read or written beyond column H - 1 on either side
+  // kernels drop inner_ld / inner_st, PF_NATURAL), so nothing is read or written beyond column H - 1 on either side
   Pass pc;
   pc.regk = true;
   pc.cols = true;

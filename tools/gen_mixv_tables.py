@@ -140,14 +140,14 @@ def configs(real_bytes):
             while Tw >= 4 and Tw * lds_words(n, Tw, False) * 8 > 160 * 1024:
                 Tw //= 2
             if Tw >= T and Tw * tpc_w >= 64:
-                wide = ('1', 2 * R, Tw, 2 if Tw * tpc_w > 256 else 1, '8 | 3')
+                wide = ('1', 2 * R, Tw, 2 if Tw * tpc_w > 256 else 1, 'PF_C2C_ONLY | PF_NT')
         if n in ALTS and real_bytes == 4 and Rc != R:
             _, tpc_n = geometry(n, R, rads)
             Tn = pow2_floor(max(1, min(32, 1024 // tpc_n)))
             while Tn >= 4 and Tn * lds_words(n, Tn, True) * 4 > 160 * 1024:
                 Tn //= 2
             if Tn >= 4 and Tn * tpc_n >= 64:
-                wide = ('2', R, Tn, 4 if Tn * tpc_n > 512 else (2 if Tn * tpc_n > 256 else 1), '8')
+                wide = ('2', R, Tn, 4 if Tn * tpc_n > 512 else (2 if Tn * tpc_n > 256 else 1), 'PF_C2C_ONLY')
         cols.append((n, Rc, T, minw, r, wide))
     return sizes, rows, cols
 
@@ -158,7 +158,7 @@ HDR64 = '''// fp64 (complex128) one-pass kernels for 7-smooth lengths that are n
 // No single number of values per thread serves a radix-15 and a radix-16 stage; here every stage keeps as many as its
 // radix divides -- 15 of the 16 in the radix-15 stage -- on a column of max_s n / R_s threads (Geo / StageV,
 // fft_pow2_impl.h).  The first radix is never a power of two: its scatter runs in odd multiples (no LDS slot padding needed).
-// Plain complex passes only (TABLE_FLAGS 8): natural layouts, no fused truncation, no four-step twiddle -- the planner keeps
+// Plain complex passes only (PF_C2C_ONLY): natural layouts, no fused truncation, no four-step twiddle -- the planner keeps
 // other uses of these lengths on the two-pass / generic paths -- plus plain packed-real rows of twice the length.
 // The reference's own tests live on such sizes (tests/test_libfft.py:26-27, tests/test_mpifft.py:57-111).
 // GENERATED by tools/gen_mixv_tables.py -- edit the generator, not the cases.
@@ -172,13 +172,13 @@ BODY = '''#include "fft_pow2_impl.h"
 namespace gfft {
 
 %(wide_decl)s#define %(X)s(N, R, T, COLS, MINW, ...) \\
-  launch_pow2_inst<%(real)s, N, R, T, COLS, true, MINW, 8, __VA_ARGS__>(d, in, out, s)
+  launch_pow2_inst<%(real)s, N, R, T, COLS, true, MINW, PF_C2C_ONLY, __VA_ARGS__>(d, in, out, s)
 // lengths divisible by 3 -- what the 3/2-rule makes of 2^k, 5 x 2^k, 7 x 2^k ... (640 -> 960, 1280 -> 1920, 448 -> 672) -- also carry
-// the fused truncating store (forward) and zero-padding load (backward) of libfft.py:263-311 (FLAGS 16, 16 | 64)
-#define %(X)sT(N, R, T, COLS, MINW, ...)                                                                                          \\
-  (d.tr_dir == 1 ? launch_pow2_one<%(real)s, N, R, T, COLS, true, MINW, 16, MODE_C2C, false, __VA_ARGS__>(d, in, out, s)           \\
-   : d.tr_dir == 2 ? launch_pow2_one<%(real)s, N, R, T, COLS, true, MINW, 16 | 64, MODE_C2C, false, __VA_ARGS__>(d, in, out, s) \\
-                   : launch_pow2_inst<%(real)s, N, R, T, COLS, true, MINW, 8, __VA_ARGS__>(d, in, out, s))
+// the fused truncating store (forward) and zero-padding load (backward) of libfft.py:263-311 (PF_TRUNC, PF_TRUNC | PF_TRUNC_LOAD)
+#define %(X)sT(N, R, T, COLS, MINW, ...) \\
+  (d.tr_dir == 1 ? launch_pow2_one<%(real)s, N, R, T, COLS, true, MINW, PF_TRUNC, MODE_C2C, false, __VA_ARGS__>(d, in, out, s) \\
+   : d.tr_dir == 2 ? launch_pow2_one<%(real)s, N, R, T, COLS, true, MINW, PF_TRUNC | PF_TRUNC_LOAD, MODE_C2C, false, __VA_ARGS__>(d, in, out, s) \\
+                   : launch_pow2_inst<%(real)s, N, R, T, COLS, true, MINW, PF_C2C_ONLY, __VA_ARGS__>(d, in, out, s))
 %(supp)s
 hipError_t launch_mixv_%(sfx)s(const PassDesc &d, bool cols, int variant, const void *in, void *out, hipStream_t s) {
   (void)variant;
@@ -202,7 +202,7 @@ static hipError_t halfv_%(sfx)s(const PassDesc &d, const void *in, void *out, hi
   if (d.ub_p > 1) return hipErrorInvalidValue;
   if (d.tr_dir) {      // fused truncating store (r2c) / zero-padding load (c2r): the lengths divisible by 3
     if ((MODE == MODE_R2C_H) != (d.tr_dir == 1)) return hipErrorInvalidValue;
-    constexpr int TF = MODE == MODE_R2C_H ? 16 : (16 | 64);
+    constexpr int TF = MODE == MODE_R2C_H ? PF_TRUNC : (PF_TRUNC | PF_TRUNC_LOAD);
     switch (d.n) {
 %(halft)s
     }
