@@ -22,7 +22,9 @@ import numpy as np
 import torch
 
 
-def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False):
+def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False):
+    """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
+    `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L)."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -144,6 +146,12 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
               % (N[0], nsteps, ('fused-kernel' if fused else 'torch-expression') + (' + HIP graph replay' if graph else ''), elapsed,
                  elapsed / nsteps * 1e3, energy))
+    if spectrum:
+        E = spectral.SpectralOps(FFT, L).spectrum(U_hat)
+        if verbose and world.Get_rank() == 0:
+            print('  from U_hat: energy = %.12f, enstrophy = %.12f, %d shells' % (E[0].sum(), E[1].sum(), E.shape[1]))
+        FFT.destroy()
+        return energy, E
     FFT.destroy()
     return energy
 
@@ -155,6 +163,8 @@ if __name__ == '__main__':
     assert round(e - 0.124953117517, 7) == 0, e
     e = solve(w, verbose=True, fused=False)
     assert round(e - 0.124953117517, 7) == 0, e
+    e, E = solve(w, verbose=True, spectrum=True)
+    assert round(E[0].sum() - 0.124953117517, 7) == 0, E[0].sum()
     if w.Get_size() == 1:
         e = solve(w, verbose=True, graph=True)
         assert round(e - 0.124953117517, 7) == 0, e

@@ -289,7 +289,21 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *   gfft_ps_curl     out = 1j * (K x u_hat)                                   compute_curl, :76-80
  *   gfft_ps_cross    out = a x b, real fields, count = n0*n1*n2 per component   cross, :69-74
  *   gfft_ps_project  P = sum(du*K/|K|^2); du -= P*K; du -= nu*|K|^2*u_hat      compute_rhs, :88-90
- *   gfft_ps_rk_stage u = u0 + cb*du (skipped when d_u is NULL); u1 += ca*du; `count` real scalars   :112-116 */
+ *   gfft_ps_rk_stage u = u0 + cb*du (skipped when d_u is NULL); u1 += ca*du; `count` real scalars   :112-116
+ *   gfft_ps_spectrum shell spectrum of u_hat[ncomp][n0][n1][n2] in ONE read, every mode in double whatever the precision:
+ *                      b = floor(sqrt(k0^2 + k1^2 + k2^2) / dk + 0.5)      (modes with b >= nbins are dropped)
+ *                      e = 0.5 * w2[i2] * sum_c |u_hat_c|^2                (d_w2 NULL: weight 1)
+ *                      out[0][b] += e;  out[1][b] += |k|^2 e               d_out = double[2][nbins], OVERWRITTEN
+ *                    d_w2 carries the Hermitian double count of an r2c layout (1 at k2 = 0 and at the Nyquist column, 2
+ *                    elsewhere); d_k* / d_w2 are real vectors of the transform's precision.  For forward-normalised u_hat
+ *                    sum(out[0]) = <u.u>/2 and sum(out[1]) = <|grad u|^2>/2 (the enstrophy of a solenoidal field).
+ *                    Partial sums of the workgroups go through the stream's scratch (allocated by the first call; run it
+ *                    once before capturing it) and are added in a fixed order, no global floating-point atomics.
+ *                    Inside a workgroup the waves add to a shared histogram in arrival order, so a bin repeats from one
+ *                    call to the next to rounding (a few units in the last place), not bit for bit.
+ *                    nbins <= 4096 and n1, n2 <= 2^30, else GFFT_ERR_UNSUPPORTED; bad arguments (null pointers other
+ *                    than d_w2, ncomp < 1, nbins < 1, dk <= 0, precision) are GFFT_ERR_INVALID before a device is
+ *                    touched; an empty block (n0 n1 n2 = 0) writes zeros. */
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
                  int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
 int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream);
@@ -297,6 +311,9 @@ int gfft_ps_project(void *d_du_hat, const void *d_u_hat, const void *d_k0, const
                     int64_t n0, int64_t n1, int64_t n2, double nu, int precision, void *stream);
 int gfft_ps_rk_stage(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb,
                      double ca, int precision, void *stream);
+int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                     const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *d_out,
+                     int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

@@ -73,6 +73,8 @@ def _declare(lib):
         'gfft_ps_cross': (c.c_int, [vp, vp, vp, c.c_int64, c.c_int, vp]),
         'gfft_ps_project': (c.c_int, [vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int, vp]),
         'gfft_ps_rk_stage': (c.c_int, [vp, vp, vp, vp, c.c_int64, c.c_double, c.c_double, c.c_int, vp]),
+        'gfft_ps_spectrum': (c.c_int, [vp, c.c_int, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int,
+                                       vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -393,6 +395,14 @@ class HipEngine:
         check(lib().gfft_ps_rk_stage(None if tu is None else tu.data_ptr(), None if tu0 is None else tu0.data_ptr(),
                                      tu1.data_ptr(), tdu.data_ptr(), count, float(cb), float(ca), precision,
                                      current_stream()))
+
+    def ps_spectrum(self, tu, ncomp, k, w2, shape, dk, nbins, tout, precision):
+        """gfft_ps_spectrum: tout = double[2][nbins] on the device, overwritten; w2 None = weight 1."""
+        self.require_device(tu)
+        self.require_device(tout)
+        check(lib().gfft_ps_spectrum(tu.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                     None if w2 is None else w2.data_ptr(), shape[0], shape[1], shape[2], float(dk),
+                                     int(nbins), tout.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

@@ -334,6 +334,12 @@ hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void
                              int64_t n1, int64_t n2, double nu, int precision, hipStream_t s);
 hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
                         int precision, hipStream_t s);
+// shell spectrum (spectral.hip): `slabs` = ps_spectrum_scratch_bytes(nbins) bytes of stream-ordered scratch
+int ps_spectrum_max_bins();
+size_t ps_spectrum_scratch_bytes(int nbins);
+hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
+                              int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
+                              int precision, hipStream_t s);
 extern int g_copy_nt;
 hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
 hipError_t launch_tile_copy(const void *src, void *dst, int64_t outer, int64_t n, int64_t inner,

@@ -2968,6 +2968,27 @@ int gfft_ps_rk_stage(void *d_u, const void *d_u0, void *d_u1, const void *d_du, 
   return GFFT_OK;
 }
 
+int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                     const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *d_out,
+                     int precision, void *stream) {
+  // (arguments first: a bad call is refused without a device, like gfft_plan_create)
+  if (!d_u_hat || !d_k0 || !d_k1 || !d_k2 || !d_out || ncomp < 1 || nbins < 1 || !(dk > 0) || n0 < 0 || n1 < 0 || n2 < 0 ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_spectrum: bad argument");
+  if (nbins > ps_spectrum_max_bins()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_spectrum: more than 4096 bins");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30)) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_spectrum: axis longer than 2^30");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' partial histograms live in the stream's shared scratch: allocated by the first call, so later
+  // calls -- captured ones included -- allocate nothing
+  void *slabs = nullptr;
+  rc = scratch_pool().get((hipStream_t)stream, ps_spectrum_scratch_bytes(nbins), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_spectrum(d_u_hat, ncomp, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk, nbins, d_out, static_cast<double *>(slabs),
+                             precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
 int gfft_malloc(void **d_ptr, size_t bytes) {
   int rc = check_device();
   if (rc) return rc;

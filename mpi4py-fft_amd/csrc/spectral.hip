@@ -92,6 +92,162 @@ ps_rk_kernel(real *__restrict__ u, const real *__restrict__ u0, real *__restrict
   }
 }
 
+// ---- shell spectrum: E(k) and |k|^2 E(k) binned by |k|, one read of u_hat ----------------------------------------------
+// out[0][b] += e, out[1][b] += |k|^2 e with e = 0.5 w2[i2] sum_c |u_c|^2 and b = floor(|k| / dk + 0.5), all in double
+// (the input is converted before squaring).  The array is cut into contiguous chunks of flat modes, one per workgroup:
+// local rows are often shorter than a wave (11 entries in the tests, N / 2P on pencils), so a lane's mode is its flat
+// index, never its place in a row, and every lane looks up its own row's k0^2 + k1^2 (two cached reads).  The workgroup
+// walks its chunk 256 x V modes at a time, carrying (i0, i1, i2) of the step's first mode along with 32-bit divisions
+// instead of dividing a 64-bit flat index per mode.
+// Shell adds: neighbouring lanes mostly hold the same shell, so each row of 16 lanes first sums its runs of equal bins
+// (DPP row shifts, no LDS traffic); the last lane of a run adds the run to the workgroup's LDS histogram with the native
+// fp64 LDS add.  The histogram goes to this workgroup's slab of the stream's scratch, and ps_spectrum_sum_kernel adds
+// the slabs in workgroup order -- no floating-point atomics on global memory.  (Within a workgroup the waves' LDS adds
+// land in arrival order: bins repeat to rounding, not bit for bit, from one launch to the next.)
+// Cost per mode beside its 16 x ncomp bytes (8 x ncomp in fp32): two 32-bit divisions, an fp64 square root and an fp64
+// divide, 16 DPP moves and, per run of equal shells in a row of 16 lanes, two LDS adds.  A three-component fp64 field
+// has the most bytes per mode to hide that behind; a one-component fp32 field has a sixth of them and is the first
+// candidate for being bound by the arithmetic instead of HBM.  tools/spectrum_probe.py measures the fp64 vector case.
+constexpr int SP_MAX_WG = 2048;          // workgroups (= slabs) of one launch: 8 per CU
+constexpr int SP_MAX_BINS = 4096;        // 2 x 4096 doubles = 64 KiB of LDS, what a workgroup gets without opting in to more
+
+template <int CTRL>
+__device__ __forceinline__ double sp_dpp(double v) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+// one step of the segmented sum: take lane - D's partial sums if that lane belongs to this lane's run
+template <int D>
+__device__ __forceinline__ void sp_step(int lane, int start, double &e, double &f) {
+  const double te = sp_dpp<0x110 + D>(e), tf = sp_dpp<0x110 + D>(f);      // row_shr:D
+  if (lane - D >= start) { e += te; f += tf; }
+}
+
+// Adds (e, k2sq e) of every lane to bin b of the workgroup's histogram; b < 0 = nothing to add.  All 64 lanes call it.
+__device__ __forceinline__ void sp_wave_add(double *hist, int nbins, int b, double e, double f) {
+  const int lane = threadIdx.x & 63;
+  const int prev = __builtin_amdgcn_mov_dpp(b, 0x111, 0xf, 0xf, false);
+  const bool head = (lane & 15) == 0 || prev != b;                         // first lane of a run (runs end with their row of 16)
+  const unsigned long long heads = __ballot(head);
+  const int start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+  sp_step<1>(lane, start, e, f);
+  sp_step<2>(lane, start, e, f);
+  sp_step<4>(lane, start, e, f);
+  sp_step<8>(lane, start, e, f);
+  const bool tail = (lane & 15) == 15 || ((heads >> 1) >> lane) & 1;
+  if (tail && b >= 0) {
+    atomicAdd(&hist[b], e);
+    atomicAdd(&hist[nbins + b], f);
+  }
+}
+
+// the V modes one lane loads at once: 16 bytes, or 8 (fp32, V = 1)
+template <typename real, int V> struct alignas(sizeof(cx<real>) * V) sp_load { cx<real> m[V]; };
+
+template <typename real, int V>
+__device__ __forceinline__ void sp_acc(double (&s)[V], const sp_load<real, V> &v) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const double x = v.m[j].x, y = v.m[j].y;          // converted before squaring
+    s[j] += x * x + y * y;
+  }
+}
+
+// V = modes per lane and load: 1 (16 B in fp64, 8 B in fp32 when the array is not 16-B aligned) or 2 (fp32, 16 B)
+template <typename real, int V>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_spectrum_kernel(const cx<real> *__restrict__ u, int ncomp, const real *__restrict__ k0, const real *__restrict__ k1,
+                   const real *__restrict__ k2, const real *__restrict__ w2, uint32_t n1, uint32_t n2, int64_t count,
+                   int64_t chunk, double dk, int nbins, double *__restrict__ slabs) {
+  extern __shared__ double sp_hist[];
+  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) sp_hist[i] = 0.0;
+  __syncthreads();
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (i0, i1, i2) of the first mode of the current step, uniform over the workgroup
+  const int64_t row0 = begin / n2;
+  uint32_t c0 = (uint32_t)(begin - row0 * n2);
+  int64_t p0 = row0 / n1;
+  uint32_t r0 = (uint32_t)(row0 - p0 * n1);
+  for (int64_t base = begin; base < end; base += PS_THREADS * V) {
+    const int64_t e0 = base + (int64_t)threadIdx.x * V;
+    // this lane's first mode: at most (n2 + 256 V) / n2 rows and as many planes further on
+    uint32_t c = c0 + threadIdx.x * V;
+    uint32_t q = c / n2;
+    uint32_t i2 = c - q * n2;
+    q += r0;
+    const uint32_t pq = q / n1;
+    uint32_t i1 = q - pq * n1;
+    int64_t i0 = p0 + pq;
+    int b[V];
+    double en[V], kk[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) { b[j] = -1; en[j] = 0.0; kk[j] = 0.0; }
+    if (e0 < end) {                                      // (count and chunk are multiples of V when V == 2: all V or none)
+      double s[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) s[j] = 0.0;
+      // components `count` modes apart, three loads in flight for a vector field
+      const sp_load<real, V> *p = reinterpret_cast<const sp_load<real, V> *>(u + e0);
+      const int64_t comp = count / V;
+      int cc = 0;
+      for (; cc + 3 <= ncomp; cc += 3, p += 3 * comp) {
+        const sp_load<real, V> v0 = p[0], v1 = p[comp], v2 = p[2 * comp];
+        sp_acc(s, v0);
+        sp_acc(s, v1);
+        sp_acc(s, v2);
+      }
+      for (; cc < ncomp; ++cc, p += comp) sp_acc(s, *p);
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const double kx = k0[i0], ky = k1[i1], kz = k2[i2];
+        const double k2sq = (kx * kx + ky * ky) + kz * kz;
+        const double w = w2 ? (double)w2[i2] : 1.0;
+        const double sh = floor(sqrt(k2sq) / dk + 0.5);
+        b[j] = sh < (double)nbins ? (int)sh : -1;       // (a NaN wavenumber drops the mode too)
+        en[j] = 0.5 * w * s[j];
+        kk[j] = k2sq * en[j];
+        if (++i2 == n2) {                                // the pair's second mode may start the next row
+          i2 = 0;
+          if (++i1 == n1) { i1 = 0; ++i0; }
+        }
+      }
+    }
+    if (V == 2) {
+      // the pair's modes are neighbours along i2: same shell almost always; otherwise the second goes in on its own
+      if (b[V - 1] == b[0]) { en[0] += en[V - 1]; kk[0] += kk[V - 1]; }
+      else if (b[V - 1] >= 0) { atomicAdd(&sp_hist[b[V - 1]], en[V - 1]); atomicAdd(&sp_hist[nbins + b[V - 1]], kk[V - 1]); }
+    }
+    sp_wave_add(sp_hist, nbins, b[0], en[0], kk[0]);
+    // advance the step's first mode by 256 V
+    c = c0 + PS_THREADS * V;
+    q = c / n2;
+    c0 = c - q * n2;
+    q += r0;
+    const uint32_t pa = q / n1;
+    r0 = q - pa * n1;
+    p0 += pa;
+  }
+  __syncthreads();
+  double *slab = slabs + (int64_t)blockIdx.x * 2 * nbins;
+  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) slab[i] = sp_hist[i];
+}
+
+// out[i] = sum over the workgroups' slabs, in workgroup order (nwg == 0: an empty block, zeros).  One thread per output walks
+// the slabs serially, eight loads in flight: at most 2048 x 16 nbins bytes, nothing beside u_hat at 1024^3, but a
+// latency-bound tail on small arrays -- unmeasured; a fixed-order tree over more threads is the remedy if it shows.
+__global__ void __launch_bounds__(PS_THREADS)
+ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double *__restrict__ out) {
+  const int i = blockIdx.x * PS_THREADS + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+#pragma unroll 8
+  for (int w = 0; w < nwg; ++w) s += slabs[(int64_t)w * n + i];
+  out[i] = s;
+}
+
 }  // namespace
 
 hipError_t launch_ps_curl(const void *u, void *out, const void *k0, const void *k1, const void *k2, int64_t n0,
@@ -142,6 +298,42 @@ hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64
   else
     hipLaunchKernelGGL(ps_rk_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (float *)u, (const float *)u0,
                        (float *)u1, (const float *)du, count, (float)cb, (float)ca);
+  return hipGetLastError();
+}
+
+int ps_spectrum_max_bins() { return SP_MAX_BINS; }
+
+size_t ps_spectrum_scratch_bytes(int nbins) { return (size_t)SP_MAX_WG * 2 * nbins * sizeof(double); }
+
+hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
+                              int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
+                              int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  // fp32: two modes per 16-B load where every component starts 16-B aligned
+  const int V = (precision == 4 && count % 2 == 0 && (uintptr_t)u % 16 == 0) ? 2 : 1;
+  const int64_t step = (int64_t)PS_THREADS * V;
+  int64_t chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
+  chunk = (chunk + step - 1) / step * step;
+  const int nwg = count ? (int)((count + chunk - 1) / chunk) : 0;
+  const size_t lds = (size_t)2 * nbins * sizeof(double);
+  if (nwg) {
+    if (precision == 8)
+      hipLaunchKernelGGL((ps_spectrum_kernel<double, 1>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<double> *)u, ncomp,
+                         (const double *)k0, (const double *)k1, (const double *)k2, (const double *)w2, (uint32_t)n1,
+                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
+    else if (V == 2)
+      hipLaunchKernelGGL((ps_spectrum_kernel<float, 2>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<float> *)u, ncomp,
+                         (const float *)k0, (const float *)k1, (const float *)k2, (const float *)w2, (uint32_t)n1,
+                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
+    else
+      hipLaunchKernelGGL((ps_spectrum_kernel<float, 1>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<float> *)u, ncomp,
+                         (const float *)k0, (const float *)k1, (const float *)k2, (const float *)w2, (uint32_t)n1,
+                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(ps_spectrum_sum_kernel, dim3((2 * nbins + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, s, slabs,
+                     nwg, 2 * nbins, out);
   return hipGetLastError();
 }
 

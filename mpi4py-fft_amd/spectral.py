@@ -9,6 +9,11 @@ the device each of those steps is one HIP kernel (csrc/spectral.hip) that reads 
     project(du_hat, u_hat, nu)  P = sum(du*K/|K|^2); du -= P*K; du -= nu*|K|^2*u_hat      :88-90
     rk_stage(u, u0, u1, du, cb, ca)   u = u0 + cb*du;  u1 += ca*du         :112-116
 
+and so are the diagnostics a DNS reads every few steps, which the reference leaves to the user:
+
+    spectrum(u_hat)             E(k) and |k|^2 E(k) per shell of width dk, Hermitian-weighted, one read of u_hat
+    energy(u_hat), enstrophy(u_hat)   their totals: <u.u>/2 and <|grad u|^2>/2
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -35,6 +40,22 @@ def local_wavenumbers(fft, L=None):
             for i, (ki, si) in enumerate(zip(k, s))]
 
 
+def hermitian_weights(fft):
+    """How often each entry of this rank's block of spectral axis 2 counts in a sum over the FULL spectrum, as a 1-D
+    device array of the transform's real precision.  A real transform stores half of the last axis (the convention
+    of `local_wavenumbers`): the columns global k2 = 0 and, for even N2, k2 = N2/2 are their own mirror images and count
+    once, every other column stands for itself and its conjugate and counts twice.  Complex transforms: all ones."""
+    s = fft.local_slice(True)[-1]
+    n = int(fft.global_shape()[-1])
+    real = np.dtype(fft.dtype(False)).kind == 'f'
+    k2 = np.arange(int(fft.global_shape(True)[-1]))[s]
+    w = np.ones(len(k2))
+    if real:
+        w[(k2 != 0) & (2 * k2 != n)] = 2
+    rdt = np.dtype(fft.dtype(True).char.lower())
+    return torch.as_tensor(w.astype(rdt), device=fft.forward.output_array.device)
+
+
 def _prec(a):
     return _lib.precision_of(a.dtype)
 
@@ -44,23 +65,94 @@ def _t(a):
 
 
 class SpectralOps:
-    """The four kernels bound to one PFFT's local spectral shape and wavenumbers."""
+    """The kernels that need wavenumbers, bound to one PFFT's local spectral shape and wavenumbers."""
     def __init__(self, fft, L=None):
         assert len(fft.global_shape()) == 3, 'vector calculus kernels are 3-D'
         self.K = local_wavenumbers(fft, L)
         self.shape = tuple(int(n) for n in fft.shape(True))
+        self.W = hermitian_weights(fft)
+        self.comms = [c for c in fft.subcomm if c.Get_size() > 1]
+        # shell width and count from GLOBAL quantities: the same on every rank
+        unit = 2 * np.pi / (np.full(3, 2 * np.pi) if L is None else np.asarray(L, dtype=float))
+        self.dk = float(unit.min())
+        self.kmax = float(np.sqrt(sum((int(n) // 2 * d) ** 2 for n, d in zip(fft.global_shape(), unit))))
+
+    def _same_precision(self, precision):
+        # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
+        assert precision == (8 if self.K[0].dtype == torch.float64 else 4), 'field and transform differ in precision'
 
     def curl(self, u_hat, out):
         """out = 1j * (K x u_hat); both [3] + spectral shape, complex."""
         assert tuple(u_hat.shape) == (3,) + self.shape == tuple(out.shape)
+        self._same_precision(_prec(u_hat))
         _lib.engine().ps_curl(_t(u_hat), _t(out), self.K, self.shape, _prec(u_hat))
         return out
 
     def project(self, du_hat, u_hat, nu):
         """In place: pressure projection and viscous term of the Navier-Stokes right-hand side."""
         assert tuple(du_hat.shape) == (3,) + self.shape == tuple(u_hat.shape)
+        self._same_precision(_prec(du_hat))
         _lib.engine().ps_project(_t(du_hat), _t(u_hat), self.K, self.shape, nu, _prec(du_hat))
         return du_hat
+
+    def default_nbins(self, dk=None):
+        """Shells of width dk that hold every mode: floor(kmax / dk + 1/2) + 1 with the global largest |k|."""
+        return int(np.floor(self.kmax / (self.dk if dk is None else dk) + 0.5)) + 1
+
+    def shells(self, nbins, dk=None):
+        """Centre of each shell: arange(nbins) * dk (shell b holds |k| in [(b - 1/2) dk, (b + 1/2) dk))."""
+        return np.arange(nbins) * (self.dk if dk is None else dk)
+
+    def spectrum(self, u_hat, nbins=None, dk=None, out=None, reduce=True):
+        """Shell spectrum of a forward-normalised field: float64 [2][nbins],
+            [0][b] = sum over shell b of 0.5 * w * sum_c |u_hat_c|^2        (E(k); sums to <u.u>/2)
+            [1][b] = the same with each mode times |k|^2                     (sums to <|grad u|^2>/2)
+        with b = floor(|k| / dk + 1/2) and w the `hermitian_weights`; modes with b >= nbins are dropped.  u_hat is
+        [m] + spectral shape or, a scalar field, the spectral shape.  dk defaults to the smallest 2 pi / L_i, nbins to
+        `default_nbins(dk)` (nothing dropped).  One kernel, one read of u_hat, no array-sized temporaries.
+
+        reduce=True: the bins are added over the ranks of the PFFT's grid (allgather_obj, in rank order, so every rank
+        holds bit-identical bins) and returned as a numpy array -- which SYNCHRONISES the stream and copies 16 nbins
+        bytes to the host.  reduce=False: only this rank's kernel is enqueued, its device tensor (`out`, a contiguous
+        double tensor of shape [2, nbins], or a new one) is returned; with `out=` given nothing allocates after the
+        first call, so the call can be captured into a HIP graph.
+
+        Bins repeat from one call to the next to rounding (a few units in the last place), not bit for bit: inside a
+        workgroup the waves add to the shared histogram in the order they arrive.  Across workgroups and ranks the
+        order is fixed."""
+        t = _t(u_hat)
+        if tuple(t.shape) == self.shape:
+            ncomp = 1
+        else:
+            assert tuple(t.shape[1:]) == self.shape and t.dim() == 4, (tuple(t.shape), self.shape)
+            ncomp = int(t.shape[0])
+        assert t.is_contiguous() and t.dtype in (torch.complex64, torch.complex128)
+        self._same_precision(8 if t.dtype == torch.complex128 else 4)
+        dk = self.dk if dk is None else float(dk)
+        nbins = self.default_nbins(dk) if nbins is None else int(nbins)
+        if out is None:
+            out = torch.empty((2, nbins), dtype=torch.float64, device=t.device)
+        assert tuple(out.shape) == (2, nbins) and out.dtype == torch.float64 and out.is_contiguous()
+        _lib.engine().ps_spectrum(t, ncomp, self.K, self.W, self.shape, dk, nbins, out, 8 if t.dtype == torch.complex128 else 4)
+        if not reduce:
+            return out
+        bins = out.cpu().numpy()                       # (waits for the kernel)
+        _lib.check_async()
+        for c in self.comms:                           # one grid axis after the other: the same order on every rank
+            parts = c.allgather_obj(bins)
+            bins = parts[0].copy()
+            for p in parts[1:]:
+                bins += p
+        return bins
+
+    def energy(self, u_hat):
+        """<u.u>/2 over the whole box, from the spectral coefficients (synchronises: see `spectrum`)."""
+        return float(self.spectrum(u_hat)[0].sum())
+
+    def enstrophy(self, u_hat):
+        """<|grad u|^2>/2 over the whole box = the enstrophy <|curl u|^2>/2 of a solenoidal field; the dissipation rate
+        is 2 nu times it (synchronises: see `spectrum`)."""
+        return float(self.spectrum(u_hat)[1].sum())
 
 
 def cross(a, b, out):
