@@ -43,44 +43,22 @@ struct Fused512F32 {
 };
 int g_fuse2_f32_n512 = 1;
 
-bool fused2_supported_f32(int kind, int n_a, int n_b) {
-  if (n_a == 512 && n_b == 512) return g_fuse2_f32_n512 != 0 && (kind == FUSED_COLS_ROWS || kind == FUSED_PLANES_CR_B);
-  if (n_a != 1024 || n_b != 1024) return false;
-  return kind == FUSED_COLS_ROWS || kind == FUSED_FOURSTEP || kind == FUSED_PLANES_2D || kind == FUSED_PLANES_2D_B || kind == FUSED_PLANES_CR_B;
-}
-
-int fused2_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *ta, int *tb) {
-  if (dA.n == 512) {
-    if (kind != FUSED_COLS_ROWS && kind != FUSED_PLANES_CR_B) return -1;
-    *ta = (int)Fused512F32::ColsToRing::ntiles(dA);
-    *tb = (int)Fused512F32::RowsFromRing::ntiles(dB);
-    return 0;
+const FusedPair *fused2_select_f32(int kind, int n_a, int n_b) {
+  if (n_a == 512 && n_b == 512) {
+    if (!g_fuse2_f32_n512) return nullptr;
+    if (kind == FUSED_COLS_ROWS) return fused_pair<Fused512F32::ColsToRing, Fused512F32::RowsFromRing>();
+    if (kind == FUSED_PLANES_CR_B) return fused_pair<Fused512F32::ColsToRingB, Fused512F32::RowsFromRing>();
+    return nullptr;
   }
+  if (n_a != 1024 || n_b != 1024) return nullptr;
   switch (kind) {
-    case FUSED_COLS_ROWS: *ta = (int)ColsToRingF32::ntiles(dA); *tb = (int)RowsFromRingF32::ntiles(dB); return 0;
-    case FUSED_FOURSTEP: *ta = (int)Fused1024F32::FourStepFirst::ntiles(dA); *tb = (int)Fused1024F32::ColsFromRing::ntiles(dB); return 0;
-    case FUSED_PLANES_2D_B:
-    case FUSED_PLANES_2D: *ta = (int)Fused1024F32::RowsToRing::ntiles(dA); *tb = (int)Fused1024F32::ColsFromRing::ntiles(dB); return 0;
-    case FUSED_PLANES_CR_B: *ta = (int)Fused1024F32::ColsToRingB::ntiles(dA); *tb = (int)RowsFromRingF32::ntiles(dB); return 0;
+    case FUSED_COLS_ROWS: return fused_pair<ColsToRingF32, RowsFromRingF32>();
+    case FUSED_FOURSTEP: return fused_pair<Fused1024F32::FourStepFirst, Fused1024F32::ColsFromRing>();
+    case FUSED_PLANES_2D: return fused_pair<Fused1024F32::RowsToRing, Fused1024F32::ColsFromRing>();
+    case FUSED_PLANES_2D_B: return fused_pair<Fused1024F32::RowsToRing, Fused1024F32::ColsFromRingB>();
+    case FUSED_PLANES_CR_B: return fused_pair<Fused1024F32::ColsToRingB, RowsFromRingF32>();
   }
-  return -1;
-}
-
-hipError_t launch_fused2_f32(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev, const FusedDesc &f,
-                             const void *in, void *ring, void *out, hipStream_t s) {
-  if (dA.n == 512) {
-    if (kind == FUSED_COLS_ROWS) return launch_fused2<Fused512F32::ColsToRing, Fused512F32::RowsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    if (kind == FUSED_PLANES_CR_B) return launch_fused2<Fused512F32::ColsToRingB, Fused512F32::RowsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    return hipErrorInvalidValue;
-  }
-  switch (kind) {
-    case FUSED_COLS_ROWS: return launch_fused2<ColsToRingF32, RowsFromRingF32>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_FOURSTEP: return launch_fused2<Fused1024F32::FourStepFirst, Fused1024F32::ColsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_PLANES_2D: return launch_fused2<Fused1024F32::RowsToRing, Fused1024F32::ColsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_PLANES_2D_B: return launch_fused2<Fused1024F32::RowsToRing, Fused1024F32::ColsFromRingB>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_PLANES_CR_B: return launch_fused2<Fused1024F32::ColsToRingB, RowsFromRingF32>(dA, dB, dev, f, in, ring, out, s);
-  }
-  return hipErrorInvalidValue;
+  return nullptr;
 }
 
 }  // namespace gfft

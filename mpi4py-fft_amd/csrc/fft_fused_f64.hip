@@ -105,25 +105,7 @@ struct Fused896 {
 };
 int g_fuse2_mixv = 1;          // option fuse2_mixv
 
-extern int g_fuse2_n512;
 int g_fuse2_mixed = 1;        // option fuse2_mixed
-bool fused2_supported_f64(int kind, int variant, int n_a, int n_b) {
-  (void)kind;
-  if (n_a != n_b)     // unequal planes: [strided -> rows] only (the 3-D schedule's pair, the slab pair of either direction)
-    return g_fuse2_mixed != 0 && variant == 1 && ((n_a == 512 && n_b == 1024) || (n_a == 1024 && n_b == 512)) &&
-           (kind == FUSED_COLS_ROWS || kind == FUSED_PLANES_CR_B);
-  if (n_a == 960 || n_a == 896) return g_fuse2_mixv != 0 && variant == 1 && kind == FUSED_COLS_ROWS;
-#ifdef GFFT_VARIANTS
-  if (variant == 2 || variant == 4) return n_a == 1024;
-#endif
-  // (n = 512: measured for the 3-D schedule's pair only -- 512^3 per step 4.82 -> 4.27 ms with 24 planes of 4 MiB ahead,
-  // 5.34 ms with 16: profiles/r04_ab_fuse2_n512.txt)
-  // (... and the batched 2-D kind, [rows -> strided] on contiguous planes: (256,512,512) axes (1,2) 0.78 -> 0.69 ms, (512,512,512) 1.57 -> 1.34 ms)
-  if (variant == 5) return n_a == 512 && (kind == FUSED_COLS_ROWS || kind == FUSED_PLANES_CR_B);      // the square n = 512 pair on 32 lines per tile (Fused512T32)
-  if (variant == 1 && n_a == 512) return g_fuse2_n512 != 0 && (kind == FUSED_COLS_ROWS || kind == FUSED_PLANES_2D || kind == FUSED_PLANES_2D_B || kind == FUSED_PLANES_CR_B);
-  if (kind == FUSED_PLANES_2D_B || kind == FUSED_PLANES_CR_B) return variant == 1 && n_a == 1024;
-  return variant == 1 && n_a == 1024;
-}
 // option fuse2_n512: 0 = no n = 512 pairs, 1 = all of them on Fused512R32 (16 lines per tile, 256 threads, two workgroups per CU), 2 (the default since
 // round 6) = the [strided -> rows] pairs on Fused512T32 instead: 32 lines per tile = 512-byte hand-off segments on 512 threads.  Plans alternating
 // on the same arrays (tools/unequal_pair_probe.py n512, profiles/r06_n512_t32_probe.txt): the slab pair (256,512,512) -- config C3's local stages --
@@ -131,60 +113,47 @@ bool fused2_supported_f64(int kind, int variant, int n_a, int n_b) {
 // transform level (2.064 / 2.096 -> 2.085 / 2.089 ms).
 int g_fuse2_n512 = 2;
 
-int fused2_tiles_f64(int kind, int variant, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b) {
-#ifdef GFFT_VARIANTS
-  if (variant == 2) return fused2_tiles_kind<Fused1024x8>(kind, dA, dB, tiles_a, tiles_b);
-  if (variant == 4) return fused2_tiles_kind<Fused1024x8R32>(kind, dA, dB, tiles_a, tiles_b);
+// fuse2_option, the value of option fuse2: 1 = the default kernels (32 values per thread, one exchange, one 512-thread workgroup
+// per CU); 3 = once the round-3 kernels (16 values per thread, two exchanges, 1024 threads), the default ones since round 6;
+// 2 / 4 = (make VARIANTS=1) 8 lines per tile, two workgroups per CU
+static const FusedPair *fused2_select_f64(int kind, int fuse2_option, int n_a, int n_b) {
+  const bool cr = kind == FUSED_COLS_ROWS, crb = kind == FUSED_PLANES_CR_B;
+#ifdef GFFT_VARIANTS      // (make VARIANTS=1: the 8-lines-per-tile kernel sets, option fuse2 = 2 / 4 -- measured a quarter slower, above)
+  if (fuse2_option == 2 || fuse2_option == 4)
+    return (n_a != 1024 || n_b != 1024) ? nullptr : fuse2_option == 2 ? pair_of_kind<Fused1024x8>(kind) : pair_of_kind<Fused1024x8R32>(kind);
+#else
+  (void)fuse2_option;       // (every other value: the default kernels)
 #endif
-  if (dA.n == 960 || dA.n == 896) {
-    if (kind != FUSED_COLS_ROWS) return -1;
-    *tiles_a = (int)(dA.n == 960 ? Fused960::ColsToRing::ntiles(dA) : Fused896::ColsToRing::ntiles(dA));
-    *tiles_b = (int)(dA.n == 960 ? Fused960::RowsFromRing::ntiles(dB) : Fused896::RowsFromRing::ntiles(dB));
-    return 0;
+  if (n_a == n_b && (n_a == 960 || n_a == 896)) {
+    if (!g_fuse2_mixv || !cr) return nullptr;
+    return n_a == 960 ? fused_pair<Fused960::ColsToRing, Fused960::RowsFromRing>() : fused_pair<Fused896::ColsToRing, Fused896::RowsFromRing>();
   }
-  if (dA.n != dB.n || (dA.n == 512 && variant == 5)) {
-    *tiles_a = (int)(dA.n == 512 ? Fused512T32::ColsToRing::ntiles(dA) : Fused1024R32::ColsToRing::ntiles(dA));
-    *tiles_b = (int)(dB.n == 512 ? Fused512T32::RowsFromRing::ntiles(dB) : Fused1024R32::RowsFromRing::ntiles(dB));
-    return 0;
+  if (n_a == 512 && n_b == 512 && g_fuse2_n512 == 2 && (cr || crb))      // the square n = 512 pair on 32 lines per tile (Fused512T32)
+    return crb ? fused_pair<Fused512T32::ColsToRingB, Fused512T32::RowsFromRing>() : fused_pair<Fused512T32::ColsToRing, Fused512T32::RowsFromRing>();
+  if (n_a != n_b) {   // unequal planes: [strided -> rows] only (the 3-D schedule's pair, the slab pair of either direction)
+    if (!g_fuse2_mixed || !(cr || crb)) return nullptr;
+    if (n_a == 512 && n_b == 1024)
+      return crb ? fused_pair<Fused512T32::ColsToRingB, Fused1024R32::RowsFromRing>() : fused_pair<Fused512T32::ColsToRing, Fused1024R32::RowsFromRing>();
+    if (n_a == 1024 && n_b == 512)
+      return crb ? fused_pair<Fused1024R32::ColsToRingB, Fused512T32::RowsFromRing>() : fused_pair<Fused1024R32::ColsToRing, Fused512T32::RowsFromRing>();
+    return nullptr;
   }
-  if (kind == FUSED_PLANES_2D_B || kind == FUSED_PLANES_CR_B) {
-    // (same tile shapes as kinds 3 / 1: the block jump changes addresses, not tiles)
-    const int k = kind == FUSED_PLANES_2D_B ? FUSED_PLANES_2D : FUSED_COLS_ROWS;
-    return dA.n == 512 ? fused2_tiles_kind<Fused512R32>(k, dA, dB, tiles_a, tiles_b) : fused2_tiles_kind<Fused1024R32>(k, dA, dB, tiles_a, tiles_b);
-  }
-  if (dA.n == 512) return fused2_tiles_kind<Fused512R32>(kind, dA, dB, tiles_a, tiles_b);
-  return fused2_tiles_kind<Fused1024R32>(kind, dA, dB, tiles_a, tiles_b);
+  if (n_a != 512 && n_a != 1024) return nullptr;
+  // (n = 512: measured for the 3-D schedule's pair only -- 512^3 per step 4.82 -> 4.27 ms with 24 planes of 4 MiB ahead,
+  // 5.34 ms with 16: profiles/r04_ab_fuse2_n512.txt)
+  // (... and the batched 2-D kind, [rows -> strided] on contiguous planes: (256,512,512) axes (1,2) 0.78 -> 0.69 ms, (512,512,512) 1.57 -> 1.34 ms)
+  if (n_a == 512 && (!g_fuse2_n512 || !(cr || crb || kind == FUSED_PLANES_2D || kind == FUSED_PLANES_2D_B))) return nullptr;
+  if (kind == FUSED_PLANES_2D_B)
+    return n_a == 512 ? fused_pair<Fused512R32::RowsToRing, Fused512R32::ColsFromRingB>() : fused_pair<Fused1024R32::RowsToRing, Fused1024R32::ColsFromRingB>();
+  if (crb)
+    return n_a == 512 ? fused_pair<Fused512R32::ColsToRingB, Fused512R32::RowsFromRing>() : fused_pair<Fused1024R32::ColsToRingB, Fused1024R32::RowsFromRing>();
+  return n_a == 512 ? pair_of_kind<Fused512R32>(kind) : pair_of_kind<Fused1024R32>(kind);
 }
 
-hipError_t launch_fused2_f64(int kind, int variant, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs,
-                             const FusedDesc &f, const void *in, void *ring, void *out, hipStream_t s) {
-#ifdef GFFT_VARIANTS
-  if (variant == 2) return launch_fused2_kind<Fused1024x8>(kind, dA, dB, dev_descs, f, in, ring, out, s);
-  if (variant == 4) return launch_fused2_kind<Fused1024x8R32>(kind, dA, dB, dev_descs, f, in, ring, out, s);
-#endif
-  if (dA.n == 960 && kind == FUSED_COLS_ROWS) return launch_fused2<Fused960::ColsToRing, Fused960::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-  if (dA.n == 896 && kind == FUSED_COLS_ROWS) return launch_fused2<Fused896::ColsToRing, Fused896::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-  if (dA.n == 960 || dA.n == 896) return hipErrorInvalidValue;
-  if (dA.n == 512 && dB.n == 512 && variant == 5)
-    return kind == FUSED_PLANES_CR_B ? launch_fused2<Fused512T32::ColsToRingB, Fused512T32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s)
-                                     : launch_fused2<Fused512T32::ColsToRing, Fused512T32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-  if (dA.n != dB.n) {
-    if (kind != FUSED_COLS_ROWS && kind != FUSED_PLANES_CR_B) return hipErrorInvalidValue;
-    const bool blk = kind == FUSED_PLANES_CR_B;
-    if (dA.n == 512)
-      return blk ? launch_fused2<Fused512T32::ColsToRingB, Fused1024R32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s)
-                 : launch_fused2<Fused512T32::ColsToRing, Fused1024R32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-    return blk ? launch_fused2<Fused1024R32::ColsToRingB, Fused512T32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s)
-               : launch_fused2<Fused1024R32::ColsToRing, Fused512T32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-  }
-  if (kind == FUSED_PLANES_2D_B)
-    return dA.n == 512 ? launch_fused2<Fused512R32::RowsToRing, Fused512R32::ColsFromRingB>(dA, dB, dev_descs, f, in, ring, out, s)
-                       : launch_fused2<Fused1024R32::RowsToRing, Fused1024R32::ColsFromRingB>(dA, dB, dev_descs, f, in, ring, out, s);
-  if (kind == FUSED_PLANES_CR_B)
-    return dA.n == 512 ? launch_fused2<Fused512R32::ColsToRingB, Fused512R32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s)
-                       : launch_fused2<Fused1024R32::ColsToRingB, Fused1024R32::RowsFromRing>(dA, dB, dev_descs, f, in, ring, out, s);
-  if (dA.n == 512) return launch_fused2_kind<Fused512R32>(kind, dA, dB, dev_descs, f, in, ring, out, s);
-  return launch_fused2_kind<Fused1024R32>(kind, dA, dB, dev_descs, f, in, ring, out, s);
+const FusedPair *fused2_select(int precision, int kind, int fuse2_option, int n_a, int n_b) {
+  const bool f32 = precision == 4;
+  if (fused_kind_real(kind)) return f32 ? fused2_select_real_f32(kind, n_a, n_b) : fused2_select_real_f64(kind, n_a, n_b);
+  return f32 ? fused2_select_f32(kind, n_a, n_b) : fused2_select_f64(kind, fuse2_option, n_a, n_b);
 }
 
 }  // namespace gfft

@@ -1,4 +1,4 @@
-// Fused pass pairs: the launch tables shared by fft_fused_f64.hip / fft_fused_f32.hip.  A pair exists for a
+// Fused pass pairs: what the four tables fft_fused_f64.hip / _f32.hip / _real_f64.hip / _real_f32.hip share.  A pair exists for a
 // (precision, n) when both passes -- the row plan and the strided plan of the stand-alone tables
 // (fft_pow2_f64.hip / fft_pow2_f32.hip), rebuilt on 1024-thread workgroups -- fit one workgroup shape.
 #pragma once
@@ -10,31 +10,30 @@ namespace gfft {
 // PF_TRANSPOSE_STORE = first four-step pass -- gfft_internal.h)
 template <typename real, int N> struct FusedCfgs;
 
-template <typename C>
-static hipError_t launch_fused2_kind(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev, const FusedDesc &f,
-                                     const void *in, void *ring, void *out, hipStream_t s) {
-  switch (kind) {
-    case FUSED_PLANES_2D:
-    case FUSED_ROWS_COLS: return launch_fused2<typename C::RowsToRing, typename C::ColsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_COLS_ROWS: return launch_fused2<typename C::ColsToRing, typename C::RowsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_FOURSTEP: return launch_fused2<typename C::FourStepFirst, typename C::ColsFromRing>(dA, dB, dev, f, in, ring, out, s);
-    case FUSED_FOURSTEP_ROWS: return launch_fused2<typename C::FourStepFirstNat, typename C::RowsFromRingT>(dA, dB, dev, f, in, ring, out, s);
-  }
-  return hipErrorInvalidValue;
+// the FusedPair of two PassCfgs: tile counts and launch of the SAME two configurations
+template <typename A, typename B>
+const FusedPair *fused_pair() {
+  static const FusedPair p = {&A::ntiles, &B::ntiles, &launch_fused2<A, B>};
+  return &p;
 }
 
-// tiles per plane of either pass: rows and four-step first passes tile the flat batch, strided passes the
-// columns of each row of the batch
+// the complex kinds on one set of configurations C (tiles per plane of either pass: rows and four-step first passes tile the
+// flat batch, strided passes the columns of each row of the batch)
 template <typename C>
-static int fused2_tiles_kind(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b) {
+static const FusedPair *pair_of_kind(int kind) {
   switch (kind) {
     case FUSED_PLANES_2D:
-    case FUSED_ROWS_COLS: *tiles_a = (int)C::RowsToRing::ntiles(dA); *tiles_b = (int)C::ColsFromRing::ntiles(dB); return 0;
-    case FUSED_COLS_ROWS: *tiles_a = (int)C::ColsToRing::ntiles(dA); *tiles_b = (int)C::RowsFromRing::ntiles(dB); return 0;
-    case FUSED_FOURSTEP: *tiles_a = (int)C::FourStepFirst::ntiles(dA); *tiles_b = (int)C::ColsFromRing::ntiles(dB); return 0;
-    case FUSED_FOURSTEP_ROWS: *tiles_a = (int)C::FourStepFirstNat::ntiles(dA); *tiles_b = (int)C::RowsFromRingT::ntiles(dB); return 0;
+    case FUSED_ROWS_COLS: return fused_pair<typename C::RowsToRing, typename C::ColsFromRing>();
+    case FUSED_COLS_ROWS: return fused_pair<typename C::ColsToRing, typename C::RowsFromRing>();
+    case FUSED_FOURSTEP: return fused_pair<typename C::FourStepFirst, typename C::ColsFromRing>();
+    case FUSED_FOURSTEP_ROWS: return fused_pair<typename C::FourStepFirstNat, typename C::RowsFromRingT>();
   }
-  return -1;
+  return nullptr;
 }
+
+// the tables of the other three files, behind fused2_select (fft_fused_f64.hip)
+const FusedPair *fused2_select_f32(int kind, int n_a, int n_b);
+const FusedPair *fused2_select_real_f64(int kind, int n_a, int n_b);
+const FusedPair *fused2_select_real_f32(int kind, int n_a, int n_b);
 
 }  // namespace gfft

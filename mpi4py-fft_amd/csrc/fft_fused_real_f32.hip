@@ -17,25 +17,16 @@ typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_
 typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 16, 16, 4> Cols1024ToRingBF32;
 typedef PassCfg<float, 1024, 32, 32, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 16, 16, 4> Cols1024FromRingBF32;
 
-bool fused2_real_supported_f32(int kind, int n_a, int n_b) {
-  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) return n_a == 512 && n_b == 1024;
-  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) return n_a == 1024 && n_b == 512;
-  return false;
-}
-
-int fused2_real_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *ta, int *tb) {
-  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) { *ta = (int)R2CRows512ToRingF32::ntiles(dA); *tb = (int)Cols1024FromRingF32::ntiles(dB); return 0; }
-  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) { *ta = (int)Cols1024ToRingF32::ntiles(dA); *tb = (int)C2RRows512FromRingF32::ntiles(dB); return 0; }
-  return -1;
-}
-
-hipError_t launch_fused2_real_f32(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev, const FusedDesc &f,
-                                  const void *in, void *ring, void *out, hipStream_t s) {
-  if (kind == FUSED_R2C_PLANES) return launch_fused2<R2CRows512ToRingF32, Cols1024FromRingF32>(dA, dB, dev, f, in, ring, out, s);
-  if (kind == FUSED_COLS_C2R) return launch_fused2<Cols1024ToRingF32, C2RRows512FromRingF32>(dA, dB, dev, f, in, ring, out, s);
-  if (kind == FUSED_R2C_PLANES_B) return launch_fused2<R2CRows512ToRingF32, Cols1024FromRingBF32>(dA, dB, dev, f, in, ring, out, s);
-  if (kind == FUSED_COLS_C2R_B) return launch_fused2<Cols1024ToRingBF32, C2RRows512FromRingF32>(dA, dB, dev, f, in, ring, out, s);
-  return hipErrorInvalidValue;
+const FusedPair *fused2_select_real_f32(int kind, int n_a, int n_b) {
+  const bool r2c = kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B;
+  if (r2c ? !(n_a == 512 && n_b == 1024) : !(n_a == 1024 && n_b == 512)) return nullptr;
+  switch (kind) {
+    case FUSED_R2C_PLANES: return fused_pair<R2CRows512ToRingF32, Cols1024FromRingF32>();
+    case FUSED_COLS_C2R: return fused_pair<Cols1024ToRingF32, C2RRows512FromRingF32>();
+    case FUSED_R2C_PLANES_B: return fused_pair<R2CRows512ToRingF32, Cols1024FromRingBF32>();
+    case FUSED_COLS_C2R_B: return fused_pair<Cols1024ToRingBF32, C2RRows512FromRingF32>();
+  }
+  return nullptr;
 }
 
 }  // namespace gfft

@@ -33,50 +33,17 @@ typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF
 typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_LOAD | PF_C2C_ONLY | PF_SYS_STORE | PF_NATURAL | PF_BLOCKS_IN, MODE_C2C, false, 32, 32> Cols1024ToRingB;
 typedef PassCfg<double, 1024, 32, 16, true, true, PF_NT_STORE | PF_C2C_ONLY | PF_SYS_LOAD | PF_NATURAL | PF_BLOCKS_OUT, MODE_C2C, false, 32, 32> Cols1024FromRingB;
 
-bool fused2_real_supported_f64(int kind, int n_a, int n_b) {
-  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) return (n_a == 512 || n_a == 1024) && n_b == 1024;
-  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) {
-    if (n_a == 1024 && n_b == 1024) return g_c2r_2048 != 0;
-    return n_a == 1024 && n_b == 512;
+const FusedPair *fused2_select_real_f64(int kind, int n_a, int n_b) {
+  const bool r2c = kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B, c2r = kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B;
+  if (r2c && !((n_a == 512 || n_a == 1024) && n_b == 1024)) return nullptr;
+  if (c2r && !(n_a == 1024 && (n_b == 512 || (n_b == 1024 && g_c2r_2048 != 0)))) return nullptr;
+  switch (kind) {
+    case FUSED_R2C_PLANES: return n_a == 512 ? fused_pair<R2CRows512ToRing, Cols1024FromRing>() : fused_pair<R2CRows1024ToRing, Cols1024FromRing>();
+    case FUSED_COLS_C2R: return n_b == 1024 ? fused_pair<Cols1024ToRing, C2RRows1024FromRing>() : fused_pair<Cols1024ToRing, C2RRows512FromRing>();
+    case FUSED_R2C_PLANES_B: return n_a == 512 ? fused_pair<R2CRows512ToRing, Cols1024FromRingB>() : fused_pair<R2CRows1024ToRing, Cols1024FromRingB>();
+    case FUSED_COLS_C2R_B: return n_b == 1024 ? fused_pair<Cols1024ToRingB, C2RRows1024FromRing>() : fused_pair<Cols1024ToRingB, C2RRows512FromRing>();
   }
-  return false;
-}
-
-int fused2_real_tiles_f64(int kind, const PassDesc &dA, const PassDesc &dB, int *ta, int *tb) {
-  // (the _B kinds: same tile shapes -- the block jump changes addresses, not tiles)
-  if (kind == FUSED_R2C_PLANES || kind == FUSED_R2C_PLANES_B) {
-    *ta = (int)(dA.n == 512 ? R2CRows512ToRing::ntiles(dA) : R2CRows1024ToRing::ntiles(dA));
-    *tb = (int)Cols1024FromRing::ntiles(dB);
-    return 0;
-  }
-  if (kind == FUSED_COLS_C2R || kind == FUSED_COLS_C2R_B) {
-    *ta = (int)Cols1024ToRing::ntiles(dA);
-    if (dB.n == 1024) { *tb = (int)C2RRows1024FromRing::ntiles(dB); return 0; }
-    *tb = (int)C2RRows512FromRing::ntiles(dB);
-    return 0;
-  }
-  return -1;
-}
-
-hipError_t launch_fused2_real_f64(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev, const FusedDesc &f,
-                                  const void *in, void *ring, void *out, hipStream_t s) {
-  if (kind == FUSED_R2C_PLANES) {
-    if (dA.n == 512) return launch_fused2<R2CRows512ToRing, Cols1024FromRing>(dA, dB, dev, f, in, ring, out, s);
-    return launch_fused2<R2CRows1024ToRing, Cols1024FromRing>(dA, dB, dev, f, in, ring, out, s);
-  }
-  if (kind == FUSED_COLS_C2R) {
-    if (dB.n == 1024) return launch_fused2<Cols1024ToRing, C2RRows1024FromRing>(dA, dB, dev, f, in, ring, out, s);
-    return launch_fused2<Cols1024ToRing, C2RRows512FromRing>(dA, dB, dev, f, in, ring, out, s);
-  }
-  if (kind == FUSED_R2C_PLANES_B) {
-    if (dA.n == 512) return launch_fused2<R2CRows512ToRing, Cols1024FromRingB>(dA, dB, dev, f, in, ring, out, s);
-    return launch_fused2<R2CRows1024ToRing, Cols1024FromRingB>(dA, dB, dev, f, in, ring, out, s);
-  }
-  if (kind == FUSED_COLS_C2R_B) {
-    if (dB.n == 1024) return launch_fused2<Cols1024ToRingB, C2RRows1024FromRing>(dA, dB, dev, f, in, ring, out, s);
-    return launch_fused2<Cols1024ToRingB, C2RRows512FromRing>(dA, dB, dev, f, in, ring, out, s);
-  }
-  return hipErrorInvalidValue;
+  return nullptr;
 }
 
 }  // namespace gfft

@@ -259,35 +259,40 @@ enum FusedKind { FUSED_ROWS_COLS = 0, FUSED_COLS_ROWS = 1, FUSED_FOURSTEP = 2, F
                  // strided axis kept on the half-spectrum side -- [r2c rows -> strided, output in blocks] forward, [strided, input in
                  // blocks -> c2r rows] backward (fft_fused_real_f64.hip / _f32.hip)
                  FUSED_R2C_PLANES_B = 9, FUSED_COLS_C2R_B = 10 };
-inline bool fused_kind_real(int kind) {
-  return kind == FUSED_R2C_PLANES || kind == FUSED_COLS_C2R || kind == FUSED_R2C_PLANES_B || kind == FUSED_COLS_C2R_B;
-}
-// variant: 1 = the default kernels (32 values per thread, one exchange, one 512-thread workgroup per CU); 3 = the round-3
-// kernels (16 values per thread, two exchanges, 1024 threads); 2 / 4 = (make VARIANTS=1) 8 lines per tile, two workgroups per CU
+// one row per kind: what gfft_plan_pass_info and gfft_plan_describe call it, and whether it is one of the real kinds
+struct FusedKindInfo { const char *pass_name, *describe_name; bool real; };
+inline constexpr FusedKindInfo kFusedKinds[] = {
+  {"fused rows+cols", "rows -> strided", false},
+  {"fused cols+rows", "strided -> rows", false},
+  {"fused four-step", "four-step", false},
+  {"fused 2-D rows+cols", "2-D planes: rows -> strided", false},
+  {"fused four-step (rows)", "four-step: strided -> rows, transposed on store", false},
+  {"fused r2c-rows+cols", "r2c rows -> strided", true},
+  {"fused cols+c2r-rows", "strided -> c2r rows", true},
+  {"fused 2-D rows+cols(blocks)", "2-D planes: rows -> strided into blocks", false},
+  {"fused 2-D cols(blocks)+rows", "2-D planes: strided from blocks -> rows", false},
+  {"fused 2-D r2c-rows+cols(blocks)", "2-D planes: r2c rows -> strided into blocks", true},
+  {"fused 2-D cols(blocks)+c2r-rows", "2-D planes: strided from blocks -> c2r rows", true},
+};
+static_assert(sizeof kFusedKinds / sizeof kFusedKinds[0] == FUSED_COLS_C2R_B + 1, "one row per FusedKind");
+inline bool fused_kind_real(int kind) { return kFusedKinds[kind].real; }
 extern int g_fuse2_n512;           // option fuse2_n512: the n = 512 pairs (fft_fused_f64.hip)
 extern int g_fuse2_mixed;          // option fuse2_mixed: pairs on planes of 512 x 1024 / 1024 x 512 points (fft_fused_f64.hip)
 extern int g_fuse2_f32_n512;       // option fuse2_f32_n512: the complex64 n = 512 pairs (fft_fused_f32.hip)
 extern int g_fuse2_mixv;           // option fuse2_mixv: the 3-D pair on n = 960 / 896 (fft_fused_f64.hip)
 extern int g_c2r_2048;             // option c2r_2048: the c2r pair on rows of 2048 reals (fft_fused_real_f64.hip)
-bool fused2_supported_f64(int kind, int variant, int n_a, int n_b);
-int fused2_tiles_f64(int kind, int variant, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
-// dev_descs: {dA, dB} in device memory (uploaded when the plan was made; the scale factors travel as arguments)
-hipError_t launch_fused2_f64(int kind, int variant, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs,
-                             const FusedDesc &f, const void *in, void *ring, void *out, hipStream_t s);
-// ... complex64 (fft_fused_f32.hip; on by default: option fuse2_f32 = 1, 0 switches them off; measured, see there)
-bool fused2_supported_f32(int kind, int n_a, int n_b);
-int fused2_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
-hipError_t launch_fused2_f32(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f,
-                             const void *in, void *ring, void *out, hipStream_t s);
-// ... the real kinds (n_a / n_b: the passes' lengths -- COMPLEX length of the packed-real rows)
-bool fused2_real_supported_f64(int kind, int n_a, int n_b);
-int fused2_real_tiles_f64(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
-hipError_t launch_fused2_real_f64(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f,
-                                  const void *in, void *ring, void *out, hipStream_t s);
-bool fused2_real_supported_f32(int kind, int n_a, int n_b);
-int fused2_real_tiles_f32(int kind, const PassDesc &dA, const PassDesc &dB, int *tiles_a, int *tiles_b);
-hipError_t launch_fused2_real_f32(int kind, const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f,
-                                  const void *in, void *ring, void *out, hipStream_t s);
+// One kernel pair A -> B, resolved when the plan is made (fft_fused_impl.h fused_pair): the tile counts come from the two
+// PassCfgs that launch.  dev_descs: {dA, dB} in device memory (uploaded when the plan was made; the scale factors travel as arguments)
+struct FusedPair {
+  unsigned (*tiles_a)(const PassDesc &), (*tiles_b)(const PassDesc &);
+  hipError_t (*launch)(const PassDesc &dA, const PassDesc &dB, const PassDesc *dev_descs, const FusedDesc &f, const void *in,
+                       void *ring, void *out, hipStream_t s);
+};
+// The pair of (precision, kind, n_a, n_b) under the option globals above, as they stand when the plan is made; nullptr: no such
+// pair in this build / under these options.  n_a / n_b: the passes' lengths (COMPLEX length of packed-real rows).  fuse2_option:
+// the raw value of option fuse2 -- which kernel set it means is decided by the complex128 table (fft_fused_f64.hip).  The
+// complex64 pairs (fft_fused_f32.hip) are on by default: option fuse2_f32 = 1, 0 switches them off; measured, see there.
+const FusedPair *fused2_select(int precision, int kind, int fuse2_option, int n_a, int n_b);
 
 // packed-real row kernels (fft_real_*.hip): d.n = complex length = half the real length
 bool real_half_supported(int n_complex);

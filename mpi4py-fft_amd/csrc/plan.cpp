@@ -77,8 +77,8 @@ struct Options {
   int wtile = 1;             // tile-major workspace under the complex 3-D pair schedule (plan_fused3; A/B)
   int plane2d = 1;           // planes of 32^2 / 64^2 points: both passes in one launch, the plane in LDS (fft_plane2d.hip; 0: two passes, A/B)
   int fuse2 = 1;             // pass pairs in one persistent launch, handed over through the Infinity Cache (fft_fused_f64.hip)
-  int fuse2_ring = 0, fuse2_lag = 0;   // slots of the hand-off ring / planes the producer runs ahead; 0 = auto (make_fused2)
-  int fuse2_kinds = 2046;    // which pairs (bit = FusedKind): measured per kind, see make_fused2 (bits 1-10; 0, [rows -> strided] of the 3-D schedule, off)
+  int fuse2_ring = 0, fuse2_lag = 0;   // slots of the hand-off ring / planes the producer runs ahead; 0 = auto (fused2_ring)
+  int fuse2_kinds = 2046;    // which pairs (bit = FusedKind): measured per kind, see fused2_pair (bits 1-10; 0, [rows -> strided] of the 3-D schedule, off)
   int fuse2_f32 = 1;         // 1: complex64 pairs (fft_fused_f32.hip); 2: the real fp32 pairs too (fft_fused_real_f32.hip: measured level, off)
   int fuse2_wait_ms = 2000;  // wall-clock limit of one wait inside a fused launch before the launch is voided (0: at once -- test hook)
   int debug_tile_lg = 0, debug_tile_side = 0, debug_tile_stride = 0;   // gfft_debug_pass: tile-major lines (rows passes)
@@ -221,7 +221,8 @@ struct Pass {
   // fft_fused2_kernel); fused.ctr and the ring's address are filled in at execution
   PassDesc d2{};
   FusedDesc fused{};
-  int fused_kind = 0, fused_variant = 1;
+  int fused_kind = 0;
+  const FusedPair *pair = nullptr;   // the kernel pair, resolved when the plan was made (fused2_pair)
   PassDesc *dev_descs = nullptr;     // {d, d2} in device memory (owned by the plan: gfft_plan_s::device_allocs)
   // the same two passes as stand-alone launches (gfft_plan_s::alt[alt_first], [alt_first + 1]): what the plan runs
   // once a fused launch has given up a wait; alt_buf / alt_bytes = the scratch region only that form needs
@@ -451,6 +452,12 @@ AsyncErrors &async_errors() {
   static AsyncErrors a;
   return a;
 }
+// this plan runs its pairs as stand-alone passes from now on: grow the scratch regions that only that form needs
+void fused_pairs_off(gfft_plan_s *pl) {
+  pl->fused_off = true;
+  for (const Pass &p : pl->passes)
+    if (p.kind == PK_FUSED2 && p.alt_buf >= 0 && p.alt_bytes > pl->region_bytes[p.alt_buf]) pl->region_bytes[p.alt_buf] = p.alt_bytes;
+}
 // move what the kernels wrote since the last look into the plans (a.m held by the caller)
 void collect_async_errors(AsyncErrors &a) {
   if (!a.flag) return;
@@ -463,10 +470,8 @@ void collect_async_errors(AsyncErrors &a) {
     auto it = a.live.find(id);
     if (it == a.live.end()) { a.orphans.push_back(id); continue; }
     gfft_plan_s *pl = it->second;
-    pl->fused_off = true;
+    fused_pairs_off(pl);
     pl->voided = true;
-    for (const Pass &p : pl->passes)
-      if (p.kind == PK_FUSED2 && p.alt_buf >= 0 && p.alt_bytes > pl->region_bytes[p.alt_buf]) pl->region_bytes[p.alt_buf] = p.alt_bytes;
   }
 }
 int report_voided(unsigned id) {
@@ -525,6 +530,23 @@ void need(gfft_plan_s *pl, int buf, size_t bytes) {
   if (bytes > pl->region_bytes[buf]) pl->region_bytes[buf] = bytes;
 }
 
+// Row pitches of the scratch arrays (workspace, four-step intermediate, hand-off slots), in entries of esz bytes.
+// Rule 1: +256 B when the pitch would be a multiple of 2 KiB (rows a power of two apart alias the memory channels).
+int64_t pitch_off_2k(int64_t P, int64_t esz) { return (P * esz) % 2048 == 0 ? P + 256 / esz : P; }
+// Rule 2, for rows of whole 128-byte lines (P a multiple of 128 / esz, and it stays one): off the multiples of 2 KiB
+// ... and never 129 x 2^k entries: the far stride of the workspace is a power of two times P, and with P = 129 x 2^k
+// the rows a far-axis tile walks lie k (2^7 + 1) 2^j bytes apart -- the one multiplier found so far that the address
+// hash of the memory channels folds onto itself (row k and row k + 2^7 j share their channel).  Measured (round 5,
+// tools/ab_combo_probe.py ws_plane_skew, profiles/r05_ab_pitch129.txt), far-axis pass alone, same arrays:
+// (1024,1024,2048) r2c f64 [1025-wide rows, P = 1032] 11.6 -> 7.2 ms; (512,1024,2048) c128 [P = 2064] 14.0 -> 6.4 ms;
+// (2048,512,2048) r2c f64 18.0 -> 7.8 ms; (1024,1024,4096) r2c f32 [2049-wide, P = 2064] 14.0 -> 8.5 ms; pitches of
+// 17 / 33 / 65 / 257 x 2^k entries (every other BASELINE-sized shape) are level with or without a skew.
+int64_t pitch_off_129(int64_t P, int64_t esz) {
+  auto odd = [](int64_t x) { while (x && !(x & 1)) x >>= 1; return x; };
+  while (odd(P) == 129 || (P * esz) % 2048 == 0) P += 128 / esz;
+  return P;
+}
+
 // Slots of the hand-off ring and planes the producer runs ahead (options fuse2_ring / fuse2_lag, else automatic); false:
 // this launch has too few planes for a ring on which the pair pays.
 // How far the producer runs ahead is a matter of BYTES, not planes: ~96 MiB of lead, twice that of ring (the Infinity
@@ -532,6 +554,11 @@ void need(gfft_plan_s *pl, int buf, size_t bytes) {
 // planes of 8 MiB (complex64: with 6 / 12 the pair LOSES, 21.1 -> 21.9 ms per 1024^3 step, with 12 / 24 it gains, ->
 // 18.9 ms; profiles/r04_ab_fuse2_f32.txt), 24 / 48 planes of 4 MiB (complex128 n = 512: 16 / 32 +11 %, 24 / 48 -11 %).
 bool fused2_ring(int precision, int n_a, int n_b, int64_t slot_bytes, int planes, int *ring_out, int *lag_out) {
+  // auto: 12 slots with the producer 6 planes ahead where there are planes enough, else 8 / 4.  Swept on one box, plans
+  // alternating on the same arrays (tools/fused2_ring_sweep.py, profiles/r03_fused2_ring_sweep_final.txt): 1024^3
+  // complex128 per step 34.3 (8 / 4) -> 32.4 (12 / 6), 32.2 (14 / 7), 31.8 (13 / 6, 11 / 6); lag 3 or ring 6: 37.9;
+  // C2 0.748 -> 0.710 ms (16 / 8: 0.70).  (Before the row tiles lost their barriers 8 / 4 was the optimum: a
+  // faster consumer wants the producer further ahead.)
   int ring = opts().fuse2_ring, lag = opts().fuse2_lag;
   if (ring <= 0) {
     int64_t ahead = (((int64_t)96 << 20) + slot_bytes - 1) / (slot_bytes > 0 ? slot_bytes : 1);
@@ -551,8 +578,7 @@ bool fused2_ring(int precision, int n_a, int n_b, int64_t slot_bytes, int planes
   return true;
 }
 
-// The hand-off protocol of the fused pairs leans on gfx94x / gfx950 specifics (make_fused2): elsewhere the pairs stay off, and
-// plan_fused3 asks BEFORE it lays the workspace out for a pair it would not get.
+// The hand-off protocol of the fused pairs leans on gfx94x / gfx950 specifics (fused2_pair): elsewhere the pairs stay off.
 bool fused2_arch_ok() {
   static int arch_ok[kMaxDevices] = {};          // 0 unknown, 1 yes, -1 no
   const int dev = current_device();
@@ -568,44 +594,43 @@ bool fused2_arch_ok() {
   return arch_ok[dev] > 0;
 }
 
-bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const PassDesc &dA, const PassDesc &dB, int planes,
-                 int64_t a_in_plane, int64_t b_out_plane, int64_t slot_bytes, Pass *out) {
-  // auto: 12 slots with the producer 6 planes ahead where there are planes enough, else 8 / 4.  Swept on one box, plans
-  // alternating on the same arrays (tools/fused2_ring_sweep.py, profiles/r03_fused2_ring_sweep_final.txt): 1024^3
-  // complex128 per step 34.3 (8 / 4) -> 32.4 (12 / 6), 32.2 (14 / 7), 31.8 (13 / 6, 11 / 6); lag 3 or ring 6: 37.9;
-  // C2 0.748 -> 0.710 ms (16 / 8: 0.70).  (Before the row tiles lost their barriers 8 / 4 was the optimum: a
-  // faster consumer wants the producer further ahead.)
+// Whether a kernel pair exists for (precision, kind, n_a, n_b) on `planes` planes of slot_bytes each, and its ring: everything
+// that can be known without the descriptors.  make_fused2 starts from it, and plan_fused3 asks it BEFORE it lays the workspace
+// out for a pair.  pair == nullptr: no pair.
+struct PairChoice {
+  const FusedPair *pair = nullptr;
+  int ring = 0, lag = 0;
+};
+PairChoice fused2_pair(int precision, int kind, int n_a, int n_b, int64_t slot_bytes, int planes) {
   // The hand-off protocol leans on gfx94x / gfx950 specifics: raw-buffer cache policy sc0 | sc1 = system scope (written
   // through / never served from a stale L2 line), stores counted by vmcnt -- so that s_waitcnt(0) means "write-through
   // acknowledged" --, relaxed agent-scope atomics as the only ordering.  On a target with another memory model (a
   // separate store counter, other policy bits) the pairs stay off: the stand-alone passes are always correct.
-  if (!fused2_arch_ok()) return false;
-  int ring = 0, lag = 0;
-  if (!fused2_ring(pl->precision, dA.n, dB.n, slot_bytes, planes, &ring, &lag)) return false;
-  if (!opts().fuse2 || !((opts().fuse2_kinds >> kind) & 1)) return false;
-#ifdef GFFT_VARIANTS      // (make VARIANTS=1: the 8-lines-per-tile kernel sets, option fuse2 = 2 / 4 -- measured a quarter slower, fft_fused_f64.hip)
-  int variant = (opts().fuse2 == 2 || opts().fuse2 == 4) ? opts().fuse2 : 1;
-#else
-  int variant = 1;
-#endif
-  if (variant == 1 && gfft::g_fuse2_n512 == 2 && pl->precision == GFFT_F64 && dA.n == 512 && dB.n == 512 && (kind == FUSED_COLS_ROWS || kind == FUSED_PLANES_CR_B))
-    variant = 5;
+  PairChoice c;
+  if (!fused2_arch_ok()) return c;
+  if (!opts().fuse2 || !((opts().fuse2_kinds >> kind) & 1)) return c;
   // (complex64 pairs are on by default since round 4 -- option fuse2_f32 = 1, profiles/r04_ab_fuse2_f32.txt; the real fp32
-  // pairs measured level with their stand-alone passes and need fuse2_f32 = 2)
-  const bool real_kind = fused_kind_real(kind);
-  const bool f32 = pl->precision == GFFT_F32;
-  if (f32 && (!opts().fuse2_f32 || (real_kind && opts().fuse2_f32 < 2))) return false;
-  if (f32 ? (real_kind ? !fused2_real_supported_f32(kind, dA.n, dB.n) : !fused2_supported_f32(kind, dA.n, dB.n))
-          : (real_kind ? !fused2_real_supported_f64(kind, dA.n, dB.n) : !fused2_supported_f64(kind, variant, dA.n, dB.n))) return false;
-  int ta = 0, tb = 0;
-  if ((f32 ? (real_kind ? fused2_real_tiles_f32(kind, dA, dB, &ta, &tb) : fused2_tiles_f32(kind, dA, dB, &ta, &tb))
-           : (real_kind ? fused2_real_tiles_f64(kind, dA, dB, &ta, &tb) : fused2_tiles_f64(kind, variant, dA, dB, &ta, &tb))) || ta < 1 || tb < 1) return false;
+  // pairs measured level to slightly slower than their stand-alone passes -- 1024^3 r2c f32 per step 11.53 ms unfused, 11.58
+  // with both pairs, 11.78 with the r2c pair alone, 11.42 with the c2r pair alone, profiles/r04_real_pairs_f32.txt -- and
+  // need fuse2_f32 = 2)
+  if (precision == GFFT_F32 && (!opts().fuse2_f32 || (fused_kind_real(kind) && opts().fuse2_f32 < 2))) return c;
+  if (!fused2_ring(precision, n_a, n_b, slot_bytes, planes, &c.ring, &c.lag)) return c;
+  c.pair = fused2_select(precision, kind, opts().fuse2, n_a, n_b);
+  return c;
+}
+
+bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const PassDesc &dA, const PassDesc &dB, int planes,
+                 int64_t a_in_plane, int64_t b_out_plane, int64_t slot_bytes, Pass *out) {
+  const PairChoice c = fused2_pair(pl->precision, kind, dA.n, dB.n, slot_bytes, planes);
+  if (!c.pair) return false;
+  const int ta = (int)c.pair->tiles_a(dA), tb = (int)c.pair->tiles_b(dB);
+  if (ta < 1 || tb < 1) return false;
   // (hand-off accesses carry 32-bit byte offsets inside a slot; tickets are 32-bit)
   if (slot_bytes >= ((int64_t)1 << 31) || (double)planes * (ta + tb) >= 1.0e9) return false;     // (tickets < 2^30: a launch that gives up pushes the counter 2^31 on)
   Pass f = a;
   f.kind = PK_FUSED2;
   f.fused_kind = kind;
-  f.fused_variant = variant;
+  f.pair = c.pair;
   f.d = dA;
   f.d2 = dB;
   f.src = a.src;
@@ -614,8 +639,8 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
   f.fused.planes = planes;
   f.fused.tiles_a = ta;
   f.fused.tiles_b = tb;
-  f.fused.ring = ring;
-  f.fused.lag = lag;
+  f.fused.ring = c.ring;
+  f.fused.lag = c.lag;
   f.fused.defer = 0;      // an A tile's counter is settled at the end of the tile (1 / 2: behind the next tile's loads / the next ticket's poll -- measured, not kept)
   f.fused.group = 1;      // one tile per ticket (groups of 2 / 4 measured level to slower, profiles/r03_ab_fuse2_group.txt)
   f.fused.a_in_plane = a_in_plane;
@@ -626,9 +651,6 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
   f.fused.plan_id = pl->id;
   f.fused.host_flag = nullptr;
   f.fused.debug = 0;
-  f.alt_first = (int)pl->alt.size();
-  pl->alt.push_back(a);
-  pl->alt.push_back(b);
   for (const Pass *q : {&a, &b})
     for (int side : {q->src, q->dst})
       if (side >= BUF_WS && side != BUF_RING) f.alt_buf = side;     // (at most one scratch region: WS of the 3-D schedule, FS of a four-step pair)
@@ -637,7 +659,6 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
 #ifdef GFFT_FUSE2_TRACE
   ctr_bytes += 256 + (size_t)1024 * 96 * 16 * sizeof(unsigned long long);       // (fft_pow2_impl.h, GFFT_TRACE_STAMP)
 #endif
-  need(pl, BUF_RING, (size_t)ring * (size_t)f.fused.slot_bytes + ctr_bytes);
   // the kernel reads the two descriptors from device memory (the scale factors travel as kernel arguments)
   const PassDesc both[2] = {f.d, f.d2};
   void *dev = nullptr;
@@ -645,6 +666,11 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
   if (hipMemcpy(dev, both, sizeof both, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); return false; }
   pl->device_allocs.push_back(dev);
   f.dev_descs = static_cast<PassDesc *>(dev);
+  // (nothing of the plan is touched before the pair is certain)
+  need(pl, BUF_RING, (size_t)c.ring * (size_t)f.fused.slot_bytes + ctr_bytes);
+  f.alt_first = (int)pl->alt.size();
+  pl->alt.push_back(a);
+  pl->alt.push_back(b);
   *out = f;
   return true;
 }
@@ -708,8 +734,7 @@ int plan_fourstep(gfft_plan_s *pl, const Line &L, int64_t n1, int64_t n2) {
   if (rc) return rc;
   // The intermediate tmp[o][i2][k1][i] lives in the FS region with its i2-stride S2 padded off
   // the power of two (same channel-aliasing argument as the 3-D workspace).
-  int64_t S2 = n1 * inner;
-  if ((S2 * esz) % 2048 == 0) S2 += 256 / esz;
+  const int64_t S2 = pitch_off_2k(n1 * inner, esz);
   Pass a, b;
   // step 1: length-n1 transforms over i1 (stride n2*inner) for every (o, i2, i); the store
   // applies W_n^(i2*k1) and writes transposed-within-row
@@ -757,8 +782,7 @@ int plan_fourstep(gfft_plan_s *pl, const Line &L, int64_t n1, int64_t n2) {
     {
       // FUSED_FOURSTEP_ROWS: the intermediate the other way round, tmp[k1][i2] (rows of n2 entries, pitch S1): the
       // first pass stores its 16 columns i2 .. i2 + 15 side by side where they are, the second reads rows
-      int64_t S1 = n2;
-      if ((S1 * esz) % 2048 == 0) S1 += 256 / esz;
+      const int64_t S1 = pitch_off_2k(n2, esz);
       PassDesc dA = a.d, dB = b.d;
       dA.batch = n2;
       dA.out_os = n1 * S1;  dA.out_ms = 1;  dA.out_is = 1;  dA.out_es = S1;
@@ -1262,6 +1286,21 @@ bool fused3_applicable(const gfft_plan_s *pl) {
   return bytes >= opts().fused3_min_bytes;
 }
 
+// algorithmic bytes of one pass of the 3-D schedule: one read + one write of its lines (nc_full: complex entries of a
+// transformed row); strided passes tile the line-rounded width, the model counts the data columns
+static double fused3_pass_bytes(const Pass &p, int prec, int64_t nc_full) {
+  const double esz = 2.0 * prec;
+  const bool half = p.d.mode == MODE_R2C_H || p.d.mode == MODE_C2R_H;
+  const double lines = p.data_inner ? (double)p.d.batch / (double)p.d.inner * (double)p.data_inner : (double)p.d.batch;
+  const double n = half ? 2.0 * p.d.n : p.d.n;          // logical length of the line
+  const bool r2c = p.d.mode == MODE_R2C || p.d.mode == MODE_R2C_H, c2r = p.d.mode == MODE_C2R || p.d.mode == MODE_C2R_H;
+  const double ein = r2c ? prec : esz, eout = c2r ? prec : esz;
+  double nin = c2r ? (double)nc_full : n, nout = r2c ? (double)nc_full : n;
+  if (p.d.tr_dir == 1) nout = p.d.tr_n;
+  if (p.d.tr_dir == 2) nin = p.d.tr_n;
+  return lines * (nin * ein + nout * eout);
+}
+
 int plan_fused3(gfft_plan_s *pl) {
   const int prec = pl->precision;
   const bool real = pl->kind == GFFT_R2C || pl->kind == GFFT_C2R;
@@ -1281,26 +1320,14 @@ int plan_fused3(gfft_plan_s *pl) {
     p.d.tr_even = (kept % 2 == 0) ? 1 : 0;
   };
   const int64_t esz = 2 * prec;
-  // workspace row pitch: rows start on 128-B lines; +256 B when the pitch would be a multiple of 2 KiB
   const int64_t seg = 128 / esz;      // (R4: rows in whole 256-byte pieces instead measured +1 % on the real fp64 schedule: more padding columns, nothing gained)
-  int64_t P = (nc + seg - 1) / seg * seg;
-  if ((P * esz) % 2048 == 0) P += 256 / esz;
-  // ... and never 129 x 2^k entries: the far stride of the workspace is a power of two times P, and with P = 129 x 2^k
-  // the rows a far-axis tile walks lie k (2^7 + 1) 2^j bytes apart -- the one multiplier found so far that the address
-  // hash of the memory channels folds onto itself (row k and row k + 2^7 j share their channel).  Measured (round 5,
-  // tools/ab_combo_probe.py ws_plane_skew, profiles/r05_ab_pitch129.txt), far-axis pass alone, same arrays:
-  // (1024,1024,2048) r2c f64 [1025-wide rows, P = 1032] 11.6 -> 7.2 ms; (512,1024,2048) c128 [P = 2064] 14.0 -> 6.4 ms;
-  // (2048,512,2048) r2c f64 18.0 -> 7.8 ms; (1024,1024,4096) r2c f32 [2049-wide, P = 2064] 14.0 -> 8.5 ms; pitches of
-  // 17 / 33 / 65 / 257 x 2^k entries (every other BASELINE-sized shape) are level with or without a skew.
-  {
-    auto odd = [](int64_t x) { while (x && !(x & 1)) x >>= 1; return x; };
-    while (odd(P) == 129 || (P * esz) % 2048 == 0) P += seg;
-  }
-  need(pl, BUF_WS, (size_t)(n0 * n1 * P * esz));
-  pl->ws_pitch = P;
   // columns the in-workspace passes run over: nc rounded up to whole 128-byte lines (the padding
   // columns hold zeros written by the pass that fills W), see PassDesc::inner_ld / inner_st
   const int64_t Pu = (nc + seg - 1) / seg * seg;
+  // workspace row pitch: rows start on 128-B lines, under both pitch rules
+  const int64_t P = pitch_off_129(pitch_off_2k(Pu, esz), esz);
+  need(pl, BUF_WS, (size_t)(n0 * n1 * P * esz));
+  pl->ws_pitch = P;
 
   auto base = [&](int n, int mode) {
     Pass p;
@@ -1430,24 +1457,12 @@ int plan_fused3(gfft_plan_s *pl) {
   // then [axis 0 -> rows] plane by plane: the fused pair then WRITES the caller's rows scattered (plane i1 =
   // rows 16 MiB apart), which costs nothing, where the mirror pair [rows -> axis 0] READS them scattered and
   // loses what the fusion gains (1024^3 c128, tools/fused2_probe.py: 20.0 ms against 18.4 ms).
-  int ring_probe = 0, lag_probe = 0;
-  const bool pair_cols_rows = !real && !tr && !flat_out && Pu == nc && opts().fuse2 && fused2_arch_ok() &&
-                              ((opts().fuse2_kinds >> FUSED_COLS_ROWS) & 1) && fused2_ring(prec, (int)n0, (int)n2, n0 * P * esz, (int)n1, &ring_probe, &lag_probe) &&
-                              (prec == GFFT_F64 ? fused2_supported_f64(FUSED_COLS_ROWS, 1, (int)n0, (int)n2)
-                                                : (opts().fuse2_f32 && fused2_supported_f32(FUSED_COLS_ROWS, (int)n0, (int)n2)));
+  const bool pair_cols_rows = !real && !tr && !flat_out && Pu == nc && fused2_pair(prec, FUSED_COLS_ROWS, (int)n0, (int)n2, n0 * P * esz, (int)n1).pair;
   // Real transforms: forward [r2c rows -> axis 1] on the contiguous planes i0 of the flat_out schedule (FUSED_R2C_PLANES),
   // backward [axis 0 -> c2r rows] on the planes i1 (FUSED_COLS_C2R), as the complex schedule runs its last two passes
-  auto real_ok = [&](int kind, int na, int nb) {
-    // (real fp32 pairs: built and measured level to slightly slower than their stand-alone passes -- 1024^3 r2c f32 per step
-    // 11.53 ms unfused, 11.58 with both pairs, 11.78 with the r2c pair alone, 11.42 with the c2r pair alone,
-    // profiles/r04_real_pairs_f32.txt -- so they need option fuse2_f32 = 2)
-    return prec == GFFT_F64 ? fused2_real_supported_f64(kind, na, nb) : (opts().fuse2_f32 >= 2 && fused2_real_supported_f32(kind, na, nb));
-  };
-  const bool pair_real = real && !tr && opts().fuse2 && fused2_arch_ok() && n2 % 2 == 0 &&
-                         (inverse ? (((opts().fuse2_kinds >> FUSED_COLS_C2R) & 1) && real_ok(FUSED_COLS_C2R, (int)n0, (int)(n2 / 2)) &&
-                                     fused2_ring(prec, (int)n0, (int)(n2 / 2), n0 * P * esz, (int)n1, &ring_probe, &lag_probe))
-                                  : (((opts().fuse2_kinds >> FUSED_R2C_PLANES) & 1) && flat_out && real_ok(FUSED_R2C_PLANES, (int)(n2 / 2), (int)n1) &&
-                                     fused2_ring(prec, (int)(n2 / 2), (int)n1, n1 * P * esz, (int)n0, &ring_probe, &lag_probe)));
+  const bool pair_real = real && !tr && n2 % 2 == 0 &&
+                         (inverse ? fused2_pair(prec, FUSED_COLS_C2R, (int)n0, (int)(n2 / 2), n0 * P * esz, (int)n1).pair != nullptr
+                                  : flat_out && fused2_pair(prec, FUSED_R2C_PLANES, (int)(n2 / 2), (int)n1, n1 * P * esz, (int)n0).pair);
   if (pair_real && inverse) { w_i0 = n1 * P; w_i1 = P; }     // (as under the complex pair, below)
   const bool cols_first = !inverse && pair_cols_rows;
   // ... and the workspace then is W[i0][k1][c]: the stand-alone axis-1 pass stores on NEAR strides (stores are
@@ -1494,29 +1509,29 @@ int plan_fused3(gfft_plan_s *pl) {
     // (strided passes tile the line-rounded width Pu; the work model counts the nc data columns)
     const double lines = p.data_inner ? (double)p.d.batch / (double)p.d.inner * (double)p.data_inner : (double)p.d.batch;
     const double n = half ? 2.0 * p.d.n : p.d.n;          // logical length of the line
-    const bool r2c = p.d.mode == MODE_R2C || p.d.mode == MODE_R2C_H, c2r = p.d.mode == MODE_C2R || p.d.mode == MODE_C2R_H;
     pl->flops += (p.d.mode == MODE_C2C ? 1.0 : 0.5) * 5.0 * n * std::log2(n) * lines;
-    const double ein = r2c ? prec : esz, eout = c2r ? prec : esz;
-    double nin = c2r ? (double)nc_full : n, nout = r2c ? (double)nc_full : n;
-    if (p.d.tr_dir == 1) nout = p.d.tr_n;
-    if (p.d.tr_dir == 2) nin = p.d.tr_n;
-    pl->bytes += lines * (nin * ein + nout * eout);
+    pl->bytes += fused3_pass_bytes(p, prec, nc_full);
     pl->passes.push_back(p);
   }
+  // passes[i], passes[i + 1] as one launch where the pair exists: dA / dB = the two passes on one plane (make_fused2)
+  auto fuse = [&](size_t i, int kind, const PassDesc &dA, const PassDesc &dB, int64_t planes, int64_t a_in_plane, int64_t b_out_plane, int64_t slot_bytes) {
+    Pass f;
+    if (!make_fused2(pl, kind, pl->passes[i], pl->passes[i + 1], dA, dB, (int)planes, a_in_plane, b_out_plane, slot_bytes, &f)) return;
+    f.bytes2 = fused3_pass_bytes(pl->passes[i], prec, nc_full) + fused3_pass_bytes(pl->passes[i + 1], prec, nc_full);
+    pl->passes[i] = f;
+    pl->passes.erase(pl->passes.begin() + i + 1);
+  };
   // Complex schedules: [rows along axis 2] + [axis 0 inside the workspace] -- passes 1 + 2 forward, 2 + 3
   // backward -- as ONE persistent launch per direction, plane by plane (a plane = one i1: n0 rows of n2
   // entries), the plane handed over through the Infinity Cache instead of W (FUSED_ROWS_COLS / _COLS_ROWS).
   if (!real && !tr && !flat_out && Pu == nc && pl->passes.size() >= 3) {
     const size_t base = pl->passes.size() - 3;
-    Pass &p1 = pl->passes[base], &p2 = pl->passes[base + 1], &p3 = pl->passes[base + 2];
-    Pass f;
-    bool ok = false;
+    const Pass &p1 = pl->passes[base], &p2 = pl->passes[base + 1], &p3 = pl->passes[base + 2];
     if (!inverse && !cols_first) {
       PassDesc dA = p1.d, dB = p2.d;                  // rows IN -> slot[i0][c];  axis 0: slot -> W[i1][k0][c]
       dA.batch = n0; dA.inner = 1; dA.in_is = 0; dA.out_is = 0; dA.out_os = P;
       dB.batch = Pu; dB.in_os = 0; dB.out_os = 0; dB.in_es = P;
-      ok = make_fused2(pl, FUSED_ROWS_COLS, p1, p2, dA, dB, (int)n1, n2 * esz, w_i1 * esz, n0 * P * esz, &f);
-      if (ok) { f.bytes2 = 1; pl->passes[base] = f; pl->passes.erase(pl->passes.begin() + base + 1); }
+      fuse(base, FUSED_ROWS_COLS, dA, dB, n1, n2 * esz, w_i1 * esz, n0 * P * esz);
     } else {
       PassDesc dA = p2.d, dB = p3.d;                  // axis 0: W[i1][k0][c] -> slot[i0][c];  rows slot -> OUT
       dA.batch = Pu; dA.in_os = 0; dA.out_os = 0; dA.out_es = P;
@@ -1530,44 +1545,26 @@ int plan_fused3(gfft_plan_s *pl) {
         dB.in_tlg = 0; dB.in_tS = 0;                   // (B reads the slot, natural rows)
         a_plane = TWc * esz;                           // plane k1 = one row of every tile
       }
-      ok = make_fused2(pl, FUSED_COLS_ROWS, p2, p3, dA, dB, (int)n1, a_plane, n2 * esz, n0 * P * esz, &f);
-      if (ok) { f.bytes2 = 1; pl->passes[base + 1] = f; pl->passes.erase(pl->passes.begin() + base + 2); }
+      fuse(base + 1, FUSED_COLS_ROWS, dA, dB, n1, a_plane, n2 * esz, n0 * P * esz);
     }
   }
   if (pair_real && pl->passes.size() >= 3) {
     const size_t base = pl->passes.size() - 3;
-    // algorithmic bytes of a pass, as the loop above counts them
-    auto alg = [&](const Pass &p) {
-      const bool half = p.d.mode == MODE_R2C_H || p.d.mode == MODE_C2R_H;
-      const double lines = p.data_inner ? (double)p.d.batch / (double)p.d.inner * (double)p.data_inner : (double)p.d.batch;
-      const double n = half ? 2.0 * p.d.n : p.d.n;
-      const bool r2c = p.d.mode == MODE_R2C || p.d.mode == MODE_R2C_H, c2r = p.d.mode == MODE_C2R || p.d.mode == MODE_C2R_H;
-      return lines * ((c2r ? (double)nc_full : n) * (r2c ? prec : esz) + (r2c ? (double)nc_full : n) * (c2r ? prec : esz));
-    };
-    Pass f;
     if (!inverse) {
-      Pass &p1 = pl->passes[base], &p2 = pl->passes[base + 1];
+      const Pass &p1 = pl->passes[base], &p2 = pl->passes[base + 1];
       if (p1.d.mode == MODE_R2C_H && p2.cols) {
         PassDesc dA = p1.d, dB = p2.d;                // r2c rows of plane i0: IN -> slot[i1][c];  axis 1: slot -> W[i0][k1][c]
         dA.batch = n1; dA.inner = 1; dA.in_os = n2 / 2; dA.in_is = 0; dA.out_os = P; dA.out_is = 0;
         dB.batch = Pu; dB.in_os = 0; dB.out_os = 0; dB.in_es = P;
-        if (make_fused2(pl, FUSED_R2C_PLANES, p1, p2, dA, dB, (int)n0, n1 * n2 * prec, w_i0 * esz, n1 * P * esz, &f)) {
-          f.bytes2 = alg(p1) + alg(p2);
-          pl->passes[base] = f;
-          pl->passes.erase(pl->passes.begin() + base + 1);
-        }
+        fuse(base, FUSED_R2C_PLANES, dA, dB, n0, n1 * n2 * prec, w_i0 * esz, n1 * P * esz);
       }
     } else {
-      Pass &p2 = pl->passes[base + 1], &p3 = pl->passes[base + 2];
+      const Pass &p2 = pl->passes[base + 1], &p3 = pl->passes[base + 2];
       if (p3.d.mode == MODE_C2R_H && p2.cols) {
         PassDesc dA = p2.d, dB = p3.d;                // axis 0 of plane i1: W -> slot[i0][c];  c2r rows: slot -> OUT
         dA.batch = Pu; dA.in_os = 0; dA.out_os = 0; dA.out_es = P;
         dB.batch = n0; dB.inner = 1; dB.in_is = 0; dB.out_is = 0; dB.in_os = P; dB.out_os = n1 * n2 / 2;
-        if (make_fused2(pl, FUSED_COLS_C2R, p2, p3, dA, dB, (int)n1, w_i1 * esz, n2 * prec, n0 * P * esz, &f)) {
-          f.bytes2 = alg(p2) + alg(p3);
-          pl->passes[base + 1] = f;
-          pl->passes.erase(pl->passes.begin() + base + 2);
-        }
+        fuse(base + 1, FUSED_COLS_C2R, dA, dB, n1, w_i1 * esz, n2 * prec, n0 * P * esz);
       }
     }
   }
@@ -1746,8 +1743,7 @@ static int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, con
   // ... and as ONE persistent launch, plane by plane through the Infinity Cache: slot[row of the plane][P]
   bool fused = false;
   if (np < ((int64_t)1 << 30)) {
-    int64_t P = n2;                                       // slot rows pitched off the power of two
-    if ((P * esz) % 2048 == 0) P += 256 / esz;
+    const int64_t P = pitch_off_2k(n2, esz);              // slot rows pitched off the power of two
     PassDesc dA, dB;
     Pass f;
     if (!cols_first) {
@@ -1781,13 +1777,9 @@ static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np
   const int64_t esz = 2 * (int64_t)prec, m = n2 / 2, H = m + 1, per = n1 / nb;
   auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
   // the hand-off slot (and the workspace of the stand-alone backward form): rows of H entries rounded up to whole 128-byte
-  // lines, pitched off multiples of 2 KiB and off 129 x 2^k entries (plan_fused3)
+  // lines, pitched off multiples of 2 KiB and off 129 x 2^k entries (pitch_off_129)
   const int64_t seg = 128 / esz, Pu = (H + seg - 1) / seg * seg;
-  int64_t P = Pu;
-  {
-    auto odd = [](int64_t x) { while (x && !(x & 1)) x >>= 1; return x; };
-    while (odd(P) == 129 || (P * esz) % 2048 == 0) P += seg;
-  }
+  const int64_t P = pitch_off_129(Pu, esz);
   // rows: packed-real, complex length m, the real side in pairs
   Pass pr;
   pr.regk = true;
@@ -2207,11 +2199,7 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
       if (ae.word())
         for (int i = 0; i < AsyncErrors::SLOTS && pl->async_slot < 0; ++i)
           if (!ae.owner[i]) { ae.owner[i] = pl; pl->async_slot = i; }
-      if (pl->async_slot < 0) {
-        pl->fused_off = true;
-        for (const Pass &q : pl->passes)
-          if (q.kind == PK_FUSED2 && q.alt_buf >= 0 && q.alt_bytes > pl->region_bytes[q.alt_buf]) pl->region_bytes[q.alt_buf] = q.alt_bytes;
-      }
+      if (pl->async_slot < 0) fused_pairs_off(pl);
     }
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2280,14 +2268,7 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
       }
       static const int debug = getenv("GFFT_FUSE2_DEBUG") ? atoi(getenv("GFFT_FUSE2_DEBUG")) : 0;
       if (debug) { f.wait_ticks = 100000u; f.host_flag = nullptr; f.debug = (unsigned)debug; }      // (1 ms; counters printed below)
-      if (pl->precision == GFFT_F32 && fused_kind_real(p.fused_kind))
-        HIP_TRY(launch_fused2_real_f32(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
-      else if (pl->precision == GFFT_F32)
-        HIP_TRY(launch_fused2_f32(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
-      else if (fused_kind_real(p.fused_kind))
-        HIP_TRY(launch_fused2_real_f64(p.fused_kind, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
-      else
-        HIP_TRY(launch_fused2_f64(p.fused_kind, p.fused_variant, d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
+      HIP_TRY(p.pair->launch(d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
       if (debug) {      // developer aid: the launch's counters (tickets drawn, waits given up, tiles per plane)
         HIP_TRY(hipStreamSynchronize(s));
         std::vector<unsigned> h(16 + 2 * (size_t)f.planes);
@@ -2345,10 +2326,7 @@ int gfft_plan_pass_info(gfft_plan pl, int i, char *buf, size_t len, double *byte
   static const char *kinds[] = {"", "embed", "mul-B", "extract"};
   if (p.kind == PK_FUSED2) {
     // two axis passes in one launch: the algorithmic bytes of both (one read + one write of the array each)
-    static const char *fk[] = {"fused rows+cols", "fused cols+rows", "fused four-step", "fused 2-D rows+cols", "fused four-step (rows)",
-                               "fused r2c-rows+cols", "fused cols+c2r-rows", "fused 2-D rows+cols(blocks)", "fused 2-D cols(blocks)+rows",
-                               "fused 2-D r2c-rows+cols(blocks)", "fused 2-D cols(blocks)+c2r-rows"};
-    snprintf(buf, len, "%s n=%dx%d", fk[p.fused_kind], p.d.n, p.d2.n);
+    snprintf(buf, len, "%s n=%dx%d", kFusedKinds[p.fused_kind].pass_name, p.d.n, p.d2.n);
     if (bytes) *bytes = p.bytes2 > 1 ? p.bytes2 : (double)p.fused.planes * 2.0 * pl->precision *
                         ((double)p.d.batch * 2.0 * p.d.n + (double)p.d2.batch * 2.0 * p.d2.n);
     return GFFT_OK;
@@ -2822,15 +2800,13 @@ int gfft_plan_describe(gfft_plan pl, char *buf, size_t len) {
   static const char *bufn[] = {"IN", "OUT", "WS", "FS", "AUX", "RING", "FS2"};
   for (const Pass &p : pl->passes) {
     if (p.kind == PK_FUSED2) {
-      static const char *fk[] = {"rows -> strided", "strided -> rows", "four-step", "2-D planes: rows -> strided", "four-step: strided -> rows, transposed on store",
-                                 "r2c rows -> strided", "strided -> c2r rows", "2-D planes: rows -> strided into blocks", "2-D planes: strided from blocks -> rows",
-                                 "2-D planes: r2c rows -> strided into blocks", "2-D planes: strided from blocks -> c2r rows"};
+      const char *fk = kFusedKinds[p.fused_kind].describe_name;
       if (pl->fused_off)
         snprintf(line, sizeof line, "  pair (%s) n=%d then n=%d as two stand-alone passes (a fused launch gave up a wait)%s  %s -> %s\n",
-                 fk[p.fused_kind], p.d.n, p.d2.n, p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
+                 fk, p.d.n, p.d2.n, p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
       else
       snprintf(line, sizeof line, "  fused pair (%s) n=%d then n=%d: %d planes, %d + %d tiles per plane, ring of %d slots x %lld KiB, one persistent launch%s  %s -> %s\n",
-               fk[p.fused_kind], p.d.n, p.d2.n, p.fused.planes, p.fused.tiles_a, p.fused.tiles_b, p.fused.ring,
+               fk, p.d.n, p.d2.n, p.fused.planes, p.fused.tiles_a, p.fused.tiles_b, p.fused.ring,
                (long long)(p.fused.slot_bytes >> 10), p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
       s += line;
       continue;

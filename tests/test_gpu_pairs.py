@@ -41,6 +41,10 @@ def test_guru2_plans_against_numpy(dt, n, planes, blocks, pitch, launches, order
     """Both directions of a batched 2-D plan whose strided axis is cut into `blocks` blocks on the buffer side, the
     buffer's planes `pitch` elements further apart than their data: forward natural -> buffer, backward buffer ->
     natural, against numpy's fft2 on the same planes."""
+    _guru2_against_numpy(dt, n, planes, blocks, pitch, launches, order)
+
+
+def _guru2_against_numpy(dt, n, planes, blocks, pitch, launches, order, tiles=None):
     import torch
     from mpi4py_fft_amd import _lib
     eng = _lib.engine()
@@ -58,6 +62,9 @@ def test_guru2_plans_against_numpy(dt, n, planes, blocks, pitch, launches, order
     if dt == 'F' and n == 512 and not cf:
         launches = 2                         # (the complex64 n = 512 pair exists as [strided -> rows] only)
     assert eng.plan_cost(hf)[2] == launches and eng.plan_cost(hb)[2] == launches, (eng.plan_describe(hf), eng.plan_describe(hb))
+    if tiles:                                # (tiles per plane of either pass: which tile shapes the pair runs on)
+        for h in (hf, hb):
+            assert '%d + %d tiles per plane' % tiles in eng.plan_describe(h), eng.plan_describe(h)
     a = torch.from_numpy(x).cuda()
     buf = torch.full((blocks * bstride,), float('nan'), dtype=cdt, device='cuda')
     eng.execute_ptr(hf, a.data_ptr(), buf.data_ptr(), 1.0 / (n * n))
@@ -81,6 +88,20 @@ def test_guru2_plans_against_numpy(dt, n, planes, blocks, pitch, launches, order
     assert rt <= tol, (rt, tol)
     eng.plan_destroy(hf)
     eng.plan_destroy(hb)
+
+
+@pytest.mark.parametrize('n512,tiles', [(1, (32, 32)), (2, (16, 16))])
+def test_guru2_plans_on_either_tile_shape_at_n_512(n512, tiles, small_ring):
+    """Option fuse2_n512: the complex128 [strided -> rows] pairs at n = 512 -- natural planes forward, blocks on the input
+    side backward -- on the 16-line tiles of every other n = 512 pair (1: csrc/fft_fused_f64.hip Fused512R32, 32 tiles of
+    either pass per 512 x 512 plane) or on the default 32-line ones (2: Fused512T32, 16 tiles): what the case above asserts,
+    and the tile counts."""
+    from mpi4py_fft_amd import _lib
+    _lib.set_option('fuse2_n512', n512)
+    try:
+        _guru2_against_numpy('D', 512, 16, 4, 0, 1, 'cols-first', tiles)
+    finally:
+        _lib.set_option('fuse2_n512', 2)          # (the library's default: options are write-only)
 
 
 @pytest.mark.parametrize('n1,n2,planes,blocks,pitch', [(512, 1024, 16, 1, 0), (512, 1024, 20, 4, 32), (1024, 512, 16, 2, 0),
