@@ -22,9 +22,14 @@ import numpy as np
 import torch
 
 
-def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False):
+def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
+          transfer=False, stats=None):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
-    `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L)."""
+    `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
+    With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
+    N_hat the fused right-hand side evaluated with nu = 0 -- the projected nonlinear term alone: T[0] = T(k) of
+    dE(k)/dt = T(k) - 2 nu k^2 E(k), T[1] = k^2 T(k); a dict passed as `stats` also receives 'nonlinear_energy'
+    (`energy(N_hat)`) and 'helicity' (`helicity(U_hat)`)."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -56,7 +61,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         W_hat = newDistArray(FFT, rank=1)                     # i K x u_hat
         UxW = newDistArray(FFT, False, rank=1)                # u x curl u
 
-        def compute_rhs_fused():
+        def compute_rhs_fused(nu=nu):
             for j in range(3):
                 FFT.backward(U_hat[j], U[j])                  # kernels read U_hat[j], write U[j]
             ops.curl(U_hat, W_hat)
@@ -146,6 +151,17 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
               % (N[0], nsteps, ('fused-kernel' if fused else 'torch-expression') + (' + HIP graph replay' if graph else ''), elapsed,
                  elapsed / nsteps * 1e3, energy))
+    if transfer:
+        assert fused and not spectrum
+        compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term
+        T = ops.transfer(U_hat, dU)
+        if stats is not None:
+            stats.update(nonlinear_energy=ops.energy(dU), helicity=ops.helicity(U_hat))
+        if verbose and world.Get_rank() == 0:
+            print('  transfer: sum T = %.3e, max |T| = %.3e, max |flux| = %.3e'
+                  % (T[0].sum(), np.abs(T[0]).max(), np.abs(spectral.flux(T)).max()))
+        FFT.destroy()
+        return energy, T
     if spectrum:
         E = spectral.SpectralOps(FFT, L).spectrum(U_hat)
         if verbose and world.Get_rank() == 0:
@@ -157,7 +173,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
 
 
 if __name__ == '__main__':
-    from mpi4py_fft_amd import comm
+    from mpi4py_fft_amd import comm, spectral
     w = comm.init_distributed()
     e = solve(w, verbose=True)
     assert round(e - 0.124953117517, 7) == 0, e
@@ -165,6 +181,12 @@ if __name__ == '__main__':
     assert round(e - 0.124953117517, 7) == 0, e
     e, E = solve(w, verbose=True, spectrum=True)
     assert round(E[0].sum() - 0.124953117517, 7) == 0, E[0].sum()
+    st = {}
+    e, T = solve(w, verbose=True, transfer=True, stats=st)
+    if w.Get_rank() == 0:
+        print('  sum T = %.3e, max |Pi| = %.3e, mean helicity = %.3e (the Taylor-Green vortex has none)'
+              % (T[0].sum(), np.abs(spectral.flux(T)).max(), st['helicity']))
+    assert abs(T[0].sum()) <= 1e-10 * np.sqrt(e * st['nonlinear_energy']) and abs(st['helicity']) <= 1e-10 * e
     if w.Get_size() == 1:
         e = solve(w, verbose=True, graph=True)
         assert round(e - 0.124953117517, 7) == 0, e

@@ -303,7 +303,24 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    call to the next to rounding (a few units in the last place), not bit for bit.
  *                    nbins <= 4096 and n1, n2 <= 2^30, else GFFT_ERR_UNSUPPORTED; bad arguments (null pointers other
  *                    than d_w2, ncomp < 1, nbins < 1, dk <= 0, precision) are GFFT_ERR_INVALID before a device is
- *                    touched; an empty block (n0 n1 n2 = 0) writes zeros. */
+ *                    touched; an empty block (n0 n1 n2 = 0) writes zeros.
+ *   gfft_ps_cospectrum shell co-spectrum of a_hat and b_hat, both [ncomp][n0][n1][n2], in ONE read of each, in double as above:
+ *                      b = floor(sqrt(k0^2 + k1^2 + k2^2) / dk + 0.5)      (modes with b >= nbins are dropped)
+ *                      GFFT_PS_DOT       c = sum_comp Re(conj(a_c) b_c) = sum_comp (Re a_c Re b_c + Im a_c Im b_c)
+ *                      GFFT_PS_HELICITY  c = Re(conj(a) . (i K x a)) = 2 K . (Re a x Im a); ncomp = 3, d_b_hat is not read
+ *                                        (may be NULL) and no curl is stored
+ *                      e = scale * w2[i2] * c                              (d_w2 NULL: weight 1)
+ *                      out[0][b] += e;  out[1][b] += |k|^2 e               d_out = double[2][nbins], OVERWRITTEN
+ *                    The bins are signed.  d_a_hat == d_b_hat is allowed: GFFT_PS_DOT of a field with itself at scale = 0.5
+ *                    is gfft_ps_spectrum to rounding.  With u_hat and the projected nonlinear term N_hat (scale = 1) row 0
+ *                    is the transfer spectrum T(k) of dE(k)/dt = T(k) - 2 nu k^2 E(k); GFFT_PS_HELICITY of u_hat gives H(k),
+ *                    sum(out[0]) = <u . curl u>.  d_w2, d_k*, scratch, summation order, repeatability and capture: as for
+ *                    gfft_ps_spectrum.
+ *                    nbins <= 4096 and n1, n2 <= 2^30, else GFFT_ERR_UNSUPPORTED; bad arguments (null pointers other
+ *                    than d_w2 and, for GFFT_PS_HELICITY, d_b_hat; an unknown op; ncomp < 1, or != 3 for GFFT_PS_HELICITY;
+ *                    nbins < 1; dk <= 0; a non-finite scale; negative extents; precision) are GFFT_ERR_INVALID before a
+ *                    device is touched; an empty block (n0 n1 n2 = 0) writes zeros. */
+enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
                  int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
 int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream);
@@ -314,6 +331,9 @@ int gfft_ps_rk_stage(void *d_u, const void *d_u0, void *d_u1, const void *d_du, 
 int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
                      const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *d_out,
                      int precision, void *stream);
+int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale, const void *d_k0,
+                       const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk,
+                       int nbins, double *d_out, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

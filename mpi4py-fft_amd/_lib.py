@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBPATH = os.path.join(_HERE, 'libgfft.so')
 
 C2C_FORWARD, C2C_BACKWARD, R2C, C2R = -1, 1, -2, 2
+PS_DOT, PS_HELICITY = 0, 1              # op of gfft_ps_cospectrum
 
 _lib = None
 
@@ -75,6 +76,8 @@ def _declare(lib):
         'gfft_ps_rk_stage': (c.c_int, [vp, vp, vp, vp, c.c_int64, c.c_double, c.c_double, c.c_int, vp]),
         'gfft_ps_spectrum': (c.c_int, [vp, c.c_int, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int,
                                        vp, c.c_int, vp]),
+        'gfft_ps_cospectrum': (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_double, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64,
+                                         c.c_double, c.c_int, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -403,6 +406,17 @@ class HipEngine:
         check(lib().gfft_ps_spectrum(tu.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
                                      None if w2 is None else w2.data_ptr(), shape[0], shape[1], shape[2], float(dk),
                                      int(nbins), tout.data_ptr(), precision, current_stream()))
+
+    def ps_cospectrum(self, ta, tb, ncomp, op, scale, k, w2, shape, dk, nbins, tout, precision):
+        """gfft_ps_cospectrum: op = PS_DOT / PS_HELICITY (tb None); tout = double[2][nbins] on the device, overwritten."""
+        self.require_device(ta)
+        self.require_device(tout)
+        if tb is not None:
+            self.require_device(tb)
+        check(lib().gfft_ps_cospectrum(ta.data_ptr(), None if tb is None else tb.data_ptr(), int(ncomp), int(op), float(scale),
+                                       k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                       None if w2 is None else w2.data_ptr(), shape[0], shape[1], shape[2], float(dk),
+                                       int(nbins), tout.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

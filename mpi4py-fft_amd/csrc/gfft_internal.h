@@ -345,6 +345,10 @@ size_t ps_spectrum_scratch_bytes(int nbins);
 hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
                               int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
                               int precision, hipStream_t s);
+// shell co-spectrum: op = GFFT_PS_DOT (0) or GFFT_PS_HELICITY (1, b unused); slabs as for the spectrum
+hipError_t launch_ps_cospectrum(const void *a, const void *b, int ncomp, int op, double scale, const void *k0, const void *k1,
+                                const void *k2, const void *w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins,
+                                double *out, double *slabs, int precision, hipStream_t s);
 extern int g_copy_nt;
 hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
 hipError_t launch_tile_copy(const void *src, void *dst, int64_t outer, int64_t n, int64_t inner,

@@ -2965,6 +2965,27 @@ int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const voi
   return GFFT_OK;
 }
 
+int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale, const void *d_k0,
+                       const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk,
+                       int nbins, double *d_out, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_a_hat || !d_k0 || !d_k1 || !d_k2 || !d_out || (op != GFFT_PS_DOT && op != GFFT_PS_HELICITY) ||
+      (op == GFFT_PS_DOT && !d_b_hat) || ncomp < 1 || (op == GFFT_PS_HELICITY && ncomp != 3) || nbins < 1 || !(dk > 0) ||
+      !std::isfinite(scale) || n0 < 0 || n1 < 0 || n2 < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_cospectrum: bad argument");
+  if (nbins > ps_spectrum_max_bins()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_cospectrum: more than 4096 bins");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30)) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_cospectrum: axis longer than 2^30");
+  int rc = check_device();
+  if (rc) return rc;
+  // the same slabs in the stream's shared scratch as the spectrum: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_pool().get((hipStream_t)stream, ps_spectrum_scratch_bytes(nbins), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_cospectrum(d_a_hat, d_b_hat, ncomp, op, scale, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk, nbins, d_out,
+                               static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
 int gfft_malloc(void **d_ptr, size_t bytes) {
   int rc = check_device();
   if (rc) return rc;

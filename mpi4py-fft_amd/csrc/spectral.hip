@@ -235,6 +235,122 @@ ps_spectrum_kernel(const cx<real> *__restrict__ u, int ncomp, const real *__rest
   for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) slab[i] = sp_hist[i];
 }
 
+// ---- shell co-spectrum: Re(conj(a_hat) . b_hat) and |k|^2 times it, binned by |k|, one read of each field -------------
+// The spectrum kernel with a signed addend: same chunks, same walk of (i0, i1, i2), same row sums, histogram and slabs
+// (sp_wave_add and the slab sum never look at a sign).  Per mode, everything in double (inputs converted first):
+//   SP_DOT       c = sum_comp (Re a_c Re b_c + Im a_c Im b_c);  the 2 x 3 loads of a vector mode are in flight together
+//   SP_HELICITY  c = Re(conj(a) . (i K x a)) = 2 K . (Re a x Im a): three components of `a` alone, the curl is never stored
+//   e = (scale w2[i2]) c
+// a == b is allowed (both are only read).  Bytes per mode double against the spectrum for SP_DOT while the arithmetic
+// beside them grows by three multiply-adds per component: of the suspects listed above, contention of the shell adds and
+// the square root / divide weigh the same per mode and so half as much per byte.
+enum { SP_DOT = 0, SP_HELICITY = 1 };
+
+template <typename real, int V>
+__device__ __forceinline__ void sp_acc_dot(double (&s)[V], const sp_load<real, V> &a, const sp_load<real, V> &b) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const double ar = a.m[j].x, ai = a.m[j].y, br = b.m[j].x, bi = b.m[j].y;          // converted before multiplying
+    s[j] += ar * br + ai * bi;
+  }
+}
+
+// V as in ps_spectrum_kernel; V = 2 needs BOTH fields 16-B aligned
+template <typename real, int V, int OP>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_cospectrum_kernel(const cx<real> *__restrict__ fa, const cx<real> *__restrict__ fb, int ncomp, double scale,
+                     const real *__restrict__ k0, const real *__restrict__ k1, const real *__restrict__ k2,
+                     const real *__restrict__ w2, uint32_t n1, uint32_t n2, int64_t count, int64_t chunk, double dk,
+                     int nbins, double *__restrict__ slabs) {
+  extern __shared__ double sp_hist[];
+  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) sp_hist[i] = 0.0;
+  __syncthreads();
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (i0, i1, i2) of the first mode of the current step, uniform over the workgroup
+  const int64_t row0 = begin / n2;
+  uint32_t c0 = (uint32_t)(begin - row0 * n2);
+  int64_t p0 = row0 / n1;
+  uint32_t r0 = (uint32_t)(row0 - p0 * n1);
+  for (int64_t base = begin; base < end; base += PS_THREADS * V) {
+    const int64_t e0 = base + (int64_t)threadIdx.x * V;
+    uint32_t c = c0 + threadIdx.x * V;
+    uint32_t q = c / n2;
+    uint32_t i2 = c - q * n2;
+    q += r0;
+    const uint32_t pq = q / n1;
+    uint32_t i1 = q - pq * n1;
+    int64_t i0 = p0 + pq;
+    int b[V];
+    double en[V], kk[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) { b[j] = -1; en[j] = 0.0; kk[j] = 0.0; }
+    if (e0 < end) {                                      // (count and chunk are multiples of V when V == 2: all V or none)
+      double s[V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) s[j] = 0.0;
+      const sp_load<real, V> *pa = reinterpret_cast<const sp_load<real, V> *>(fa + e0);
+      const int64_t comp = count / V;
+      [[maybe_unused]] sp_load<real, V> h0, h1, h2;      // SP_HELICITY: the three components, used once the wavenumbers are known
+      if constexpr (OP == SP_DOT) {
+        const sp_load<real, V> *pb = reinterpret_cast<const sp_load<real, V> *>(fb + e0);
+        int cc = 0;
+        for (; cc + 3 <= ncomp; cc += 3, pa += 3 * comp, pb += 3 * comp) {
+          const sp_load<real, V> a0 = pa[0], a1 = pa[comp], a2 = pa[2 * comp];
+          const sp_load<real, V> b0 = pb[0], b1 = pb[comp], b2 = pb[2 * comp];
+          sp_acc_dot(s, a0, b0);
+          sp_acc_dot(s, a1, b1);
+          sp_acc_dot(s, a2, b2);
+        }
+        for (; cc < ncomp; ++cc, pa += comp, pb += comp) {
+          const sp_load<real, V> a0 = *pa, b0 = *pb;
+          sp_acc_dot(s, a0, b0);
+        }
+      } else {
+        h0 = pa[0];
+        h1 = pa[comp];
+        h2 = pa[2 * comp];
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const double kx = k0[i0], ky = k1[i1], kz = k2[i2];
+        const double k2sq = (kx * kx + ky * ky) + kz * kz;
+        const double w = w2 ? (double)w2[i2] : 1.0;
+        const double sh = floor(sqrt(k2sq) / dk + 0.5);
+        b[j] = sh < (double)nbins ? (int)sh : -1;       // (a NaN wavenumber drops the mode too)
+        if constexpr (OP == SP_HELICITY) {
+          const double x0 = h0.m[j].x, x1 = h1.m[j].x, x2 = h2.m[j].x;              // Re a
+          const double y0 = h0.m[j].y, y1 = h1.m[j].y, y2 = h2.m[j].y;              // Im a
+          s[j] = 2.0 * ((kx * (x1 * y2 - x2 * y1) + ky * (x2 * y0 - x0 * y2)) + kz * (x0 * y1 - x1 * y0));
+        }
+        en[j] = (scale * w) * s[j];
+        kk[j] = k2sq * en[j];
+        if (++i2 == n2) {                                // the pair's second mode may start the next row
+          i2 = 0;
+          if (++i1 == n1) { i1 = 0; ++i0; }
+        }
+      }
+    }
+    if (V == 2) {
+      // the pair's modes are neighbours along i2: same shell almost always; otherwise the second goes in on its own
+      if (b[V - 1] == b[0]) { en[0] += en[V - 1]; kk[0] += kk[V - 1]; }
+      else if (b[V - 1] >= 0) { atomicAdd(&sp_hist[b[V - 1]], en[V - 1]); atomicAdd(&sp_hist[nbins + b[V - 1]], kk[V - 1]); }
+    }
+    sp_wave_add(sp_hist, nbins, b[0], en[0], kk[0]);
+    // advance the step's first mode by 256 V
+    c = c0 + PS_THREADS * V;
+    q = c / n2;
+    c0 = c - q * n2;
+    q += r0;
+    const uint32_t pn = q / n1;
+    r0 = q - pn * n1;
+    p0 += pn;
+  }
+  __syncthreads();
+  double *slab = slabs + (int64_t)blockIdx.x * 2 * nbins;
+  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) slab[i] = sp_hist[i];
+}
+
 // out[i] = sum over the workgroups' slabs, in workgroup order (nwg == 0: an empty block, zeros).  One thread per output walks
 // the slabs serially, eight loads in flight: at most 2048 x 16 nbins bytes, nothing beside u_hat at 1024^3, but a
 // latency-bound tail on small arrays -- unmeasured; a fixed-order tree over more threads is the remedy if it shows.
@@ -305,23 +421,48 @@ int ps_spectrum_max_bins() { return SP_MAX_BINS; }
 
 size_t ps_spectrum_scratch_bytes(int nbins) { return (size_t)SP_MAX_WG * 2 * nbins * sizeof(double); }
 
+namespace {
+
+// launch geometry of the shell kernels: V modes per lane, one contiguous chunk of whole steps per workgroup
+struct sp_geom { int V; int64_t chunk; int nwg; };
+
+// fp32: two modes per 16-B load where every component of every field starts 16-B aligned
+sp_geom sp_geometry(int64_t count, int precision, bool aligned16) {
+  sp_geom g;
+  g.V = (precision == 4 && count % 2 == 0 && aligned16) ? 2 : 1;
+  const int64_t step = (int64_t)PS_THREADS * g.V;
+  g.chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
+  g.chunk = (g.chunk + step - 1) / step * step;
+  g.nwg = count ? (int)((count + g.chunk - 1) / g.chunk) : 0;
+  return g;
+}
+
+template <typename real, int V>
+void sp_launch_co(int op, const sp_geom &g, size_t lds, hipStream_t s, const void *a, const void *b, int ncomp, double scale,
+                  const void *k0, const void *k1, const void *k2, const void *w2, int64_t n1, int64_t n2, int64_t count,
+                  double dk, int nbins, double *slabs) {
+  const auto kern = op == SP_HELICITY ? ps_cospectrum_kernel<real, V, SP_HELICITY> : ps_cospectrum_kernel<real, V, SP_DOT>;
+  hipLaunchKernelGGL(kern, dim3(g.nwg), dim3(PS_THREADS), lds, s, (const cx<real> *)a, (const cx<real> *)b, ncomp, scale,
+                     (const real *)k0, (const real *)k1, (const real *)k2, (const real *)w2, (uint32_t)n1, (uint32_t)n2,
+                     count, g.chunk, dk, nbins, slabs);
+}
+
+}  // namespace
+
 hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
                               int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
                               int precision, hipStream_t s) {
   const int64_t count = n0 * n1 * n2;
-  // fp32: two modes per 16-B load where every component starts 16-B aligned
-  const int V = (precision == 4 && count % 2 == 0 && (uintptr_t)u % 16 == 0) ? 2 : 1;
-  const int64_t step = (int64_t)PS_THREADS * V;
-  int64_t chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
-  chunk = (chunk + step - 1) / step * step;
-  const int nwg = count ? (int)((count + chunk - 1) / chunk) : 0;
+  const sp_geom g = sp_geometry(count, precision, (uintptr_t)u % 16 == 0);
+  const int64_t chunk = g.chunk;
+  const int nwg = g.nwg;
   const size_t lds = (size_t)2 * nbins * sizeof(double);
   if (nwg) {
     if (precision == 8)
       hipLaunchKernelGGL((ps_spectrum_kernel<double, 1>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<double> *)u, ncomp,
                          (const double *)k0, (const double *)k1, (const double *)k2, (const double *)w2, (uint32_t)n1,
                          (uint32_t)n2, count, chunk, dk, nbins, slabs);
-    else if (V == 2)
+    else if (g.V == 2)
       hipLaunchKernelGGL((ps_spectrum_kernel<float, 2>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<float> *)u, ncomp,
                          (const float *)k0, (const float *)k1, (const float *)k2, (const float *)w2, (uint32_t)n1,
                          (uint32_t)n2, count, chunk, dk, nbins, slabs);
@@ -334,6 +475,29 @@ hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const vo
   }
   hipLaunchKernelGGL(ps_spectrum_sum_kernel, dim3((2 * nbins + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, s, slabs,
                      nwg, 2 * nbins, out);
+  return hipGetLastError();
+}
+
+// op: GFFT_PS_DOT (0) / GFFT_PS_HELICITY (1; b is not read); same slabs and slab sum as the spectrum
+hipError_t launch_ps_cospectrum(const void *a, const void *b, int ncomp, int op, double scale, const void *k0, const void *k1,
+                                const void *k2, const void *w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins,
+                                double *out, double *slabs, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  const bool aligned = (uintptr_t)a % 16 == 0 && (op == SP_HELICITY || (uintptr_t)b % 16 == 0);
+  const sp_geom g = sp_geometry(count, precision, aligned);
+  const size_t lds = (size_t)2 * nbins * sizeof(double);
+  if (g.nwg) {
+    if (precision == 8)
+      sp_launch_co<double, 1>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
+    else if (g.V == 2)
+      sp_launch_co<float, 2>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
+    else
+      sp_launch_co<float, 1>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(ps_spectrum_sum_kernel, dim3((2 * nbins + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, s, slabs,
+                     g.nwg, 2 * nbins, out);
   return hipGetLastError();
 }
 

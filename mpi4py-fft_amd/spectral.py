@@ -13,6 +13,9 @@ and so are the diagnostics a DNS reads every few steps, which the reference leav
 
     spectrum(u_hat)             E(k) and |k|^2 E(k) per shell of width dk, Hermitian-weighted, one read of u_hat
     energy(u_hat), enstrophy(u_hat)   their totals: <u.u>/2 and <|grad u|^2>/2
+    cospectrum(a_hat, b_hat)    Re(conj(a_hat) . b_hat) per shell, signed, one read of each field
+    transfer(u_hat, n_hat)      T(k) of the shell budget dE(k)/dt = T(k) - 2 nu k^2 E(k); flux(T) = the energy flux
+    helicity_spectrum(u_hat), helicity(u_hat)   H(k) = Re(conj(u_hat) . (i K x u_hat)) without a stored curl; <u . curl u>
 
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
@@ -120,6 +123,13 @@ class SpectralOps:
         Bins repeat from one call to the next to rounding (a few units in the last place), not bit for bit: inside a
         workgroup the waves add to the shared histogram in the order they arrive.  Across workgroups and ranks the
         order is fixed."""
+        t, ncomp, precision = self._field(u_hat)
+        dk, nbins, out = self._bins(t, nbins, dk, out)
+        _lib.engine().ps_spectrum(t, ncomp, self.K, self.W, self.shape, dk, nbins, out, precision)
+        return self._reduce(out) if reduce else out
+
+    def _field(self, u_hat):
+        """(tensor, components, precision) of a spectral field: [m] + spectral shape or, a scalar field, the spectral shape"""
         t = _t(u_hat)
         if tuple(t.shape) == self.shape:
             ncomp = 1
@@ -127,15 +137,21 @@ class SpectralOps:
             assert tuple(t.shape[1:]) == self.shape and t.dim() == 4, (tuple(t.shape), self.shape)
             ncomp = int(t.shape[0])
         assert t.is_contiguous() and t.dtype in (torch.complex64, torch.complex128)
-        self._same_precision(8 if t.dtype == torch.complex128 else 4)
+        precision = 8 if t.dtype == torch.complex128 else 4
+        self._same_precision(precision)
+        return t, ncomp, precision
+
+    def _bins(self, t, nbins, dk, out):
+        """The defaults of a shell histogram and its device tensor: (dk, nbins, out)"""
         dk = self.dk if dk is None else float(dk)
         nbins = self.default_nbins(dk) if nbins is None else int(nbins)
         if out is None:
             out = torch.empty((2, nbins), dtype=torch.float64, device=t.device)
         assert tuple(out.shape) == (2, nbins) and out.dtype == torch.float64 and out.is_contiguous()
-        _lib.engine().ps_spectrum(t, ncomp, self.K, self.W, self.shape, dk, nbins, out, 8 if t.dtype == torch.complex128 else 4)
-        if not reduce:
-            return out
+        return dk, nbins, out
+
+    def _reduce(self, out):
+        """This rank's bins added over the ranks of the grid, on the host: the same bits on every rank"""
         bins = out.cpu().numpy()                       # (waits for the kernel)
         _lib.check_async()
         for c in self.comms:                           # one grid axis after the other: the same order on every rank
@@ -153,6 +169,48 @@ class SpectralOps:
         """<|grad u|^2>/2 over the whole box = the enstrophy <|curl u|^2>/2 of a solenoidal field; the dissipation rate
         is 2 nu times it (synchronises: see `spectrum`)."""
         return float(self.spectrum(u_hat)[1].sum())
+
+    def cospectrum(self, a_hat, b_hat, scale=1.0, nbins=None, dk=None, out=None, reduce=True):
+        """Shell co-spectrum of two forward-normalised fields of the same shape and precision: float64 [2][nbins],
+            [0][b] = sum over shell b of scale * w * sum_c Re(conj(a_hat_c) * b_hat_c)      (sums to scale * <a.b>)
+            [1][b] = the same with each mode times |k|^2
+        signed.  Shells, weights, shapes, defaults, `reduce` / `out` and repeatability are those of `spectrum`; one kernel,
+        one read of each field, no array-sized temporaries.  a_hat may be b_hat: cospectrum(u, u, scale=0.5) equals
+        spectrum(u) to rounding."""
+        ta, ncomp, precision = self._field(a_hat)
+        tb, mb, pb = self._field(b_hat)
+        assert (ncomp, precision) == (mb, pb) and ta.dim() == tb.dim(), 'the two fields differ in shape or precision'
+        dk, nbins, out = self._bins(ta, nbins, dk, out)
+        _lib.engine().ps_cospectrum(ta, tb, ncomp, _lib.PS_DOT, scale, self.K, self.W, self.shape, dk, nbins, out, precision)
+        return self._reduce(out) if reduce else out
+
+    def transfer(self, u_hat, n_hat, nbins=None, dk=None, out=None, reduce=True):
+        """Transfer spectrum: [0][b] = T(k) = sum w Re(conj(u_hat) . n_hat) with n_hat the projected nonlinear term, [1][b] =
+        k^2 T(k).  The shell budget is dE(k)/dt = T(k) - 2 nu k^2 E(k) (row 1 of `spectrum`); sum T = 0 for a conservative
+        nonlinear term, and `flux(T)` is the energy flux through each shell."""
+        return self.cospectrum(u_hat, n_hat, 1.0, nbins, dk, out, reduce)
+
+    def helicity_spectrum(self, u_hat, nbins=None, dk=None, out=None, reduce=True):
+        """Helicity spectrum of a velocity field [3] + spectral shape: [0][b] = H(k) = sum w Re(conj(u_hat) . w_hat) with
+        w_hat = 1j * (K x u_hat) formed in registers -- no curl is stored; sums to <u . curl u>.  [1][b] = k^2 H(k).
+        Realizability: |H(k)| <= 2 k E(k) mode by mode.  Otherwise as `cospectrum`."""
+        t, ncomp, precision = self._field(u_hat)
+        assert ncomp == 3 and t.dim() == 4, 'helicity needs a three-component field'
+        dk, nbins, out = self._bins(t, nbins, dk, out)
+        _lib.engine().ps_cospectrum(t, None, 3, _lib.PS_HELICITY, 1.0, self.K, self.W, self.shape, dk, nbins, out, precision)
+        return self._reduce(out) if reduce else out
+
+    def helicity(self, u_hat):
+        """Mean helicity <u . curl u> over the whole box (synchronises: see `spectrum`)."""
+        return float(self.helicity_spectrum(u_hat)[0].sum())
+
+
+def flux(T):
+    """Energy flux through the shells from a transfer spectrum `T` ([2][nbins] as `SpectralOps.transfer` returns it, or
+    its row 0): Pi[b] = -sum_{j <= b} T[0][j], the energy leaving shells 0..b per unit time; the last entry is -sum T,
+    zero for a conservative nonlinear term.  Host numpy."""
+    T = np.asarray(T, dtype=np.float64)
+    return -np.cumsum(T[0] if T.ndim == 2 else T)
 
 
 def cross(a, b, out):

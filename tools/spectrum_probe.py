@@ -5,7 +5,12 @@
       kept between calls: the favourable form) -- |u|^2, component sum, weight broadcast, two index_add_;
   (c) gfft_probe_copy of u_hat's bytes (read + write: the same-run streaming ceiling),
 forms alternating in one process, HIP events.   usage: python tools/spectrum_probe.py [N ...]   (default 512 1024)
-SPECTRUM_PROBE_ONLY=a runs form (a) alone (for a counter pass under rocprofv3)."""
+Then the two-field forms on the same u_hat and a second field v_hat, transfer (T) and helicity (H):
+  (a') gfft_ps_cospectrum -- GFFT_PS_DOT reads u_hat and v_hat once, GFFT_PS_HELICITY reads u_hat once;
+  (b') torch expressions with the same kept meshes -- Re u Re v + Im u Im v, component sum, weight broadcast, two
+       index_add_; for helicity the curl 1j * (K x u_hat) is MATERIALISED first (three components written, read back);
+  (c') gfft_probe_copy moving the bytes (a') reads: u_hat -> a buffer is read + write = the two fields of T; half of it for H.
+SPECTRUM_PROBE_REPS sets the timed rounds (default 7).  SPECTRUM_PROBE_ONLY=a runs form (a) alone, =a2 the two (a') kernels alone (for a counter pass under rocprofv3)."""
 import os
 import sys
 
@@ -15,7 +20,7 @@ import torch
 
 from mpi4py_fft_amd import _lib
 
-REPS = 7
+REPS = int(os.environ.get('SPECTRUM_PROBE_REPS', 7))      # (the torch forms take seconds per call at 1024^3)
 only = os.environ.get('SPECTRUM_PROBE_ONLY')
 
 
@@ -26,6 +31,72 @@ def timed(fn):
     e.record()
     e.synchronize()
     return s.elapsed_time(e)
+
+
+def two_fields(N, u, K, w, dk, nbins, k2sq=None, bins=None):
+    """(a'), (b'), (c') for the transfer (T: u_hat . v_hat) and the helicity (H: u_hat alone); meshes given = all forms"""
+    eng, L, st = _lib.engine(), _lib.lib(), _lib.current_stream()
+    shape, nbytes = tuple(u.shape[1:]), u.numel() * 16
+    v = torch.empty_like(u)
+    for c in range(3):
+        torch.view_as_real(v[c]).normal_()
+    out_t, out_h = (torch.zeros((2, nbins), dtype=torch.float64, device='cuda') for _ in range(2))
+
+    def a_t():
+        eng.ps_cospectrum(u, v, 3, _lib.PS_DOT, 1.0, K, w, shape, dk, nbins, out_t, 8)
+
+    def a_h():
+        eng.ps_cospectrum(u, None, 3, _lib.PS_HELICITY, 1.0, K, w, shape, dk, nbins, out_h, 8)
+
+    forms = [("(a') cospectrum DOT", a_t), ("(a') cospectrum HELICITY", a_h)]
+    if bins is not None:
+        ob_t, ob_h = torch.zeros_like(out_t), torch.zeros_like(out_h)
+        k0, k1, k2 = K[0][:, None, None], K[1][None, :, None], K[2][None, None, :]
+
+        def binned(e, ob):
+            e *= w
+            ob.zero_()
+            ob[0].index_add_(0, bins, e.reshape(-1))
+            e *= k2sq
+            ob[1].index_add_(0, bins, e.reshape(-1))
+
+        def b_t():
+            binned((u.real * v.real + u.imag * v.imag).sum(0), ob_t)
+
+        def b_h():
+            wh = torch.empty_like(u)                    # the stored curl
+            wh[0] = 1j * (k1 * u[2] - k2 * u[1])
+            wh[1] = 1j * (k2 * u[0] - k0 * u[2])
+            wh[2] = 1j * (k0 * u[1] - k1 * u[0])
+            binned((u.real * wh.real + u.imag * wh.imag).sum(0), ob_h)
+
+        def c_t():
+            _lib.check(L.gfft_probe_copy(u.data_ptr(), v2.data_ptr(), nbytes, st))
+
+        def c_h():
+            _lib.check(L.gfft_probe_copy(u.data_ptr(), v2.data_ptr(), nbytes // 2, st))
+
+        v2 = torch.empty_like(u)
+        forms += [("(b') torch T", b_t), ("(b') torch H, stored curl", b_h), ("(c') copy, bytes of T", c_t),
+                  ("(c') copy, bytes of H", c_h)]
+    for _, f in forms:
+        f()
+    torch.cuda.synchronize()
+    times = [[] for _ in forms]
+    for _ in range(REPS):
+        for t, (_, f) in zip(times, forms):
+            t.append(timed(f))
+    print('N = %d, two fields: u_hat and v_hat %.2f GB each' % (N, nbytes / 1e9))
+    for (name, _), ts in zip(forms, times):
+        print('  %-28s min %.3f  median %.3f ms   [%s]' % (name, min(ts), float(np.median(ts)), ' '.join('%.3f' % t for t in ts)))
+    if bins is not None:
+        err = [float(((x - y).abs().max() / y.abs().max())) for x, y in ((ob_t, out_t), (ob_h, out_h))]
+        m = [min(t) for t in times]
+        print("  (a') and (b') agree to %.1e (T), %.1e (H) of the largest bin" % tuple(err))
+        print("  T: (a') reads %.0f GB/s; (c') moves %.0f GB/s; (a') / (c') time = %.2f; (b') / (a') = %.1f x"
+              % (2 * nbytes / m[0] / 1e6, 2 * nbytes / m[4] / 1e6, m[0] / m[4], m[2] / m[0]))
+        print("  H: (a') reads %.0f GB/s; (c') moves %.0f GB/s; (a') / (c') time = %.2f; (b') / (a') = %.1f x"
+              % (nbytes / m[1] / 1e6, nbytes / m[5] / 1e6, m[1] / m[5], m[3] / m[1]), flush=True)
 
 
 def main():
@@ -54,6 +125,9 @@ def main():
         torch.cuda.synchronize()
         got = out.clone()
         ta, tb, tc = [], [], []
+        if only == 'a2':
+            two_fields(N, u, K, w, dk, nbins)
+            continue
         if only == 'a':
             ta = [timed(form_a) for _ in range(REPS)]
             print('N = %d  (a) gfft_ps_spectrum: %s ms' % (N, ' '.join('%.3f' % t for t in ta)))
@@ -90,7 +164,9 @@ def main():
             print('  %-24s min %.3f  median %.3f ms   [%s]' % (name, min(ts), float(np.median(ts)), ' '.join('%.3f' % t for t in ts)))
         print('  (a) reads %.0f GB/s; (c) moves %.0f GB/s (read + write), i.e. %.0f GB/s each way; (a) read rate / (c) total rate = %.2f; '
               '(b) / (a) = %.1f x' % (nbytes / a / 1e6, 2 * nbytes / c / 1e6, nbytes / c / 1e6, (nbytes / a) / (2 * nbytes / c), b / a), flush=True)
-        del k2sq, bins, dst, u
+        del dst
+        two_fields(N, u, K, w, dk, nbins, k2sq, bins)
+        del k2sq, bins, u
         torch.cuda.empty_cache()
 
 
