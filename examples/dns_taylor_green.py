@@ -9,6 +9,11 @@ kernels (`mpi4py_fft_amd.spectral`: curl, cross product, projection + viscous te
 `fused=True`, default) or as torch expressions that transcribe the reference line by line
 (`fused=False`, the A/B baseline: same answer, one temporary per operator).
 
+`cfl=` turns the fixed step into a CFL-controlled one: every step takes dt = min(cfl / rate, dt) with rate = max
+sum_c |u_c| N_c / L_c from `SpectralOps.timestep` (one read of U, which the step has in physical space anyway).  With
+`device_dt=True` the step never visits the host: the statistics kernel, `gfft_ps_timestep` and the RK stages that read
+dt from device memory are all enqueued, so the adaptive step replays from a HIP graph too (`graph=True`).
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -23,13 +28,16 @@ import torch
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
-          transfer=False, stats=None):
+          transfer=False, stats=None, cfl=None, device_dt=False):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
     N_hat the fused right-hand side evaluated with nu = 0 -- the projected nonlinear term alone: T[0] = T(k) of
     dE(k)/dt = T(k) - 2 nu k^2 E(k), T[1] = k^2 T(k); a dict passed as `stats` also receives 'nonlinear_energy'
-    (`energy(N_hat)`) and 'helicity' (`helicity(U_hat)`)."""
+    (`energy(N_hat)`) and 'helicity' (`helicity(U_hat)`).
+    cfl: take dt = `SpectralOps.timestep(U, cfl, dt_max=dt)` at every step (fused path) instead of the fixed `dt`;
+    device_dt=True keeps that step in device memory (one rank; needed under graph=True).  These paths take the final
+    energy from `SpectralOps.stats`, sum_c S2_c / (2 N^3), and put the simulated 'time' into a dict passed as `stats`."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -99,17 +107,32 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
 
     a = [1. / 6., 1. / 3., 1. / 3., 1. / 6.]
     b = [0.5, 0.5, 1.]
+    adaptive = cfl is not None
+    if adaptive:
+        assert fused and (device_dt or not graph), 'a CFL-controlled step needs the fused path, and device_dt under a graph'
+        sim_time = [0.0]
+        if device_dt:
+            dt_dev = torch.zeros(2, dtype=torch.float64, device=dev)      # [0] the step, [1] the running time
     if dev.type == 'cuda':
         torch.cuda.synchronize()
     t0 = time.time()
     def step():
+        h = dt
+        if adaptive and device_dt:
+            ops.timestep(U, cfl, dt_max=dt, out=dt_dev)          # enqueued: nothing comes back to the host
+        elif adaptive:
+            h = ops.timestep(U, cfl, dt_max=dt)
+            sim_time[0] += h
         uh0.copy_(uh)
         uh1.copy_(uh)
         for rk in range(4):
-            if fused:
+            if adaptive and device_dt:
+                compute_rhs_fused()
+                spectral.rk_stage(U_hat if rk < 3 else None, U_hat0, U_hat1, dU, b[rk] if rk < 3 else 0.0, a[rk], dt=dt_dev)
+            elif fused:
                 compute_rhs_fused()
                 spectral.rk_stage(U_hat if rk < 3 else None, U_hat0, U_hat1, dU,
-                                  b[rk] * dt if rk < 3 else 0.0, a[rk] * dt)
+                                  b[rk] * h if rk < 3 else 0.0, a[rk] * h)
             else:
                 compute_rhs()
                 if rk < 3:
@@ -128,6 +151,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         # first execution, so the step can be captured into a HIP graph and replayed.
         assert fused and world.Get_size() == 1 and dev.type == 'cuda'
         keep = uh.clone()
+        keep_u = u.clone() if adaptive else None     # the adaptive step READS U: the warm-up must not leave its own there
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):
             step()                               # warm-up on the capture stream: scratch, tables
@@ -138,6 +162,9 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         with torch.cuda.graph(g):
             step()
         uh.copy_(keep)
+        if adaptive:
+            u.copy_(keep_u)
+            dt_dev.zero_()
         torch.cuda.synchronize()
         t0 = time.time()
         for _ in range(nsteps):
@@ -145,12 +172,22 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     else:
         for _ in range(nsteps):
             step()
-    energy = sum(world.allgather_obj(float((u * u).sum().item()))) / N[0] / N[1] / N[2] / 2
+    if adaptive:
+        st = ops.stats(U)                                     # rank-reduced; one read of U, no temporaries
+        energy = float(sum(st[2 + 6 * c + 3] for c in range(3))) / (2.0 * N[0] * N[1] * N[2])
+        if device_dt:
+            sim_time[0] = float(dt_dev[1].item())
+        if stats is not None:
+            stats.update(time=sim_time[0])
+    else:
+        energy = sum(world.allgather_obj(float((u * u).sum().item()))) / N[0] / N[1] / N[2] / 2
     elapsed = time.time() - t0
     if verbose and world.Get_rank() == 0:
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
               % (N[0], nsteps, ('fused-kernel' if fused else 'torch-expression') + (' + HIP graph replay' if graph else ''), elapsed,
                  elapsed / nsteps * 1e3, energy))
+        if adaptive:
+            print('  CFL %g (%s dt): simulated time %.6f in %d steps' % (cfl, 'device' if device_dt else 'host', sim_time[0], nsteps))
     if transfer:
         assert fused and not spectrum
         compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term
@@ -187,9 +224,15 @@ if __name__ == '__main__':
         print('  sum T = %.3e, max |Pi| = %.3e, mean helicity = %.3e (the Taylor-Green vortex has none)'
               % (T[0].sum(), np.abs(spectral.flux(T)).max(), st['helicity']))
     assert abs(T[0].sum()) <= 1e-10 * np.sqrt(e * st['nonlinear_energy']) and abs(st['helicity']) <= 1e-10 * e
+    st = {}
+    ea = solve(w, verbose=True, cfl=0.05, stats=st)          # CFL-controlled: about 0.004 per step instead of 0.01
+    assert 0.124953117517 < ea < 0.125 and 0 < st['time'] < 0.1, (ea, st)
     if w.Get_size() == 1:
         e = solve(w, verbose=True, graph=True)
         assert round(e - 0.124953117517, 7) == 0, e
+        eg = solve(w, verbose=True, graph=True, cfl=0.05, device_dt=True)
+        assert eg == ea, (eg, ea)                            # the device-side step is the same arithmetic
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)
+        solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, cfl=0.5)

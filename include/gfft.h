@@ -319,8 +319,38 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    nbins <= 4096 and n1, n2 <= 2^30, else GFFT_ERR_UNSUPPORTED; bad arguments (null pointers other
  *                    than d_w2 and, for GFFT_PS_HELICITY, d_b_hat; an unknown op; ncomp < 1, or != 3 for GFFT_PS_HELICITY;
  *                    nbins < 1; dk <= 0; a non-finite scale; negative extents; precision) are GFFT_ERR_INVALID before a
- *                    device is touched; an empty block (n0 n1 n2 = 0) writes zeros. */
+ *                    device is touched; an empty block (n0 n1 n2 = 0) writes zeros.
+ *   gfft_ps_stats    physical-space statistics of a REAL field u[ncomp][count] (components `count` scalars apart) in ONE
+ *                    read, every value converted to double before any arithmetic; d_out = double[GFFT_PS_STATS_HEAD +
+ *                    GFFT_PS_STATS_PER_COMP * ncomp] on the device, OVERWRITTEN:
+ *                      out[0]          = max over points of sum_c |u_c| * inv_dx[c]   (advective CFL rate: dt <= C / out[0])
+ *                      out[1]          = max over points of sum_c u_c^2
+ *                      out[2 + 6c + 0] = max u_c        out[2 + 6c + 1] = min u_c
+ *                      out[2 + 6c + 2] = sum u_c        out[2 + 6c + 3] = sum u_c^2
+ *                      out[2 + 6c + 4] = sum u_c^3 as (u u) u              out[2 + 6c + 5] = sum u_c^4 as (u u)(u u)
+ *                    inv_dx: `ncomp` HOST doubles (N_i / L_i of the grid; entries may be 0), passed by value in the launch.
+ *                    NaN: the sums propagate it -- a NaN anywhere in component c makes its four sums NaN, which is the
+ *                    blow-up signal to test for; the extrema follow fmax / fmin and ignore it, so out[0], out[1] and the
+ *                    max / min skip a point whose value is NaN.
+ *                    The result repeats BIT FOR BIT from one call to the next for the same array, count and alignment:
+ *                    lanes add their own points in index order, lanes of a wave, waves of a workgroup and the workgroups'
+ *                    partial results (in the stream's scratch, allocated by the first call: run it once before capturing
+ *                    it) combine in a fixed tree; no floating-point atomics.
+ *                    An empty block (count = 0) writes the identities: out[0] = out[1] = 0, max = -inf, min = +inf, sums 0.
+ *                    ncomp > 4 is GFFT_ERR_UNSUPPORTED; bad arguments (a null pointer, ncomp < 1, count < 0, an inv_dx
+ *                    entry that is negative or not finite, precision) are GFFT_ERR_INVALID before a device is touched.
+ *   gfft_ps_timestep one tiny kernel on the output of gfft_ps_stats, r = d_stats[0]:
+ *                      want = (r > 0 and finite) ? cfl / r : dt_max;   d_dt[0] = min(max(want, dt_min), dt_max);
+ *                      d_dt[1] += d_dt[0]                                   (the running simulation time)
+ *                    d_dt = double[2] on the device.  GFFT_ERR_INVALID unless cfl > 0, 0 <= dt_min <= dt_max, all finite.
+ *   gfft_ps_rk_stage_dt  gfft_ps_rk_stage with the coefficients cb * d_dt[0] and ca * d_dt[0]: the products are formed in
+ *                    double on the device and rounded to the field's precision as gfft_ps_rk_stage rounds its arguments,
+ *                    so the result is bit for bit that of gfft_ps_rk_stage(..., cb * dt, ca * dt, ...).  A captured launch
+ *                    reads d_dt[0] at every replay: with gfft_ps_stats and gfft_ps_timestep in front of it a whole
+ *                    CFL-controlled step replays from one graph.
+ *                    All three only enqueue on `stream`: no synchronisation, no allocation after a stream's first call. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
+enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
                  int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
 int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream);
@@ -334,6 +364,11 @@ int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const voi
 int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale, const void *d_k0,
                        const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk,
                        int nbins, double *d_out, int precision, void *stream);
+int gfft_ps_stats(const void *d_u, int ncomp, int64_t count, const double *inv_dx /* host, ncomp */, double *d_out,
+                  int precision, void *stream);
+int gfft_ps_timestep(const double *d_stats, double cfl, double dt_min, double dt_max, double *d_dt /* [2] */, void *stream);
+int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb, double ca,
+                        const double *d_dt, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

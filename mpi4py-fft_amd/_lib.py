@@ -16,6 +16,7 @@ LIBPATH = os.path.join(_HERE, 'libgfft.so')
 
 C2C_FORWARD, C2C_BACKWARD, R2C, C2R = -1, 1, -2, 2
 PS_DOT, PS_HELICITY = 0, 1              # op of gfft_ps_cospectrum
+PS_STATS_HEAD, PS_STATS_PER_COMP = 2, 6 # layout of gfft_ps_stats' output: double[HEAD + PER_COMP * ncomp]
 
 _lib = None
 
@@ -78,6 +79,9 @@ def _declare(lib):
                                        vp, c.c_int, vp]),
         'gfft_ps_cospectrum': (c.c_int, [vp, vp, c.c_int, c.c_int, c.c_double, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64,
                                          c.c_double, c.c_int, vp, c.c_int, vp]),
+        'gfft_ps_stats': (c.c_int, [vp, c.c_int, c.c_int64, c.POINTER(c.c_double), vp, c.c_int, vp]),
+        'gfft_ps_timestep': (c.c_int, [vp, c.c_double, c.c_double, c.c_double, vp, vp]),
+        'gfft_ps_rk_stage_dt': (c.c_int, [vp, vp, vp, vp, c.c_int64, c.c_double, c.c_double, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -417,6 +421,29 @@ class HipEngine:
                                        k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
                                        None if w2 is None else w2.data_ptr(), shape[0], shape[1], shape[2], float(dk),
                                        int(nbins), tout.data_ptr(), precision, current_stream()))
+
+    def ps_stats(self, tu, ncomp, count, inv_dx, tout, precision):
+        """gfft_ps_stats: tu = real [ncomp][count]; inv_dx = ncomp host floats; tout = double[2 + 6 ncomp] on the device,
+        overwritten."""
+        self.require_device(tu)
+        self.require_device(tout)
+        inv = (ctypes.c_double * int(ncomp))(*[float(x) for x in inv_dx])
+        check(lib().gfft_ps_stats(tu.data_ptr(), int(ncomp), int(count), inv, tout.data_ptr(), precision, current_stream()))
+
+    def ps_timestep(self, tstats, cfl, dt_min, dt_max, tdt):
+        """gfft_ps_timestep: tdt = double[2] on the device: [0] = the clamped step, [1] += it."""
+        self.require_device(tstats)
+        self.require_device(tdt)
+        check(lib().gfft_ps_timestep(tstats.data_ptr(), float(cfl), float(dt_min), float(dt_max), tdt.data_ptr(),
+                                     current_stream()))
+
+    def ps_rk_stage_dt(self, tu, tu0, tu1, tdu, count, cb, ca, tdt, precision):
+        """gfft_ps_rk_stage_dt: ps_rk_stage with the coefficients cb * tdt[0], ca * tdt[0] (tdt: device double)."""
+        self.require_device(tu1)
+        self.require_device(tdt)
+        check(lib().gfft_ps_rk_stage_dt(None if tu is None else tu.data_ptr(), None if tu0 is None else tu0.data_ptr(),
+                                        tu1.data_ptr(), tdu.data_ptr(), count, float(cb), float(ca), tdt.data_ptr(),
+                                        precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

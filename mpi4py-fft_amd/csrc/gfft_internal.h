@@ -339,6 +339,14 @@ hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void
                              int64_t n1, int64_t n2, double nu, int precision, hipStream_t s);
 hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
                         int precision, hipStream_t s);
+hipError_t launch_ps_rk_dt(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
+                           const double *dt, int precision, hipStream_t s);
+hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, double dt_max, double *dt, hipStream_t s);
+// physical-space statistics (spectral.hip): `slabs` = ps_stats_scratch_bytes() bytes of stream-ordered scratch
+int ps_stats_max_comp();
+size_t ps_stats_scratch_bytes();
+hipError_t launch_ps_stats(const void *u, int ncomp, int64_t count, const double *inv_dx, double *out, double *slabs,
+                           int precision, hipStream_t s);
 // shell spectrum (spectral.hip): `slabs` = ps_spectrum_scratch_bytes(nbins) bytes of stream-ordered scratch
 int ps_spectrum_max_bins();
 size_t ps_spectrum_scratch_bytes(int nbins);

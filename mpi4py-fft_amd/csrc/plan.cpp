@@ -2986,6 +2986,44 @@ int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int 
   return GFFT_OK;
 }
 
+int gfft_ps_stats(const void *d_u, int ncomp, int64_t count, const double *inv_dx, double *d_out, int precision,
+                  void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_u || !inv_dx || !d_out || ncomp < 1 || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_stats: bad argument");
+  if (ncomp > ps_stats_max_comp()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_stats: more than 4 components");
+  for (int c = 0; c < ncomp; ++c)
+    if (!std::isfinite(inv_dx[c]) || inv_dx[c] < 0) return fail(GFFT_ERR_INVALID, "gfft_ps_stats: inv_dx must be finite and >= 0");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' partial results live in the stream's shared scratch: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_pool().get((hipStream_t)stream, ps_stats_scratch_bytes(), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_stats(d_u, ncomp, count, inv_dx, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_timestep(const double *d_stats, double cfl, double dt_min, double dt_max, double *d_dt, void *stream) {
+  if (!d_stats || !d_dt || !std::isfinite(cfl) || !std::isfinite(dt_min) || !std::isfinite(dt_max) || !(cfl > 0) ||
+      !(dt_min >= 0) || !(dt_min <= dt_max))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_timestep: bad argument");
+  int rc = check_device();
+  if (rc) return rc;
+  HIP_TRY(launch_ps_timestep(d_stats, cfl, dt_min, dt_max, d_dt, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb, double ca,
+                        const double *d_dt, int precision, void *stream) {
+  if ((d_u && !d_u0) || !d_u1 || !d_du || !d_dt || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_dt: bad argument");
+  int rc = check_device();
+  if (rc) return rc;
+  HIP_TRY(launch_ps_rk_dt(d_u, d_u0, d_u1, d_du, count, cb, ca, d_dt, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
 int gfft_malloc(void **d_ptr, size_t bytes) {
   int rc = check_device();
   if (rc) return rc;

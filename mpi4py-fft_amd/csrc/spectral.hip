@@ -82,14 +82,43 @@ ps_project_kernel(cx<real> *__restrict__ du, const cx<real> *__restrict__ u, con
 
 // Runge-Kutta stage on `count` real scalars: u = u0 + cb du (if u != null); u1 += ca du
 template <typename real>
-__global__ void __launch_bounds__(PS_THREADS)
-ps_rk_kernel(real *__restrict__ u, const real *__restrict__ u0, real *__restrict__ u1, const real *__restrict__ du,
-             int64_t count, real cb, real ca) {
+__device__ __forceinline__ void ps_rk_body(real *__restrict__ u, const real *__restrict__ u0, real *__restrict__ u1,
+                                           const real *__restrict__ du, int64_t count, real cb, real ca) {
   for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * PS_THREADS) {
     const real d = du[e];
     if (u) u[e] = u0[e] + cb * d;
     u1[e] += ca * d;
   }
+}
+
+template <typename real>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_rk_kernel(real *__restrict__ u, const real *__restrict__ u0, real *__restrict__ u1, const real *__restrict__ du,
+             int64_t count, real cb, real ca) {
+  ps_rk_body(u, u0, u1, du, count, cb, ca);
+}
+
+// The same stage with the time step read from device memory: coefficients cb dt[0] and ca dt[0], the products formed in
+// double and rounded to the field's precision exactly as the host path rounds (real)(cb * dt) -- the same body, so the
+// result is bit for bit that of ps_rk_kernel with host-multiplied coefficients.  A captured graph replays with whatever
+// dt[0] holds at that moment.
+template <typename real>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_rk_dt_kernel(real *__restrict__ u, const real *__restrict__ u0, real *__restrict__ u1, const real *__restrict__ du,
+                int64_t count, double cb, double ca, const double *__restrict__ dt) {
+  const double h = dt[0];
+  ps_rk_body(u, u0, u1, du, count, (real)(cb * h), (real)(ca * h));
+}
+
+// dt[0] = clamp(cfl / stats[0], dt_min, dt_max) (dt_max where the rate is zero or not finite); dt[1] += dt[0]
+__global__ void ps_timestep_kernel(const double *__restrict__ stats, double cfl, double dt_min, double dt_max,
+                                   double *__restrict__ dt) {
+  if (blockIdx.x || threadIdx.x) return;
+  const double r = stats[0];
+  const double want = (r > 0.0 && isfinite(r)) ? cfl / r : dt_max;
+  const double h = fmin(fmax(want, dt_min), dt_max);
+  dt[0] = h;
+  dt[1] += h;
 }
 
 // ---- shell spectrum: E(k) and |k|^2 E(k) binned by |k|, one read of u_hat ----------------------------------------------
@@ -364,6 +393,121 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
   out[i] = s;
 }
 
+// ---- physical-space statistics: CFL rate, extrema and the first four power sums, one read of u --------------------------
+// u = [NC][count] reals, components `count` apart.  NVAL = 2 + 6 NC doubles, every value converted before any arithmetic:
+//   [0] max over points of sum_c |u_c| inv_dx[c]      [1] max over points of sum_c u_c^2
+//   [2 + 6c + 0..5] max u_c, min u_c, sum u_c, sum u_c^2, sum (u u) u, sum (u u)(u u)
+// Geometry (that of the shell kernels): 256-lane workgroups, at most SP_MAX_WG, each owning one contiguous chunk of whole
+// steps of 256 V points; a lane loads 16 bytes per component (V = 2 in fp64, 4 in fp32; V = 1 where count % V != 0 or
+// the base is not 16-byte aligned), the NC loads of a point in flight together.  NC is a template parameter so that the
+// NVAL accumulators of a lane are registers (an array indexed by a runtime component would live in scratch memory).
+// Summation order -- fixed, so the result repeats bit for bit for the same array, count and alignment:
+//   1. a lane combines its own points in index order (the V of a load, then step after step);
+//   2. the 64 lanes of a wave by the butterfly lane ^ 32, 16, 8, 4, 2, 1 (both partners form the same a + b);
+//   3. the 4 waves of a workgroup through LDS, in wave order; the result goes to slot [value][workgroup] of the slabs;
+//   4. st_reduce_kernel, one workgroup per value: lane t combines slabs t, t + 256, ... in that order, then 2. and 3.
+// No floating-point atomics.  Sums propagate a NaN (the blow-up signal); max / min are fmax / fmin and ignore it, so
+// [0] and [1] skip a point whose rate or square is NaN.
+// Cost per value beside its bytes: a conversion and 11 fp64 operations; no divide, no square root, no LDS in the loop.
+// Registers (hipcc -O3, gfx950; no instantiation spills or uses scratch): ps_stats_kernel<double, 2, 3> 70 VGPRs,
+// <float, 4, 3> 70, <double, 2, 4> 90, <float, 4, 4> 98 (the largest), <double, 1, 3> 62, <float, 1, 3> 58;
+// st_reduce_kernel 12, ps_rk_dt_kernel 14 / 10 (double / float), ps_timestep_kernel 13.
+constexpr int ST_MAX_COMP = 4;
+constexpr int ST_HEAD = 2, ST_PER_COMP = 6;
+enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
+
+struct st_scale { double v[ST_MAX_COMP]; };          // inv_dx, by value in the launch
+
+__host__ __device__ constexpr int st_kind(int i) {
+  return i < ST_HEAD ? ST_MAX0 : (i - ST_HEAD) % ST_PER_COMP == 0 ? ST_MAX : (i - ST_HEAD) % ST_PER_COMP == 1 ? ST_MIN : ST_SUM;
+}
+
+__device__ __forceinline__ double st_identity(int kind) {
+  return kind == ST_MAX ? -INFINITY : kind == ST_MIN ? INFINITY : 0.0;
+}
+
+__device__ __forceinline__ double st_combine(int kind, double a, double b) {
+  return kind == ST_SUM ? a + b : kind == ST_MIN ? fmin(a, b) : fmax(a, b);
+}
+
+// step 2 of the order: afterwards every lane of the wave holds the wave's value
+__device__ __forceinline__ double st_wave(int kind, double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = st_combine(kind, v, __shfl_xor(v, off));
+  return v;
+}
+
+// the V points one lane loads from one component: 16 bytes, or one scalar
+template <typename real, int V> struct alignas(sizeof(real) * V) st_load { real m[V]; };
+
+template <typename real, int V, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_stats_kernel(const real *__restrict__ u, int64_t count, int64_t chunk, st_scale inv, double *__restrict__ slabs) {
+  constexpr int NVAL = ST_HEAD + ST_PER_COMP * NC;
+  __shared__ double st_part[PS_THREADS / 64][NVAL];
+  double val[NVAL];
+#pragma unroll
+  for (int i = 0; i < NVAL; ++i) val[i] = st_identity(st_kind(i));
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (count and chunk are multiples of V: a lane has all V points of a load or none)
+  for (int64_t e0 = begin + (int64_t)threadIdx.x * V; e0 < end; e0 += PS_THREADS * V) {
+    st_load<real, V> v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = *reinterpret_cast<const st_load<real, V> *>(u + c * count + e0);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      double rate = 0.0, sq = 0.0;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const double x = v[c].m[j];                    // converted before any arithmetic
+        const double xx = x * x;
+        double *a = val + ST_HEAD + ST_PER_COMP * c;
+        rate += fabs(x) * inv.v[c];
+        sq += xx;
+        a[0] = fmax(a[0], x);
+        a[1] = fmin(a[1], x);
+        a[2] += x;
+        a[3] += xx;
+        a[4] += xx * x;
+        a[5] += xx * xx;
+      }
+      val[0] = fmax(val[0], rate);
+      val[1] = fmax(val[1], sq);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NVAL; ++i) {
+    const double w = st_wave(st_kind(i), val[i]);
+    if ((threadIdx.x & 63) == 0) st_part[threadIdx.x >> 6][i] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < NVAL) {
+    const int i = threadIdx.x, kind = st_kind(i);
+    double r = st_part[0][i];
+    for (int w = 1; w < PS_THREADS / 64; ++w) r = st_combine(kind, r, st_part[w][i]);
+    slabs[(int64_t)i * SP_MAX_WG + blockIdx.x] = r;
+  }
+}
+
+// out[i] = the nwg workgroup values of slot i combined in the fixed order above; workgroup i of the launch owns value i
+// (nwg == 0, an empty block: the identities 0, -inf, +inf, 0).  At most 8 dependent loads per lane, not 2048.
+__global__ void __launch_bounds__(PS_THREADS)
+st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+  __shared__ double part[PS_THREADS / 64];
+  const int i = blockIdx.x, kind = st_kind(i);
+  double r = st_identity(kind);
+  for (int w = threadIdx.x; w < nwg; w += PS_THREADS) r = st_combine(kind, r, slabs[(int64_t)i * SP_MAX_WG + w]);
+  r = st_wave(kind, r);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    r = part[0];
+    for (int w = 1; w < PS_THREADS / 64; ++w) r = st_combine(kind, r, part[w]);
+    out[i] = r;
+  }
+}
+
 }  // namespace
 
 hipError_t launch_ps_curl(const void *u, void *out, const void *k0, const void *k1, const void *k2, int64_t n0,
@@ -414,6 +558,63 @@ hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64
   else
     hipLaunchKernelGGL(ps_rk_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (float *)u, (const float *)u0,
                        (float *)u1, (const float *)du, count, (float)cb, (float)ca);
+  return hipGetLastError();
+}
+
+hipError_t launch_ps_rk_dt(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
+                           const double *dt, int precision, hipStream_t s) {
+  if (!count) return hipSuccess;
+  if (precision == 8)
+    hipLaunchKernelGGL(ps_rk_dt_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (double *)u,
+                       (const double *)u0, (double *)u1, (const double *)du, count, cb, ca, dt);
+  else
+    hipLaunchKernelGGL(ps_rk_dt_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (float *)u, (const float *)u0,
+                       (float *)u1, (const float *)du, count, cb, ca, dt);
+  return hipGetLastError();
+}
+
+hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, double dt_max, double *dt, hipStream_t s) {
+  hipLaunchKernelGGL(ps_timestep_kernel, dim3(1), dim3(64), 0, s, stats, cfl, dt_min, dt_max, dt);
+  return hipGetLastError();
+}
+
+int ps_stats_max_comp() { return ST_MAX_COMP; }
+
+size_t ps_stats_scratch_bytes() { return (size_t)SP_MAX_WG * (ST_HEAD + ST_PER_COMP * ST_MAX_COMP) * sizeof(double); }
+
+namespace {
+
+template <typename real, int V>
+void st_launch(int ncomp, int nwg, hipStream_t s, const void *u, int64_t count, int64_t chunk, const st_scale &inv,
+               double *slabs) {
+  const auto kern = ncomp == 1 ? ps_stats_kernel<real, V, 1> : ncomp == 2 ? ps_stats_kernel<real, V, 2>
+                  : ncomp == 3 ? ps_stats_kernel<real, V, 3> : ps_stats_kernel<real, V, 4>;
+  hipLaunchKernelGGL(kern, dim3(nwg), dim3(PS_THREADS), 0, s, (const real *)u, count, chunk, inv, slabs);
+}
+
+}  // namespace
+
+// 1 <= ncomp <= ST_MAX_COMP; `slabs` = ps_stats_scratch_bytes() bytes of stream-ordered scratch
+hipError_t launch_ps_stats(const void *u, int ncomp, int64_t count, const double *inv_dx, double *out, double *slabs,
+                           int precision, hipStream_t s) {
+  // 16-byte loads where every component starts 16-byte aligned, else one scalar per lane (as sp_geometry decides)
+  const int wide = precision == 8 ? 2 : 4;
+  const int V = (count % wide == 0 && (uintptr_t)u % 16 == 0) ? wide : 1;
+  const int64_t step = (int64_t)PS_THREADS * V;
+  int64_t chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
+  chunk = (chunk + step - 1) / step * step;
+  const int nwg = count ? (int)((count + chunk - 1) / chunk) : 0;
+  st_scale inv = {};
+  for (int c = 0; c < ncomp; ++c) inv.v[c] = inv_dx[c];
+  if (nwg) {
+    if (precision == 8 && V == 2) st_launch<double, 2>(ncomp, nwg, s, u, count, chunk, inv, slabs);
+    else if (precision == 8) st_launch<double, 1>(ncomp, nwg, s, u, count, chunk, inv, slabs);
+    else if (V == 4) st_launch<float, 4>(ncomp, nwg, s, u, count, chunk, inv, slabs);
+    else st_launch<float, 1>(ncomp, nwg, s, u, count, chunk, inv, slabs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(st_reduce_kernel, dim3(ST_HEAD + ST_PER_COMP * ncomp), dim3(PS_THREADS), 0, s, slabs, nwg, out);
   return hipGetLastError();
 }
 

@@ -17,6 +17,15 @@ and so are the diagnostics a DNS reads every few steps, which the reference leav
     transfer(u_hat, n_hat)      T(k) of the shell budget dE(k)/dt = T(k) - 2 nu k^2 E(k); flux(T) = the energy flux
     helicity_spectrum(u_hat), helicity(u_hat)   H(k) = Re(conj(u_hat) . (i K x u_hat)) without a stored curl; <u . curl u>
 
+and the physical-space side of the same diagnostics, one read of a real field, bit for bit repeatable:
+
+    stats(u)                    CFL rate max sum_c |u_c| N_c / L_c, max |u|^2, and per component max, min and the sums of
+                                u, u^2, u^3, u^4; moments(stats, npoints) turns the sums into mean / variance / skewness /
+                                flatness; a NaN in a sum is the blow-up signal
+    cfl_rate(u), timestep(u, cfl, dt_max)   the advective limit dt <= cfl / rate, clamped; with out= a device double[2]
+                                the step never leaves the device and rk_stage(..., dt=) reads it there, so a
+                                CFL-controlled RK4 step can be captured into one HIP graph
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -79,6 +88,10 @@ class SpectralOps:
         unit = 2 * np.pi / (np.full(3, 2 * np.pi) if L is None else np.asarray(L, dtype=float))
         self.dk = float(unit.min())
         self.kmax = float(np.sqrt(sum((int(n) // 2 * d) ** 2 for n, d in zip(fft.global_shape(), unit))))
+        # the physical side (stats): this rank's block and the grid's N_i / L_i
+        self.pshape = tuple(int(n) for n in fft.shape(False))
+        self.inv_dx = [float(n) / float(l) for n, l in zip(fft.global_shape(), np.full(3, 2 * np.pi) if L is None else np.asarray(L, dtype=float))]
+        self._stats_dev = None
 
     def _same_precision(self, precision):
         # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
@@ -204,6 +217,110 @@ class SpectralOps:
         """Mean helicity <u . curl u> over the whole box (synchronises: see `spectrum`)."""
         return float(self.helicity_spectrum(u_hat)[0].sum())
 
+    def stats(self, u, inv_dx=None, out=None, reduce=True):
+        """Single-point statistics of a real physical-space field in one read: float64 [2 + 6 m],
+            [0]          max over points of sum_c |u_c| * inv_dx[c]          (advective CFL rate: dt <= C / [0])
+            [1]          max over points of sum_c u_c^2
+            [2 + 6c + 0..5]   max u_c, min u_c, sum u_c, sum u_c^2, sum u_c^3, sum u_c^4      (`moments` reads the sums)
+        u is a contiguous real tensor or DeviceArray of shape [m] + fft.shape(False), m <= 4, or a scalar field of that
+        shape, in the transform's precision; every value is converted to double first.  inv_dx (m floats >= 0)
+        defaults to N_i / L_i for m == 3 and to zeros otherwise.  A NaN anywhere in component c makes its four sums NaN
+        (test those for a blow-up); max / min, [0] and [1] follow fmax / fmin and skip it.
+
+        `reduce` and `out` as in `spectrum`: reduce=True combines over the ranks of the grid on the host (maxima with
+        np.maximum, minima with np.minimum, sums added in rank order, one grid axis after the other, so every rank holds
+        identical bits), which synchronises; reduce=False only enqueues and returns the device tensor (`out`, a
+        contiguous double tensor of 2 + 6 m entries, or a new one), so it can be captured.  Unlike the spectrum the
+        result repeats bit for bit from one call to the next: the summation order is fixed."""
+        t, ncomp, precision = self._real_field(u)
+        if inv_dx is None:
+            inv_dx = self.inv_dx if ncomp == 3 else [0.0] * ncomp
+        assert len(inv_dx) == ncomp
+        nval = _lib.PS_STATS_HEAD + _lib.PS_STATS_PER_COMP * ncomp
+        if out is None:
+            out = torch.empty(nval, dtype=torch.float64, device=t.device)
+        assert tuple(out.shape) == (nval,) and out.dtype == torch.float64 and out.is_contiguous()
+        count = int(np.prod(self.pshape, dtype=np.int64))
+        _lib.engine().ps_stats(t, ncomp, count, inv_dx, out, precision)
+        return self._reduce_stats(out) if reduce else out
+
+    def _real_field(self, u):
+        """(tensor, components, precision) of a physical field: [m] + local physical shape or, a scalar field, that shape"""
+        t = _t(u)
+        if tuple(t.shape) == self.pshape:
+            ncomp = 1
+        else:
+            assert tuple(t.shape[1:]) == self.pshape and t.dim() == 4, (tuple(t.shape), self.pshape)
+            ncomp = int(t.shape[0])
+        assert t.is_contiguous() and t.dtype in (torch.float32, torch.float64), 'stats needs a contiguous real field'
+        precision = 8 if t.dtype == torch.float64 else 4
+        self._same_precision(precision)
+        return t, ncomp, precision
+
+    def _reduce_stats(self, out):
+        """This rank's statistics combined over the ranks of the grid, on the host: the same bits on every rank"""
+        vals = out.cpu().numpy()                       # (waits for the kernels)
+        _lib.check_async()
+        head, per = _lib.PS_STATS_HEAD, _lib.PS_STATS_PER_COMP
+        idx = np.arange(len(vals))
+        is_max = (idx < head) | ((idx - head) % per == 0)
+        is_min = (idx >= head) & ((idx - head) % per == 1)
+        for c in self.comms:                           # one grid axis after the other: the same order on every rank
+            parts = c.allgather_obj(vals)
+            vals = parts[0].copy()
+            for p in parts[1:]:
+                vals = np.where(is_max, np.maximum(vals, p), np.where(is_min, np.minimum(vals, p), vals + p))
+        return vals
+
+    def cfl_rate(self, u):
+        """max over the whole box of sum_c |u_c| N_c / L_c: an advective step is stable for dt <= C / cfl_rate
+        (synchronises: see `stats`)."""
+        return float(self.stats(u)[0])
+
+    def timestep(self, u, cfl, dt_max, dt_min=0.0, out=None):
+        """The CFL-limited step min(max(cfl / cfl_rate(u), dt_min), dt_max); dt_max where the rate is zero or not finite.
+        out=None: on any grid, from the rank-reduced rate; synchronises and returns a Python float.
+        out = a device double[2] tensor: one-rank grids only (no device-side reduction over ranks); enqueues the
+        statistics into a tensor this object keeps and then `gfft_ps_timestep`, which writes the step to out[0] and adds
+        it to out[1] (the running time); returns `out`.  Nothing synchronises or, after the first call, allocates, so
+        the call can be captured with the `rk_stage(..., dt=out)` calls that read the step."""
+        assert cfl > 0 and 0 <= dt_min <= dt_max and np.isfinite([cfl, dt_min, dt_max]).all()
+        if out is None:
+            return timestep_from_rate(self.cfl_rate(u), cfl, dt_max, dt_min)
+        assert not self.comms, 'the device path of timestep needs a one-rank grid'
+        assert tuple(out.shape) == (2,) and out.dtype == torch.float64 and out.is_contiguous()
+        t, ncomp, _ = self._real_field(u)
+        nval = _lib.PS_STATS_HEAD + _lib.PS_STATS_PER_COMP * 4
+        if self._stats_dev is None or self._stats_dev.device != t.device:
+            self._stats_dev = torch.empty(nval, dtype=torch.float64, device=t.device)
+        st = self._stats_dev[:_lib.PS_STATS_HEAD + _lib.PS_STATS_PER_COMP * ncomp]
+        self.stats(t, out=st, reduce=False)
+        _lib.engine().ps_timestep(st, cfl, dt_min, dt_max, out)
+        return out
+
+
+def timestep_from_rate(rate, cfl, dt_max, dt_min=0.0):
+    """The formula of `SpectralOps.timestep` and gfft_ps_timestep on a host float: cfl / rate clamped to
+    [dt_min, dt_max]; dt_max for a rate that is zero, negative, infinite or NaN."""
+    rate = float(rate)
+    want = cfl / rate if (rate > 0 and np.isfinite(rate)) else dt_max
+    return float(min(max(want, dt_min), dt_max))
+
+
+def moments(stats, npoints):
+    """Single-point moments from `SpectralOps.stats` (rank-reduced) and the GLOBAL number of points: float64 [m][4] =
+    per component the mean, the variance <(u - <u>)^2>, the skewness <(u - <u>)^3> / variance^(3/2) and the flatness
+    <(u - <u>)^4> / variance^2 (3 for a Gaussian, 3/2 for a sine).  Host numpy."""
+    s = np.asarray(stats, dtype=np.float64)
+    s = s[_lib.PS_STATS_HEAD:].reshape(-1, _lib.PS_STATS_PER_COMP)
+    n = float(npoints)
+    m1, m2, m3, m4 = (s[:, j] / n for j in (2, 3, 4, 5))
+    var = m2 - m1 * m1
+    c3 = m3 - 3 * m1 * m2 + 2 * m1 ** 3
+    c4 = m4 - 4 * m1 * m3 + 6 * m1 * m1 * m2 - 3 * m1 ** 4
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.stack([m1, var, c3 / var ** 1.5, c4 / (var * var)], axis=1)
+
 
 def flux(T):
     """Energy flux through the shells from a transfer spectrum `T` ([2][nbins] as `SpectralOps.transfer` returns it, or
@@ -222,9 +339,17 @@ def cross(a, b, out):
     return out
 
 
-def rk_stage(u, u0, u1, du, cb, ca):
-    """u = u0 + cb*du (skipped when u is None); u1 += ca*du -- one pass over the four arrays."""
+def rk_stage(u, u0, u1, du, cb, ca, dt=None):
+    """u = u0 + cb*du (skipped when u is None); u1 += ca*du -- one pass over the four arrays.
+    dt: a device double tensor; the coefficients are then cb * dt[0] and ca * dt[0], multiplied on the device (bit for
+    bit the result of passing the host products), so a captured stage follows a step that `timestep(out=)` wrote."""
     mult = 2 if np.dtype(du.dtype).kind == 'c' else 1
     count = int(np.prod(du.shape, dtype=np.int64)) * mult
+    if dt is not None:
+        dt = _t(dt)
+        assert dt.dtype == torch.float64 and dt.numel() >= 1 and dt.is_contiguous()
+        _lib.engine().ps_rk_stage_dt(None if u is None else _t(u), None if u0 is None else _t(u0), _t(u1), _t(du),
+                                     count, cb, ca, dt, _prec(du))
+        return
     _lib.engine().ps_rk_stage(None if u is None else _t(u), None if u0 is None else _t(u0), _t(u1), _t(du),
                               count, cb, ca, _prec(du))
