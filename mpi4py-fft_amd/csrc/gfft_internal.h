@@ -2,8 +2,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 
 namespace gfft {
+
+// ---- what plan.cpp shares with the entry points outside it (spectral.hip) ------------------
+int fail(int code, const std::string &msg);        // sets the calling thread's gfft_last_error(); returns code
+int hip_fail(hipError_t e, const char *what);      // ... to "<what>: <HIP's error string>"; GFFT_ERR_NO_DEVICE or GFFT_ERR_HIP
+int check_device();                                // GFFT_OK, or GFFT_ERR_NO_DEVICE (libgfft has no host fallback)
+int scratch_get(hipStream_t s, size_t bytes, void **out);   // the stream's shared scratch, grown to `bytes` (not inside a capture)
+#define HIP_TRY(expr)                                        \
+  do {                                                       \
+    hipError_t _e = (expr);                                  \
+    if (_e != hipSuccess) return gfft::hip_fail(_e, #expr);  \
+  } while (0)
 
 // ordinal of the calling thread's current device, as an index into per-device state: function attributes, CU
 // counts and the twiddle-table caches belong to ONE device, and a process may drive several
@@ -332,31 +344,6 @@ hipError_t launch_embed(const PointDesc &p, int precision, const void *in, void 
 hipError_t launch_mulb(const PointDesc &p, int precision, void *scratch, hipStream_t s);
 hipError_t launch_extract(const PointDesc &p, int precision, const void *scratch, void *out, double scale, hipStream_t s);
 hipError_t launch_scale(void *data, int64_t count, int precision, double scale, hipStream_t s);
-hipError_t launch_ps_curl(const void *u, void *out, const void *k0, const void *k1, const void *k2, int64_t n0,
-                          int64_t n1, int64_t n2, int precision, hipStream_t s);
-hipError_t launch_ps_cross(const void *a, const void *b, void *out, int64_t count, int precision, hipStream_t s);
-hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void *k1, const void *k2, int64_t n0,
-                             int64_t n1, int64_t n2, double nu, int precision, hipStream_t s);
-hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
-                        int precision, hipStream_t s);
-hipError_t launch_ps_rk_dt(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
-                           const double *dt, int precision, hipStream_t s);
-hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, double dt_max, double *dt, hipStream_t s);
-// physical-space statistics (spectral.hip): `slabs` = ps_stats_scratch_bytes() bytes of stream-ordered scratch
-int ps_stats_max_comp();
-size_t ps_stats_scratch_bytes();
-hipError_t launch_ps_stats(const void *u, int ncomp, int64_t count, const double *inv_dx, double *out, double *slabs,
-                           int precision, hipStream_t s);
-// shell spectrum (spectral.hip): `slabs` = ps_spectrum_scratch_bytes(nbins) bytes of stream-ordered scratch
-int ps_spectrum_max_bins();
-size_t ps_spectrum_scratch_bytes(int nbins);
-hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
-                              int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
-                              int precision, hipStream_t s);
-// shell co-spectrum: op = GFFT_PS_DOT (0) or GFFT_PS_HELICITY (1, b unused); slabs as for the spectrum
-hipError_t launch_ps_cospectrum(const void *a, const void *b, int ncomp, int op, double scale, const void *k0, const void *k1,
-                                const void *k2, const void *w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins,
-                                double *out, double *slabs, int precision, hipStream_t s);
 extern int g_copy_nt;
 hipError_t launch_copy(const void *src, void *dst, size_t bytes, hipStream_t s);
 hipError_t launch_tile_copy(const void *src, void *dst, int64_t outer, int64_t n, int64_t inner,

@@ -1,4 +1,5 @@
-// libgfft.so: C ABI (include/gfft.h) + the planner.
+// libgfft.so: C ABI (include/gfft.h) + the planner.  (The pseudo-spectral entry points live next to their kernels in spectral.hip
+// and report errors, find the device and get scratch through the four functions gfft_internal.h declares from here.)
 //
 // The planner is the device-side counterpart of fftw_planxfftn() (mpi4py_fft/fftw/
 // fftw_planxfftn.c:10-77): it turns (sizes, axes, kind) into one strided+batched 1-D pass per
@@ -30,6 +31,12 @@ using namespace gfft;
 namespace {
 
 thread_local std::string g_last_error;
+bool g_device_checked = false;
+
+}  // namespace
+
+// what the pseudo-spectral entry points in spectral.hip share with the ones here (declared in gfft_internal.h)
+namespace gfft {
 
 int fail(int code, const std::string &msg) {
   g_last_error = msg;
@@ -41,13 +48,6 @@ int hip_fail(hipError_t e, const char *what) {
               std::string(what) + ": " + hipGetErrorString(e));
 }
 
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t _e = (expr);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #expr);  \
-  } while (0)
-
-bool g_device_checked = false;
 int check_device() {
   if (g_device_checked) return GFFT_OK;
   int n = 0;
@@ -59,6 +59,10 @@ int check_device() {
   g_device_checked = true;
   return GFFT_OK;
 }
+
+}  // namespace gfft
+
+namespace {
 
 // ---- tunables ---------------------------------------------------------------------------
 struct Options {
@@ -395,6 +399,8 @@ ScratchPool &scratch_pool() {
 std::atomic<int> g_live_plans{0};
 
 }  // namespace
+
+int gfft::scratch_get(hipStream_t s, size_t bytes, void **out) { return scratch_pool().get(s, bytes, out); }
 
 struct gfft_plan_s {
   int ndims = 0, kind = 0, precision = 0;
@@ -2902,125 +2908,6 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
   int rc = check_device();
   if (rc) return rc;
   HIP_TRY(launch_scale(d_data, count, precision, scale, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
-                 int64_t n0, int64_t n1, int64_t n2, int precision, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  if (!d_u_hat || !d_out || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || (precision != 4 && precision != 8))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_curl: bad argument");
-  HIP_TRY(launch_ps_curl(d_u_hat, d_out, d_k0, d_k1, d_k2, n0, n1, n2, precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  if (!d_a || !d_b || !d_out || count < 0 || (precision != 4 && precision != 8))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_cross: bad argument");
-  HIP_TRY(launch_ps_cross(d_a, d_b, d_out, count, precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_project(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
-                    int64_t n0, int64_t n1, int64_t n2, double nu, int precision, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  if (!d_du_hat || !d_u_hat || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || (precision != 4 && precision != 8))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_project: bad argument");
-  HIP_TRY(launch_ps_project(d_du_hat, d_u_hat, d_k0, d_k1, d_k2, n0, n1, n2, nu, precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_rk_stage(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb,
-                     double ca, int precision, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  if ((d_u && !d_u0) || !d_u1 || !d_du || count < 0 || (precision != 4 && precision != 8))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage: bad argument");
-  HIP_TRY(launch_ps_rk(d_u, d_u0, d_u1, d_du, count, cb, ca, precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
-                     const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *d_out,
-                     int precision, void *stream) {
-  // (arguments first: a bad call is refused without a device, like gfft_plan_create)
-  if (!d_u_hat || !d_k0 || !d_k1 || !d_k2 || !d_out || ncomp < 1 || nbins < 1 || !(dk > 0) || n0 < 0 || n1 < 0 || n2 < 0 ||
-      (precision != GFFT_F32 && precision != GFFT_F64))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_spectrum: bad argument");
-  if (nbins > ps_spectrum_max_bins()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_spectrum: more than 4096 bins");
-  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30)) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_spectrum: axis longer than 2^30");
-  int rc = check_device();
-  if (rc) return rc;
-  // the workgroups' partial histograms live in the stream's shared scratch: allocated by the first call, so later
-  // calls -- captured ones included -- allocate nothing
-  void *slabs = nullptr;
-  rc = scratch_pool().get((hipStream_t)stream, ps_spectrum_scratch_bytes(nbins), &slabs);
-  if (rc) return rc;
-  HIP_TRY(launch_ps_spectrum(d_u_hat, ncomp, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk, nbins, d_out, static_cast<double *>(slabs),
-                             precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale, const void *d_k0,
-                       const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk,
-                       int nbins, double *d_out, int precision, void *stream) {
-  // (arguments first, as in gfft_ps_spectrum)
-  if (!d_a_hat || !d_k0 || !d_k1 || !d_k2 || !d_out || (op != GFFT_PS_DOT && op != GFFT_PS_HELICITY) ||
-      (op == GFFT_PS_DOT && !d_b_hat) || ncomp < 1 || (op == GFFT_PS_HELICITY && ncomp != 3) || nbins < 1 || !(dk > 0) ||
-      !std::isfinite(scale) || n0 < 0 || n1 < 0 || n2 < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_cospectrum: bad argument");
-  if (nbins > ps_spectrum_max_bins()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_cospectrum: more than 4096 bins");
-  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30)) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_cospectrum: axis longer than 2^30");
-  int rc = check_device();
-  if (rc) return rc;
-  // the same slabs in the stream's shared scratch as the spectrum: the first call allocates, later ones only enqueue
-  void *slabs = nullptr;
-  rc = scratch_pool().get((hipStream_t)stream, ps_spectrum_scratch_bytes(nbins), &slabs);
-  if (rc) return rc;
-  HIP_TRY(launch_ps_cospectrum(d_a_hat, d_b_hat, ncomp, op, scale, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk, nbins, d_out,
-                               static_cast<double *>(slabs), precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_stats(const void *d_u, int ncomp, int64_t count, const double *inv_dx, double *d_out, int precision,
-                  void *stream) {
-  // (arguments first, as in gfft_ps_spectrum)
-  if (!d_u || !inv_dx || !d_out || ncomp < 1 || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_stats: bad argument");
-  if (ncomp > ps_stats_max_comp()) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_stats: more than 4 components");
-  for (int c = 0; c < ncomp; ++c)
-    if (!std::isfinite(inv_dx[c]) || inv_dx[c] < 0) return fail(GFFT_ERR_INVALID, "gfft_ps_stats: inv_dx must be finite and >= 0");
-  int rc = check_device();
-  if (rc) return rc;
-  // the workgroups' partial results live in the stream's shared scratch: the first call allocates, later ones only enqueue
-  void *slabs = nullptr;
-  rc = scratch_pool().get((hipStream_t)stream, ps_stats_scratch_bytes(), &slabs);
-  if (rc) return rc;
-  HIP_TRY(launch_ps_stats(d_u, ncomp, count, inv_dx, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_timestep(const double *d_stats, double cfl, double dt_min, double dt_max, double *d_dt, void *stream) {
-  if (!d_stats || !d_dt || !std::isfinite(cfl) || !std::isfinite(dt_min) || !std::isfinite(dt_max) || !(cfl > 0) ||
-      !(dt_min >= 0) || !(dt_min <= dt_max))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_timestep: bad argument");
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(launch_ps_timestep(d_stats, cfl, dt_min, dt_max, d_dt, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb, double ca,
-                        const double *d_dt, int precision, void *stream) {
-  if ((d_u && !d_u0) || !d_u1 || !d_du || !d_dt || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
-    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_dt: bad argument");
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(launch_ps_rk_dt(d_u, d_u0, d_u1, d_du, count, cb, ca, d_dt, precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -1,10 +1,15 @@
-// Pointwise kernels of the pseudo-spectral caller either side of the transform path
-// (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one
-// temporary per operator): i K x u_hat, u x w, pressure projection + viscous term, and the
-// Runge-Kutta stage update, each one pass over its operands.  HBM-bound elementwise work:
-// 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead of three
-// array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity).
+// The pseudo-spectral layer either side of the transform path: the gfft_ps_* entry points of include/gfft.h (at the end of
+// the file), their launchers and their kernels, each one pass over its operands.
+//   * pointwise (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one temporary per
+//     operator): i K x u_hat, u x w, pressure projection + viscous term, the Runge-Kutta stage update and the time-step
+//     controller.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
+//     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
+//   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
+//     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity) and physical-space statistics (ps_stats_kernel).
+#include "../../include/gfft.h"
 #include "gfft_internal.h"
+
+#include <cmath>
 
 namespace gfft {
 
@@ -121,9 +126,14 @@ __global__ void ps_timestep_kernel(const double *__restrict__ stats, double cfl,
   dt[1] += h;
 }
 
-// ---- shell spectrum: E(k) and |k|^2 E(k) binned by |k|, one read of u_hat ----------------------------------------------
-// out[0][b] += e, out[1][b] += |k|^2 e with e = 0.5 w2[i2] sum_c |u_c|^2 and b = floor(|k| / dk + 0.5), all in double
-// (the input is converted before squaring).  The array is cut into contiguous chunks of flat modes, one per workgroup:
+// ---- shell sums: a per-mode value c and |k|^2 c binned by |k|, one read of each field ----------------------------------
+// out[0][b] += e, out[1][b] += |k|^2 e with e = (scale w2[i2]) c and b = floor(|k| / dk + 0.5), all in double (the inputs
+// are converted before any arithmetic; c may be negative: sp_wave_add and the slab sum never look at a sign).  c per mode:
+//   SP_NORM      sum_comp |a_c|^2 -- at scale = 0.5 the spectrum E(k); three loads in flight for a vector field.
+//                Internal: gfft_ps_spectrum passes it, gfft_ps_cospectrum refuses it like any unknown op
+//   SP_DOT       sum_comp (Re a_c Re b_c + Im a_c Im b_c); the 2 x 3 loads of a vector mode are in flight together; a == b is allowed
+//   SP_HELICITY  Re(conj(a) . (i K x a)) = 2 K . (Re a x Im a): three components of `a` alone, the curl is never stored
+// The array is cut into contiguous chunks of flat modes, one per workgroup:
 // local rows are often shorter than a wave (11 entries in the tests, N / 2P on pencils), so a lane's mode is its flat
 // index, never its place in a row, and every lane looks up its own row's k0^2 + k1^2 (two cached reads).  The workgroup
 // walks its chunk 256 x V modes at a time, carrying (i0, i1, i2) of the step's first mode along with 32-bit divisions
@@ -137,8 +147,12 @@ __global__ void ps_timestep_kernel(const double *__restrict__ stats, double cfl,
 // divide, 16 DPP moves and, per run of equal shells in a row of 16 lanes, two LDS adds.  A three-component fp64 field
 // has the most bytes per mode to hide that behind; a one-component fp32 field has a sixth of them and is the first
 // candidate for being bound by the arithmetic instead of HBM.  tools/spectrum_probe.py measures the fp64 vector case.
+// Bytes per mode double against SP_NORM for SP_DOT while the arithmetic beside them grows by three multiply-adds per
+// component: of the suspects listed above, contention of the shell adds and the square root / divide weigh the same per
+// mode and so half as much per byte.
 constexpr int SP_MAX_WG = 2048;          // workgroups (= slabs) of one launch: 8 per CU
 constexpr int SP_MAX_BINS = 4096;        // 2 x 4096 doubles = 64 KiB of LDS, what a workgroup gets without opting in to more
+enum { SP_DOT = GFFT_PS_DOT, SP_HELICITY = GFFT_PS_HELICITY, SP_NORM };
 
 template <int CTRL>
 __device__ __forceinline__ double sp_dpp(double v) {
@@ -184,12 +198,22 @@ __device__ __forceinline__ void sp_acc(double (&s)[V], const sp_load<real, V> &v
   }
 }
 
-// V = modes per lane and load: 1 (16 B in fp64, 8 B in fp32 when the array is not 16-B aligned) or 2 (fp32, 16 B)
 template <typename real, int V>
+__device__ __forceinline__ void sp_acc_dot(double (&s)[V], const sp_load<real, V> &a, const sp_load<real, V> &b) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const double ar = a.m[j].x, ai = a.m[j].y, br = b.m[j].x, bi = b.m[j].y;          // converted before multiplying
+    s[j] += ar * br + ai * bi;
+  }
+}
+
+// V = modes per lane and load: 1 (16 B in fp64, 8 B in fp32 when a field that is read is not 16-B aligned) or 2 (fp32, 16 B)
+template <typename real, int V, int OP>
 __global__ void __launch_bounds__(PS_THREADS)
-ps_spectrum_kernel(const cx<real> *__restrict__ u, int ncomp, const real *__restrict__ k0, const real *__restrict__ k1,
-                   const real *__restrict__ k2, const real *__restrict__ w2, uint32_t n1, uint32_t n2, int64_t count,
-                   int64_t chunk, double dk, int nbins, double *__restrict__ slabs) {
+ps_shell_kernel(const cx<real> *__restrict__ fa, const cx<real> *__restrict__ fb, int ncomp, double scale,
+                const real *__restrict__ k0, const real *__restrict__ k1, const real *__restrict__ k2,
+                const real *__restrict__ w2, uint32_t n1, uint32_t n2, int64_t count, int64_t chunk, double dk,
+                int nbins, double *__restrict__ slabs) {
   extern __shared__ double sp_hist[];
   for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) sp_hist[i] = 0.0;
   __syncthreads();
@@ -218,110 +242,20 @@ ps_spectrum_kernel(const cx<real> *__restrict__ u, int ncomp, const real *__rest
       double s[V];
 #pragma unroll
       for (int j = 0; j < V; ++j) s[j] = 0.0;
-      // components `count` modes apart, three loads in flight for a vector field
-      const sp_load<real, V> *p = reinterpret_cast<const sp_load<real, V> *>(u + e0);
-      const int64_t comp = count / V;
-      int cc = 0;
-      for (; cc + 3 <= ncomp; cc += 3, p += 3 * comp) {
-        const sp_load<real, V> v0 = p[0], v1 = p[comp], v2 = p[2 * comp];
-        sp_acc(s, v0);
-        sp_acc(s, v1);
-        sp_acc(s, v2);
-      }
-      for (; cc < ncomp; ++cc, p += comp) sp_acc(s, *p);
-#pragma unroll
-      for (int j = 0; j < V; ++j) {
-        const double kx = k0[i0], ky = k1[i1], kz = k2[i2];
-        const double k2sq = (kx * kx + ky * ky) + kz * kz;
-        const double w = w2 ? (double)w2[i2] : 1.0;
-        const double sh = floor(sqrt(k2sq) / dk + 0.5);
-        b[j] = sh < (double)nbins ? (int)sh : -1;       // (a NaN wavenumber drops the mode too)
-        en[j] = 0.5 * w * s[j];
-        kk[j] = k2sq * en[j];
-        if (++i2 == n2) {                                // the pair's second mode may start the next row
-          i2 = 0;
-          if (++i1 == n1) { i1 = 0; ++i0; }
-        }
-      }
-    }
-    if (V == 2) {
-      // the pair's modes are neighbours along i2: same shell almost always; otherwise the second goes in on its own
-      if (b[V - 1] == b[0]) { en[0] += en[V - 1]; kk[0] += kk[V - 1]; }
-      else if (b[V - 1] >= 0) { atomicAdd(&sp_hist[b[V - 1]], en[V - 1]); atomicAdd(&sp_hist[nbins + b[V - 1]], kk[V - 1]); }
-    }
-    sp_wave_add(sp_hist, nbins, b[0], en[0], kk[0]);
-    // advance the step's first mode by 256 V
-    c = c0 + PS_THREADS * V;
-    q = c / n2;
-    c0 = c - q * n2;
-    q += r0;
-    const uint32_t pa = q / n1;
-    r0 = q - pa * n1;
-    p0 += pa;
-  }
-  __syncthreads();
-  double *slab = slabs + (int64_t)blockIdx.x * 2 * nbins;
-  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) slab[i] = sp_hist[i];
-}
-
-// ---- shell co-spectrum: Re(conj(a_hat) . b_hat) and |k|^2 times it, binned by |k|, one read of each field -------------
-// The spectrum kernel with a signed addend: same chunks, same walk of (i0, i1, i2), same row sums, histogram and slabs
-// (sp_wave_add and the slab sum never look at a sign).  Per mode, everything in double (inputs converted first):
-//   SP_DOT       c = sum_comp (Re a_c Re b_c + Im a_c Im b_c);  the 2 x 3 loads of a vector mode are in flight together
-//   SP_HELICITY  c = Re(conj(a) . (i K x a)) = 2 K . (Re a x Im a): three components of `a` alone, the curl is never stored
-//   e = (scale w2[i2]) c
-// a == b is allowed (both are only read).  Bytes per mode double against the spectrum for SP_DOT while the arithmetic
-// beside them grows by three multiply-adds per component: of the suspects listed above, contention of the shell adds and
-// the square root / divide weigh the same per mode and so half as much per byte.
-enum { SP_DOT = 0, SP_HELICITY = 1 };
-
-template <typename real, int V>
-__device__ __forceinline__ void sp_acc_dot(double (&s)[V], const sp_load<real, V> &a, const sp_load<real, V> &b) {
-#pragma unroll
-  for (int j = 0; j < V; ++j) {
-    const double ar = a.m[j].x, ai = a.m[j].y, br = b.m[j].x, bi = b.m[j].y;          // converted before multiplying
-    s[j] += ar * br + ai * bi;
-  }
-}
-
-// V as in ps_spectrum_kernel; V = 2 needs BOTH fields 16-B aligned
-template <typename real, int V, int OP>
-__global__ void __launch_bounds__(PS_THREADS)
-ps_cospectrum_kernel(const cx<real> *__restrict__ fa, const cx<real> *__restrict__ fb, int ncomp, double scale,
-                     const real *__restrict__ k0, const real *__restrict__ k1, const real *__restrict__ k2,
-                     const real *__restrict__ w2, uint32_t n1, uint32_t n2, int64_t count, int64_t chunk, double dk,
-                     int nbins, double *__restrict__ slabs) {
-  extern __shared__ double sp_hist[];
-  for (int i = threadIdx.x; i < 2 * nbins; i += PS_THREADS) sp_hist[i] = 0.0;
-  __syncthreads();
-  const int64_t begin = (int64_t)blockIdx.x * chunk;
-  const int64_t end = begin + chunk < count ? begin + chunk : count;
-  // (i0, i1, i2) of the first mode of the current step, uniform over the workgroup
-  const int64_t row0 = begin / n2;
-  uint32_t c0 = (uint32_t)(begin - row0 * n2);
-  int64_t p0 = row0 / n1;
-  uint32_t r0 = (uint32_t)(row0 - p0 * n1);
-  for (int64_t base = begin; base < end; base += PS_THREADS * V) {
-    const int64_t e0 = base + (int64_t)threadIdx.x * V;
-    uint32_t c = c0 + threadIdx.x * V;
-    uint32_t q = c / n2;
-    uint32_t i2 = c - q * n2;
-    q += r0;
-    const uint32_t pq = q / n1;
-    uint32_t i1 = q - pq * n1;
-    int64_t i0 = p0 + pq;
-    int b[V];
-    double en[V], kk[V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) { b[j] = -1; en[j] = 0.0; kk[j] = 0.0; }
-    if (e0 < end) {                                      // (count and chunk are multiples of V when V == 2: all V or none)
-      double s[V];
-#pragma unroll
-      for (int j = 0; j < V; ++j) s[j] = 0.0;
+      // components `count` modes apart
       const sp_load<real, V> *pa = reinterpret_cast<const sp_load<real, V> *>(fa + e0);
       const int64_t comp = count / V;
       [[maybe_unused]] sp_load<real, V> h0, h1, h2;      // SP_HELICITY: the three components, used once the wavenumbers are known
-      if constexpr (OP == SP_DOT) {
+      if constexpr (OP == SP_NORM) {
+        int cc = 0;
+        for (; cc + 3 <= ncomp; cc += 3, pa += 3 * comp) {
+          const sp_load<real, V> v0 = pa[0], v1 = pa[comp], v2 = pa[2 * comp];
+          sp_acc(s, v0);
+          sp_acc(s, v1);
+          sp_acc(s, v2);
+        }
+        for (; cc < ncomp; ++cc, pa += comp) sp_acc(s, *pa);
+      } else if constexpr (OP == SP_DOT) {
         const sp_load<real, V> *pb = reinterpret_cast<const sp_load<real, V> *>(fb + e0);
         int cc = 0;
         for (; cc + 3 <= ncomp; cc += 3, pa += 3 * comp, pb += 3 * comp) {
@@ -413,7 +347,7 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // <float, 4, 3> 70, <double, 2, 4> 90, <float, 4, 4> 98 (the largest), <double, 1, 3> 62, <float, 1, 3> 58;
 // st_reduce_kernel 12, ps_rk_dt_kernel 14 / 10 (double / float), ps_timestep_kernel 13.
 constexpr int ST_MAX_COMP = 4;
-constexpr int ST_HEAD = 2, ST_PER_COMP = 6;
+constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
 
 struct st_scale { double v[ST_MAX_COMP]; };          // inv_dx, by value in the launch
@@ -508,69 +442,52 @@ st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__
   }
 }
 
-}  // namespace
+// ---- launchers ---------------------------------------------------------------------------------------------------------
+// f(real()) with the element type of `precision`: a launcher names its kernel and arguments once
+template <typename F>
+hipError_t by_precision(int precision, F &&f) { return precision == GFFT_F64 ? f(double()) : f(float()); }
+
+// `kern` on `grid` workgroups of 256 lanes, the arguments converted to its parameter types (void * to typed pointers, double to real)
+template <typename... P, typename... A>
+hipError_t ps_launch(void (*kern)(P...), int grid, size_t lds, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(PS_THREADS), lds, s, static_cast<P>(args)...);
+  return hipGetLastError();
+}
+
+// a grid-stride kernel over `count` elements (none: nothing to launch)
+template <typename K, typename... A>
+hipError_t ps_pointwise(K kern, int64_t count, hipStream_t s, A... args) {
+  return count ? ps_launch(kern, ps_grid(count), 0, s, args...) : hipSuccess;
+}
 
 hipError_t launch_ps_curl(const void *u, void *out, const void *k0, const void *k1, const void *k2, int64_t n0,
                           int64_t n1, int64_t n2, int precision, hipStream_t s) {
   const int64_t count = n0 * n1 * n2;
-  if (!count) return hipSuccess;
-  if (precision == 8)
-    hipLaunchKernelGGL(ps_curl_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (const cx<double> *)u,
-                       (cx<double> *)out, (const double *)k0, (const double *)k1, (const double *)k2, n1, n2, count);
-  else
-    hipLaunchKernelGGL(ps_curl_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (const cx<float> *)u,
-                       (cx<float> *)out, (const float *)k0, (const float *)k1, (const float *)k2, n1, n2, count);
-  return hipGetLastError();
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(ps_curl_kernel<decltype(r)>, count, s, u, out, k0, k1, k2, n1, n2, count); });
 }
 
 hipError_t launch_ps_cross(const void *a, const void *b, void *out, int64_t count, int precision, hipStream_t s) {
-  if (!count) return hipSuccess;
-  if (precision == 8)
-    hipLaunchKernelGGL(ps_cross_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (const double *)a,
-                       (const double *)b, (double *)out, count);
-  else
-    hipLaunchKernelGGL(ps_cross_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (const float *)a,
-                       (const float *)b, (float *)out, count);
-  return hipGetLastError();
+  return by_precision(precision, [&](auto r) { return ps_pointwise(ps_cross_kernel<decltype(r)>, count, s, a, b, out, count); });
 }
 
 hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void *k1, const void *k2, int64_t n0,
                              int64_t n1, int64_t n2, double nu, int precision, hipStream_t s) {
   const int64_t count = n0 * n1 * n2;
-  if (!count) return hipSuccess;
-  if (precision == 8)
-    hipLaunchKernelGGL(ps_project_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (cx<double> *)du,
-                       (const cx<double> *)u, (const double *)k0, (const double *)k1, (const double *)k2, n1, n2,
-                       count, nu);
-  else
-    hipLaunchKernelGGL(ps_project_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (cx<float> *)du,
-                       (const cx<float> *)u, (const float *)k0, (const float *)k1, (const float *)k2, n1, n2, count,
-                       (float)nu);
-  return hipGetLastError();
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(ps_project_kernel<decltype(r)>, count, s, du, u, k0, k1, k2, n1, n2, count, nu); });
 }
 
 hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
                         int precision, hipStream_t s) {
-  if (!count) return hipSuccess;
-  if (precision == 8)
-    hipLaunchKernelGGL(ps_rk_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (double *)u,
-                       (const double *)u0, (double *)u1, (const double *)du, count, cb, ca);
-  else
-    hipLaunchKernelGGL(ps_rk_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (float *)u, (const float *)u0,
-                       (float *)u1, (const float *)du, count, (float)cb, (float)ca);
-  return hipGetLastError();
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(ps_rk_kernel<decltype(r)>, count, s, u, u0, u1, du, count, cb, ca); });
 }
 
 hipError_t launch_ps_rk_dt(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
                            const double *dt, int precision, hipStream_t s) {
-  if (!count) return hipSuccess;
-  if (precision == 8)
-    hipLaunchKernelGGL(ps_rk_dt_kernel<double>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (double *)u,
-                       (const double *)u0, (double *)u1, (const double *)du, count, cb, ca, dt);
-  else
-    hipLaunchKernelGGL(ps_rk_dt_kernel<float>, dim3(ps_grid(count)), dim3(PS_THREADS), 0, s, (float *)u, (const float *)u0,
-                       (float *)u1, (const float *)du, count, cb, ca, dt);
-  return hipGetLastError();
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(ps_rk_dt_kernel<decltype(r)>, count, s, u, u0, u1, du, count, cb, ca, dt); });
 }
 
 hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, double dt_max, double *dt, hipStream_t s) {
@@ -578,59 +495,14 @@ hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, do
   return hipGetLastError();
 }
 
-int ps_stats_max_comp() { return ST_MAX_COMP; }
-
-size_t ps_stats_scratch_bytes() { return (size_t)SP_MAX_WG * (ST_HEAD + ST_PER_COMP * ST_MAX_COMP) * sizeof(double); }
-
-namespace {
-
-template <typename real, int V>
-void st_launch(int ncomp, int nwg, hipStream_t s, const void *u, int64_t count, int64_t chunk, const st_scale &inv,
-               double *slabs) {
-  const auto kern = ncomp == 1 ? ps_stats_kernel<real, V, 1> : ncomp == 2 ? ps_stats_kernel<real, V, 2>
-                  : ncomp == 3 ? ps_stats_kernel<real, V, 3> : ps_stats_kernel<real, V, 4>;
-  hipLaunchKernelGGL(kern, dim3(nwg), dim3(PS_THREADS), 0, s, (const real *)u, count, chunk, inv, slabs);
-}
-
-}  // namespace
-
-// 1 <= ncomp <= ST_MAX_COMP; `slabs` = ps_stats_scratch_bytes() bytes of stream-ordered scratch
-hipError_t launch_ps_stats(const void *u, int ncomp, int64_t count, const double *inv_dx, double *out, double *slabs,
-                           int precision, hipStream_t s) {
-  // 16-byte loads where every component starts 16-byte aligned, else one scalar per lane (as sp_geometry decides)
-  const int wide = precision == 8 ? 2 : 4;
-  const int V = (count % wide == 0 && (uintptr_t)u % 16 == 0) ? wide : 1;
-  const int64_t step = (int64_t)PS_THREADS * V;
-  int64_t chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
-  chunk = (chunk + step - 1) / step * step;
-  const int nwg = count ? (int)((count + chunk - 1) / chunk) : 0;
-  st_scale inv = {};
-  for (int c = 0; c < ncomp; ++c) inv.v[c] = inv_dx[c];
-  if (nwg) {
-    if (precision == 8 && V == 2) st_launch<double, 2>(ncomp, nwg, s, u, count, chunk, inv, slabs);
-    else if (precision == 8) st_launch<double, 1>(ncomp, nwg, s, u, count, chunk, inv, slabs);
-    else if (V == 4) st_launch<float, 4>(ncomp, nwg, s, u, count, chunk, inv, slabs);
-    else st_launch<float, 1>(ncomp, nwg, s, u, count, chunk, inv, slabs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(st_reduce_kernel, dim3(ST_HEAD + ST_PER_COMP * ncomp), dim3(PS_THREADS), 0, s, slabs, nwg, out);
-  return hipGetLastError();
-}
-
-int ps_spectrum_max_bins() { return SP_MAX_BINS; }
-
-size_t ps_spectrum_scratch_bytes(int nbins) { return (size_t)SP_MAX_WG * 2 * nbins * sizeof(double); }
-
-namespace {
-
-// launch geometry of the shell kernels: V modes per lane, one contiguous chunk of whole steps per workgroup
+// launch geometry of the reductions: V elements per lane and load, one contiguous chunk of whole steps of 256 V per workgroup
 struct sp_geom { int V; int64_t chunk; int nwg; };
 
-// fp32: two modes per 16-B load where every component of every field starts 16-B aligned
-sp_geom sp_geometry(int64_t count, int precision, bool aligned16) {
+// wide = the elements of a 16-byte load (shell kernels: 1 or 2 modes; ps_stats: 2 or 4 reals), taken where they divide
+// `count` and every component of every field that is read starts 16-byte aligned; else one element per lane
+sp_geom sp_geometry(int64_t count, int wide, bool aligned16) {
   sp_geom g;
-  g.V = (precision == 4 && count % 2 == 0 && aligned16) ? 2 : 1;
+  g.V = (count % wide == 0 && aligned16) ? wide : 1;
   const int64_t step = (int64_t)PS_THREADS * g.V;
   g.chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
   g.chunk = (g.chunk + step - 1) / step * step;
@@ -638,68 +510,171 @@ sp_geom sp_geometry(int64_t count, int precision, bool aligned16) {
   return g;
 }
 
+constexpr size_t ST_SCRATCH_BYTES = (size_t)SP_MAX_WG * (ST_HEAD + ST_PER_COMP * ST_MAX_COMP) * sizeof(double);
+
 template <typename real, int V>
-void sp_launch_co(int op, const sp_geom &g, size_t lds, hipStream_t s, const void *a, const void *b, int ncomp, double scale,
-                  const void *k0, const void *k1, const void *k2, const void *w2, int64_t n1, int64_t n2, int64_t count,
-                  double dk, int nbins, double *slabs) {
-  const auto kern = op == SP_HELICITY ? ps_cospectrum_kernel<real, V, SP_HELICITY> : ps_cospectrum_kernel<real, V, SP_DOT>;
-  hipLaunchKernelGGL(kern, dim3(g.nwg), dim3(PS_THREADS), lds, s, (const cx<real> *)a, (const cx<real> *)b, ncomp, scale,
-                     (const real *)k0, (const real *)k1, (const real *)k2, (const real *)w2, (uint32_t)n1, (uint32_t)n2,
-                     count, g.chunk, dk, nbins, slabs);
+auto st_kernel(int ncomp) {
+  return ncomp == 1 ? ps_stats_kernel<real, V, 1> : ncomp == 2 ? ps_stats_kernel<real, V, 2>
+       : ncomp == 3 ? ps_stats_kernel<real, V, 3> : ps_stats_kernel<real, V, 4>;
+}
+
+// 1 <= ncomp <= ST_MAX_COMP; `slabs` = ST_SCRATCH_BYTES of stream-ordered scratch
+hipError_t launch_ps_stats(const void *u, int ncomp, int64_t count, const double *inv_dx, double *out, double *slabs,
+                           int precision, hipStream_t s) {
+  const sp_geom g = sp_geometry(count, 16 / precision, (uintptr_t)u % 16 == 0);
+  st_scale inv = {};
+  for (int c = 0; c < ncomp; ++c) inv.v[c] = inv_dx[c];
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    return ps_launch(g.V == W ? st_kernel<real, W>(ncomp) : st_kernel<real, 1>(ncomp), g.nwg, 0, s, u, count, g.chunk, inv, slabs);
+  });
+  if (e != hipSuccess) return e;
+  return ps_launch(st_reduce_kernel, ST_HEAD + ST_PER_COMP * ncomp, 0, s, slabs, g.nwg, out);
+}
+
+template <typename real, int V>
+auto sp_kernel(int op) {
+  return op == SP_NORM ? ps_shell_kernel<real, V, SP_NORM>
+       : op == SP_HELICITY ? ps_shell_kernel<real, V, SP_HELICITY> : ps_shell_kernel<real, V, SP_DOT>;
+}
+
+// op: SP_NORM / SP_DOT / SP_HELICITY (b is read by SP_DOT alone); `slabs` = SP_MAX_WG x 2 nbins doubles of stream-ordered scratch
+hipError_t launch_ps_shell(const void *a, const void *b, int ncomp, int op, double scale, const void *k0, const void *k1,
+                           const void *k2, const void *w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins,
+                           double *out, double *slabs, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  const bool aligned = (uintptr_t)a % 16 == 0 && (op != SP_DOT || (uintptr_t)b % 16 == 0);
+  const sp_geom g = sp_geometry(count, 8 / precision, aligned);
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(cx<real>);
+    return ps_launch(g.V == W ? sp_kernel<real, W>(op) : sp_kernel<real, 1>(op), g.nwg, (size_t)2 * nbins * sizeof(double), s, a, b,
+                     ncomp, scale, k0, k1, k2, w2, n1, n2, count, g.chunk, dk, nbins, slabs);
+  });
+  if (e != hipSuccess) return e;
+  return ps_launch(ps_spectrum_sum_kernel, (2 * nbins + PS_THREADS - 1) / PS_THREADS, 0, s, slabs, g.nwg, 2 * nbins, out);
+}
+
+// gfft_ps_spectrum and gfft_ps_cospectrum behind their own argument checks (`bad`); fn names the caller in the messages.
+// Arguments first: a bad call is refused without a device, like gfft_plan_create
+int ps_shell(const char *fn, bool bad, const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale,
+             const void *d_k0, const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2,
+             double dk, int nbins, double *d_out, int precision, void *stream) {
+  if (bad || !d_a_hat || !d_k0 || !d_k1 || !d_k2 || !d_out || ncomp < 1 || nbins < 1 || !(dk > 0) || n0 < 0 || n1 < 0 || n2 < 0 ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, std::string(fn) + ": bad argument");
+  static_assert(SP_MAX_BINS == 4096, "the message names the limit");
+  if (nbins > SP_MAX_BINS) return fail(GFFT_ERR_UNSUPPORTED, std::string(fn) + ": more than 4096 bins");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, std::string(fn) + ": axis longer than 2^30");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' partial histograms live in the stream's shared scratch: allocated by the first call, so later
+  // calls -- captured ones included -- allocate nothing
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, (size_t)SP_MAX_WG * 2 * nbins * sizeof(double), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_shell(d_a_hat, d_b_hat, ncomp, op, scale, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk, nbins, d_out,
+                          static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
 }
 
 }  // namespace
 
-hipError_t launch_ps_spectrum(const void *u, int ncomp, const void *k0, const void *k1, const void *k2, const void *w2,
-                              int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *out, double *slabs,
-                              int precision, hipStream_t s) {
-  const int64_t count = n0 * n1 * n2;
-  const sp_geom g = sp_geometry(count, precision, (uintptr_t)u % 16 == 0);
-  const int64_t chunk = g.chunk;
-  const int nwg = g.nwg;
-  const size_t lds = (size_t)2 * nbins * sizeof(double);
-  if (nwg) {
-    if (precision == 8)
-      hipLaunchKernelGGL((ps_spectrum_kernel<double, 1>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<double> *)u, ncomp,
-                         (const double *)k0, (const double *)k1, (const double *)k2, (const double *)w2, (uint32_t)n1,
-                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
-    else if (g.V == 2)
-      hipLaunchKernelGGL((ps_spectrum_kernel<float, 2>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<float> *)u, ncomp,
-                         (const float *)k0, (const float *)k1, (const float *)k2, (const float *)w2, (uint32_t)n1,
-                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
-    else
-      hipLaunchKernelGGL((ps_spectrum_kernel<float, 1>), dim3(nwg), dim3(PS_THREADS), lds, s, (const cx<float> *)u, ncomp,
-                         (const float *)k0, (const float *)k1, (const float *)k2, (const float *)w2, (uint32_t)n1,
-                         (uint32_t)n2, count, chunk, dk, nbins, slabs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ps_spectrum_sum_kernel, dim3((2 * nbins + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, s, slabs,
-                     nwg, 2 * nbins, out);
-  return hipGetLastError();
-}
-
-// op: GFFT_PS_DOT (0) / GFFT_PS_HELICITY (1; b is not read); same slabs and slab sum as the spectrum
-hipError_t launch_ps_cospectrum(const void *a, const void *b, int ncomp, int op, double scale, const void *k0, const void *k1,
-                                const void *k2, const void *w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins,
-                                double *out, double *slabs, int precision, hipStream_t s) {
-  const int64_t count = n0 * n1 * n2;
-  const bool aligned = (uintptr_t)a % 16 == 0 && (op == SP_HELICITY || (uintptr_t)b % 16 == 0);
-  const sp_geom g = sp_geometry(count, precision, aligned);
-  const size_t lds = (size_t)2 * nbins * sizeof(double);
-  if (g.nwg) {
-    if (precision == 8)
-      sp_launch_co<double, 1>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
-    else if (g.V == 2)
-      sp_launch_co<float, 2>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
-    else
-      sp_launch_co<float, 1>(op, g, lds, s, a, b, ncomp, scale, k0, k1, k2, w2, n1, n2, count, dk, nbins, slabs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ps_spectrum_sum_kernel, dim3((2 * nbins + PS_THREADS - 1) / PS_THREADS), dim3(PS_THREADS), 0, s, slabs,
-                     g.nwg, 2 * nbins, out);
-  return hipGetLastError();
-}
-
 }  // namespace gfft
+
+// ---- C ABI (include/gfft.h) --------------------------------------------------------------------------------------------
+using namespace gfft;
+
+extern "C" {
+
+int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
+                 int64_t n0, int64_t n1, int64_t n2, int precision, void *stream) {
+  if (int rc = check_device()) return rc;
+  if (!d_u_hat || !d_out || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || (precision != 4 && precision != 8))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_curl: bad argument");
+  HIP_TRY(launch_ps_curl(d_u_hat, d_out, d_k0, d_k1, d_k2, n0, n1, n2, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream) {
+  if (int rc = check_device()) return rc;
+  if (!d_a || !d_b || !d_out || count < 0 || (precision != 4 && precision != 8))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_cross: bad argument");
+  HIP_TRY(launch_ps_cross(d_a, d_b, d_out, count, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_project(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
+                    int64_t n0, int64_t n1, int64_t n2, double nu, int precision, void *stream) {
+  if (int rc = check_device()) return rc;
+  if (!d_du_hat || !d_u_hat || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || (precision != 4 && precision != 8))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_project: bad argument");
+  HIP_TRY(launch_ps_project(d_du_hat, d_u_hat, d_k0, d_k1, d_k2, n0, n1, n2, nu, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_rk_stage(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb,
+                     double ca, int precision, void *stream) {
+  if (int rc = check_device()) return rc;
+  if ((d_u && !d_u0) || !d_u1 || !d_du || count < 0 || (precision != 4 && precision != 8))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage: bad argument");
+  HIP_TRY(launch_ps_rk(d_u, d_u0, d_u1, d_du, count, cb, ca, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_spectrum(const void *d_u_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                     const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk, int nbins, double *d_out,
+                     int precision, void *stream) {
+  return ps_shell("gfft_ps_spectrum", false, d_u_hat, nullptr, ncomp, SP_NORM, 0.5, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk,
+                  nbins, d_out, precision, stream);
+}
+
+int gfft_ps_cospectrum(const void *d_a_hat, const void *d_b_hat, int ncomp, int op, double scale, const void *d_k0,
+                       const void *d_k1, const void *d_k2, const void *d_w2, int64_t n0, int64_t n1, int64_t n2, double dk,
+                       int nbins, double *d_out, int precision, void *stream) {
+  const bool bad = (op != GFFT_PS_DOT && op != GFFT_PS_HELICITY) || (op == GFFT_PS_DOT && !d_b_hat) ||
+                   (op == GFFT_PS_HELICITY && ncomp != 3) || !std::isfinite(scale);
+  return ps_shell("gfft_ps_cospectrum", bad, d_a_hat, d_b_hat, ncomp, op, scale, d_k0, d_k1, d_k2, d_w2, n0, n1, n2, dk,
+                  nbins, d_out, precision, stream);
+}
+
+int gfft_ps_stats(const void *d_u, int ncomp, int64_t count, const double *inv_dx, double *d_out, int precision,
+                  void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_u || !inv_dx || !d_out || ncomp < 1 || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_stats: bad argument");
+  static_assert(ST_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > ST_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_stats: more than 4 components");
+  for (int c = 0; c < ncomp; ++c)
+    if (!std::isfinite(inv_dx[c]) || inv_dx[c] < 0) return fail(GFFT_ERR_INVALID, "gfft_ps_stats: inv_dx must be finite and >= 0");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' partial results live in the stream's shared scratch: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, ST_SCRATCH_BYTES, &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_stats(d_u, ncomp, count, inv_dx, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_timestep(const double *d_stats, double cfl, double dt_min, double dt_max, double *d_dt, void *stream) {
+  if (!d_stats || !d_dt || !std::isfinite(cfl) || !std::isfinite(dt_min) || !std::isfinite(dt_max) || !(cfl > 0) ||
+      !(dt_min >= 0) || !(dt_min <= dt_max))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_timestep: bad argument");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_timestep(d_stats, cfl, dt_min, dt_max, d_dt, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb, double ca,
+                        const double *d_dt, int precision, void *stream) {
+  if ((d_u && !d_u0) || !d_u1 || !d_du || !d_dt || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_dt: bad argument");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_rk_dt(d_u, d_u0, d_u1, d_du, count, cb, ca, d_dt, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+}  // extern "C"

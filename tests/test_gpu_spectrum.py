@@ -120,6 +120,20 @@ def test_many_shells(dt, nbins):
     fft.destroy()
 
 
+def test_misaligned_fp32_field():
+    """u_hat starts 8 bytes into its allocation: an even mode count, but the kernel must take the 8-byte loads."""
+    from mpi4py_fft_amd import comm
+    shape, dt, m = (24, 16, 20), 'f', 3
+    G, k, w, ref, modes = _reference(shape, dt, m)
+    fft, ops = _ops(comm.COMM_SELF, shape, dt)
+    big = torch.zeros(G.size + 1, dtype=torch.complex64, device='cuda')
+    uh = big[1:].view(G.shape)
+    uh.copy_(torch.as_tensor(np.array(G)))
+    assert uh.is_contiguous() and uh.data_ptr() % 16 == 8 and G[0].size % 2 == 0
+    R.assert_bins(ops.spectrum(uh), ref, modes, 'u_hat off by 8 bytes')
+    fft.destroy()
+
+
 def test_more_shells_than_the_limit_is_an_error():
     from mpi4py_fft_amd import comm, _lib
     shape = (24, 16, 20)
