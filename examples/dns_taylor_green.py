@@ -14,6 +14,11 @@ sum_c |u_c| N_c / L_c from `SpectralOps.timestep` (one read of U, which the step
 `device_dt=True` the step never visits the host: the statistics kernel, `gfft_ps_timestep` and the RK stages that read
 dt from device memory are all enqueued, so the adaptive step replays from a HIP graph too (`graph=True`).
 
+`forcing=(eps, blo, bhi)` keeps the flow from decaying: linear forcing f_hat = g U_hat in shells blo..bhi with the gain
+g = eps / (2 E_band) of `SpectralOps.forcing_gain`, computed once per step from the U_hat the step starts from and held
+over its four stages; the term rides in the projection kernel (`project(..., force=)`), no extra pass.  With
+`device_gain=True` the gain stays in device memory, so the forced step replays from a HIP graph as well.
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -28,7 +33,7 @@ import torch
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
-          transfer=False, stats=None, cfl=None, device_dt=False):
+          transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -37,7 +42,11 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     (`energy(N_hat)`) and 'helicity' (`helicity(U_hat)`).
     cfl: take dt = `SpectralOps.timestep(U, cfl, dt_max=dt)` at every step (fused path) instead of the fixed `dt`;
     device_dt=True keeps that step in device memory (one rank; needed under graph=True).  These paths take the final
-    energy from `SpectralOps.stats`, sum_c S2_c / (2 N^3), and put the simulated 'time' into a dict passed as `stats`."""
+    energy from `SpectralOps.stats`, sum_c S2_c / (2 N^3), and put the simulated 'time' into a dict passed as `stats`.
+    forcing=(eps, blo, bhi) (fused path): every right-hand side adds g U_hat in shells blo..bhi, g = eps / (2 E_band) from
+    `SpectralOps.forcing_gain` of the U_hat at the start of the step; device_gain=True computes it through `out=` and
+    leaves it in device memory (one rank; needed under graph=True).  A dict passed as `stats` receives the last 'gain'
+    and 'band_energy'."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -69,6 +78,8 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         W_hat = newDistArray(FFT, rank=1)                     # i K x u_hat
         UxW = newDistArray(FFT, False, rank=1)                # u x curl u
 
+        force = [None]                                        # project's force= of the current step
+
         def compute_rhs_fused(nu=nu):
             for j in range(3):
                 FFT.backward(U_hat[j], U[j])                  # kernels read U_hat[j], write U[j]
@@ -78,7 +89,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             spectral.cross(U, curl, UxW)
             for j in range(3):
                 FFT.forward(UxW[j], dU[j])
-            ops.project(dU, U_hat, nu)
+            ops.project(dU, U_hat, nu, force=force[0])
 
     def fwd(x, out):      # physical (torch expression) -> spectral slice `out`
         out.copy_(FFT.forward(x).tensor)
@@ -113,11 +124,24 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         sim_time = [0.0]
         if device_dt:
             dt_dev = torch.zeros(2, dtype=torch.float64, device=dev)      # [0] the step, [1] the running time
+    forced = forcing is not None
+    if forced:
+        assert fused and (device_gain or not graph), 'forcing needs the fused path, and device_gain under a graph'
+        f_eps, band = float(forcing[0]), (int(forcing[1]), int(forcing[2]))
+        last_gain = [0.0, 0.0]                                # gain and band energy of the last step
+        if device_gain:
+            gain_dev = torch.zeros(2, dtype=torch.float64, device=dev)    # [0] the gain, [1] the band energy
+            force[0] = (gain_dev, band)
     if dev.type == 'cuda':
         torch.cuda.synchronize()
     t0 = time.time()
     def step():
         h = dt
+        if forced and device_gain:
+            ops.forcing_gain(U_hat, f_eps, band, out=gain_dev)   # enqueued, like the step below
+        elif forced:
+            last_gain[:] = ops.forcing_gain(U_hat, f_eps, band)
+            force[0] = (last_gain[0], band)
         if adaptive and device_dt:
             ops.timestep(U, cfl, dt_max=dt, out=dt_dev)          # enqueued: nothing comes back to the host
         elif adaptive:
@@ -181,6 +205,11 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             stats.update(time=sim_time[0])
     else:
         energy = sum(world.allgather_obj(float((u * u).sum().item()))) / N[0] / N[1] / N[2] / 2
+    if forced:
+        if device_gain:
+            last_gain[:] = gain_dev.cpu().tolist()
+        if stats is not None:
+            stats.update(gain=last_gain[0], band_energy=last_gain[1])
     elapsed = time.time() - t0
     if verbose and world.Get_rank() == 0:
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
@@ -188,6 +217,9 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                  elapsed / nsteps * 1e3, energy))
         if adaptive:
             print('  CFL %g (%s dt): simulated time %.6f in %d steps' % (cfl, 'device' if device_dt else 'host', sim_time[0], nsteps))
+        if forced:
+            print('  forcing shells %d..%d at eps = %g (%s gain): last gain %.6f on band energy %.6f -> injecting %.6f'
+                  % (band + (f_eps, 'device' if device_gain else 'host', last_gain[0], last_gain[1], 2 * last_gain[0] * last_gain[1])))
     if transfer:
         assert fused and not spectrum
         compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term
@@ -232,6 +264,16 @@ if __name__ == '__main__':
         assert round(e - 0.124953117517, 7) == 0, e
         eg = solve(w, verbose=True, graph=True, cfl=0.05, device_dt=True)
         assert eg == ea, (eg, ea)                            # the device-side step is the same arithmetic
+    st = {}
+    ef = solve(w, verbose=True, forcing=(0.1, 3, 3), stats=st)    # forced at the Taylor-Green shell: 0.1 x 10 x 0.01 goes in
+    if w.Get_rank() == 0:
+        print('  forced: energy %.9f against %.9f unforced: injected rate %.4f of eps = 0.1'
+              % (ef, e, (ef - 0.124953117517) / (10 * 0.01)))
+    assert 0.09 <= (ef - 0.124953117517) / (10 * 0.01) <= 0.11 and abs(2 * st['gain'] * st['band_energy'] - 0.1) <= 1e-12, (ef, st)
+    if w.Get_size() == 1:
+        sg = {}
+        eg = solve(w, verbose=True, graph=True, forcing=(0.1, 3, 3), device_gain=True, stats=sg)
+        assert abs(eg - ef) <= 1e-12 and abs(sg['gain'] - st['gain']) <= 1e-12 * st['gain'], (eg, ef, sg, st)
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)

@@ -348,7 +348,24 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    so the result is bit for bit that of gfft_ps_rk_stage(..., cb * dt, ca * dt, ...).  A captured launch
  *                    reads d_dt[0] at every replay: with gfft_ps_stats and gfft_ps_timestep in front of it a whole
  *                    CFL-controlled step replays from one graph.
- *                    All three only enqueue on `stream`: no synchronisation, no allocation after a stream's first call. */
+ *                    All three only enqueue on `stream`: no synchronisation, no allocation after a stream's first call.
+ *   gfft_ps_force_gain   one tiny kernel on the output of gfft_ps_spectrum (d_spec = double[2][nbins]; row 0 is read): the gain
+ *                    of a linear band forcing that injects energy at the rate eps,
+ *                      E_f = d_spec[blo] + d_spec[blo + 1] + ... + d_spec[bhi]      (one thread, in that order)
+ *                      d_gain[0] = min(eps / (2 E_f), gain_max)  where E_f > 0 and finite, else 0;   d_gain[1] = E_f
+ *                    d_gain = double[2] on the device.  GFFT_ERR_INVALID (before a device is touched) for a null pointer,
+ *                    nbins < 1, blo < 0, bhi < blo, bhi >= nbins, eps negative or not finite, gain_max NaN or <= 0
+ *                    (+inf: no clamp).  Only enqueues.
+ *   gfft_ps_project_forced   gfft_ps_project and, AFTER the projection and the viscous term, for every mode whose shell
+ *                    b = floor(sqrt(k0^2 + k1^2 + k2^2) / dk + 0.5) (the expression of gfft_ps_spectrum, in double) satisfies
+ *                    blo <= b <= bhi:  du_hat_c += g * u_hat_c, g = d_gain[0] (read on the device at run time) or, d_gain
+ *                    NULL, `gain`; either is converted to the field's precision once, so the same double gives the same
+ *                    bits both ways.  With g from gfft_ps_force_gain on the spectrum of u_hat the injected power
+ *                    sum w Re(conj(u_hat) . g u_hat) = 2 g E_f is eps.  The term is not projected: it is solenoidal where
+ *                    u_hat is.  One pass over the same arrays as gfft_ps_project; outside the band the result is bit for
+ *                    bit that of gfft_ps_project.  A captured launch follows whatever d_gain[0] holds at each replay.
+ *                    GFFT_ERR_INVALID (before a device is touched) as gfft_ps_project and for dk <= 0, blo < 0, bhi < blo,
+ *                    a non-finite `gain` with d_gain NULL; n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
@@ -369,6 +386,11 @@ int gfft_ps_stats(const void *d_u, int ncomp, int64_t count, const double *inv_d
 int gfft_ps_timestep(const double *d_stats, double cfl, double dt_min, double dt_max, double *d_dt /* [2] */, void *stream);
 int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int64_t count, double cb, double ca,
                         const double *d_dt, int precision, void *stream);
+int gfft_ps_force_gain(const double *d_spec, int nbins, int blo, int bhi, double eps, double gain_max,
+                       double *d_gain /* [2] */, void *stream);
+int gfft_ps_project_forced(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
+                           int64_t n0, int64_t n1, int64_t n2, double nu, double dk, int blo, int bhi,
+                           double gain, const double *d_gain /* NULL: use `gain` */, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

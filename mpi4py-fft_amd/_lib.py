@@ -82,6 +82,9 @@ def _declare(lib):
         'gfft_ps_stats': (c.c_int, [vp, c.c_int, c.c_int64, c.POINTER(c.c_double), vp, c.c_int, vp]),
         'gfft_ps_timestep': (c.c_int, [vp, c.c_double, c.c_double, c.c_double, vp, vp]),
         'gfft_ps_rk_stage_dt': (c.c_int, [vp, vp, vp, vp, c.c_int64, c.c_double, c.c_double, vp, c.c_int, vp]),
+        'gfft_ps_force_gain': (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, vp, vp]),
+        'gfft_ps_project_forced': (c.c_int, [vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_double,
+                                             c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -444,6 +447,25 @@ class HipEngine:
         check(lib().gfft_ps_rk_stage_dt(None if tu is None else tu.data_ptr(), None if tu0 is None else tu0.data_ptr(),
                                         tu1.data_ptr(), tdu.data_ptr(), count, float(cb), float(ca), tdt.data_ptr(),
                                         precision, current_stream()))
+
+    def ps_force_gain(self, tspec, nbins, blo, bhi, eps, gain_max, tgain):
+        """gfft_ps_force_gain: tspec = double[2][nbins] as ps_spectrum writes it; tgain = double[2] on the device:
+        [0] = min(eps / (2 E_f), gain_max), [1] = E_f, the energy of shells blo..bhi."""
+        self.require_device(tspec)
+        self.require_device(tgain)
+        check(lib().gfft_ps_force_gain(tspec.data_ptr(), int(nbins), int(blo), int(bhi), float(eps), float(gain_max),
+                                       tgain.data_ptr(), current_stream()))
+
+    def ps_project_forced(self, tdu, tu, k, shape, nu, dk, blo, bhi, gain, tgain, precision):
+        """gfft_ps_project_forced: ps_project, then du += g u in shells blo..bhi; g = tgain[0] (device double) or, tgain
+        None, the float `gain`."""
+        self.require_device(tdu)
+        if tgain is not None:
+            self.require_device(tgain)
+        check(lib().gfft_ps_project_forced(tdu.data_ptr(), tu.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                           shape[0], shape[1], shape[2], float(nu), float(dk), int(blo), int(bhi),
+                                           float(gain), None if tgain is None else tgain.data_ptr(), precision,
+                                           current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

@@ -1,8 +1,8 @@
 // The pseudo-spectral layer either side of the transform path: the gfft_ps_* entry points of include/gfft.h (at the end of
 // the file), their launchers and their kernels, each one pass over its operands.
 //   * pointwise (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one temporary per
-//     operator): i K x u_hat, u x w, pressure projection + viscous term, the Runge-Kutta stage update and the time-step
-//     controller.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
+//     operator): i K x u_hat, u x w, pressure projection + viscous term (with a band forcing fused in where asked for),
+//     the Runge-Kutta stage update, the time-step controller and the forcing gain.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
 //     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity) and physical-space statistics (ps_stats_kernel).
@@ -10,6 +10,7 @@
 #include "gfft_internal.h"
 
 #include <cmath>
+#include <limits>
 
 namespace gfft {
 
@@ -55,12 +56,68 @@ ps_cross_kernel(const real *__restrict__ a, const real *__restrict__ b, real *__
   }
 }
 
-// p = sum_i du_i k_i / |k|^2 (|k|^2 = 0 -> 1);  du_j -= k_j p;  du_j -= nu |k|^2 u_j
+// The shell of a mode: b = floor(|k| / dk + 0.5), in double from wavenumbers converted to double first (k2sq = |k|^2).  The
+// ONE definition: ps_shell_kernel bins by it and the forced ps_project_kernel forces by it, so the band that is forced is
+// the band whose energy the spectrum reports.  Integer-valued, or NaN for a NaN wavenumber (which compares false everywhere).
+__device__ __forceinline__ double ps_shell_of(double kx, double ky, double kz, double dk, double &k2sq) {
+  k2sq = (kx * kx + ky * ky) + kz * kz;
+  return floor(sqrt(k2sq) / dk + 0.5);
+}
+
+// What ps_project_kernel does to a mode after the projection and the viscous term.  A launch passes an argument pack `A`
+// by value; arg.bind<real>() turns it, once per lane and before the loop, into the functor applied to every mode.
+// gfft_ps_project: nothing.
+struct ps_no_force {
+  template <typename real> __device__ __forceinline__ ps_no_force bind() const { return *this; }
+  template <typename real>
+  __device__ __forceinline__ void operator()(real, real, real, real, const cx<real> &, const cx<real> &, const cx<real> &,
+                                             cx<real> &, cx<real> &, cx<real> &) const {}
+};
+
+// gfft_ps_project_forced: du_c += g u_c for the modes whose shell lies in [blo, bhi].  The exact shell costs an fp64 square
+// root and an fp64 divide; it is evaluated only where |k|^2 -- the `kk` the projection has already formed, in the field's
+// precision -- lies in [lo2, hi2], bounds the host computes once (ps_band_bounds) so that no mode of the band fails them.
+// Everywhere else the test is two compares, and the mode leaves exactly as gfft_ps_project leaves it.
 template <typename real>
+struct ps_band_force {
+  real g, lo2, hi2;
+  double dk, blo, bhi;
+  __device__ __forceinline__ void operator()(real kx, real ky, real kz, real kk, const cx<real> &u0, const cx<real> &u1,
+                                             const cx<real> &u2, cx<real> &d0, cx<real> &d1, cx<real> &d2) const {
+    if (kk >= lo2 && kk <= hi2) {
+      double k2sq;
+      const double sh = ps_shell_of((double)kx, (double)ky, (double)kz, dk, k2sq);
+      if (sh >= blo && sh <= bhi) {
+        d0.x += g * u0.x; d0.y += g * u0.y;
+        d1.x += g * u1.x; d1.y += g * u1.y;
+        d2.x += g * u2.x; d2.y += g * u2.y;
+      }
+    }
+  }
+};
+
+// g = (real)gain[0] where `gain` is given (read when the kernel runs: a captured launch follows what ps_force_gain_kernel
+// wrote in front of it), else (real)gain_val -- the one conversion either way, so the same double gives the same bits.
+// lo2 / hi2 arrive as doubles already representable in `real` (ps_band_bounds rounds them outwards).
+struct ps_band_args {
+  double dk;
+  int blo, bhi;
+  double lo2, hi2, gain_val;
+  const double *gain;
+  template <typename real> __device__ __forceinline__ ps_band_force<real> bind() const {
+    return {(real)(gain ? gain[0] : gain_val), (real)lo2, (real)hi2, dk, (double)blo, (double)bhi};
+  }
+};
+
+// p = sum_i du_i k_i / |k|^2 (|k|^2 = 0 -> 1);  du_j -= k_j p;  du_j -= nu |k|^2 u_j;  then the mode's forcing, if any (A).
+// One pass over nine component arrays either way: pointwise, grid-stride, no LDS, no atomics.
+// (Registers: in the list above ps_stats_kernel.)
+template <typename real, typename A>
 __global__ void __launch_bounds__(PS_THREADS)
 ps_project_kernel(cx<real> *__restrict__ du, const cx<real> *__restrict__ u, const real *__restrict__ k0,
                   const real *__restrict__ k1, const real *__restrict__ k2, int64_t n1, int64_t n2,
-                  int64_t count, real nu) {
+                  int64_t count, real nu, A arg) {
+  const auto force = arg.template bind<real>();
   for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * PS_THREADS) {
     const int64_t row = e / n2;
     const real kz = k2[e - row * n2];
@@ -79,6 +136,7 @@ ps_project_kernel(cx<real> *__restrict__ du, const cx<real> *__restrict__ u, con
     d0.x -= v * u0.x; d0.y -= v * u0.y;
     d1.x -= v * u1.x; d1.y -= v * u1.y;
     d2.x -= v * u2.x; d2.y -= v * u2.y;
+    force(kx, ky, kz, kk, u0, u1, u2, d0, d1, d2);
     du[e] = d0;
     du[e + count] = d1;
     du[e + 2 * count] = d2;
@@ -124,6 +182,17 @@ __global__ void ps_timestep_kernel(const double *__restrict__ stats, double cfl,
   const double h = fmin(fmax(want, dt_min), dt_max);
   dt[0] = h;
   dt[1] += h;
+}
+
+// E_f = spec[blo] + ... + spec[bhi] (row 0 of gfft_ps_spectrum's bins), added serially in that order;
+// gain[0] = min(eps / (2 E_f), gain_max) (0 where E_f is zero, negative or not finite); gain[1] = E_f
+__global__ void ps_force_gain_kernel(const double *__restrict__ spec, int blo, int bhi, double eps, double gain_max,
+                                     double *__restrict__ gain) {
+  if (blockIdx.x || threadIdx.x) return;
+  double ef = 0.0;
+  for (int b = blo; b <= bhi; ++b) ef += spec[b];
+  gain[0] = (ef > 0.0 && isfinite(ef)) ? fmin(eps / (2.0 * ef), gain_max) : 0.0;
+  gain[1] = ef;
 }
 
 // ---- shell sums: a per-mode value c and |k|^2 c binned by |k|, one read of each field ----------------------------------
@@ -277,9 +346,9 @@ ps_shell_kernel(const cx<real> *__restrict__ fa, const cx<real> *__restrict__ fb
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const double kx = k0[i0], ky = k1[i1], kz = k2[i2];
-        const double k2sq = (kx * kx + ky * ky) + kz * kz;
+        double k2sq;
+        const double sh = ps_shell_of(kx, ky, kz, dk, k2sq);
         const double w = w2 ? (double)w2[i2] : 1.0;
-        const double sh = floor(sqrt(k2sq) / dk + 0.5);
         b[j] = sh < (double)nbins ? (int)sh : -1;       // (a NaN wavenumber drops the mode too)
         if constexpr (OP == SP_HELICITY) {
           const double x0 = h0.m[j].x, x1 = h1.m[j].x, x2 = h2.m[j].x;              // Re a
@@ -345,7 +414,8 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // Cost per value beside its bytes: a conversion and 11 fp64 operations; no divide, no square root, no LDS in the loop.
 // Registers (hipcc -O3, gfx950; no instantiation spills or uses scratch): ps_stats_kernel<double, 2, 3> 70 VGPRs,
 // <float, 4, 3> 70, <double, 2, 4> 90, <float, 4, 4> 98 (the largest), <double, 1, 3> 62, <float, 1, 3> 58;
-// st_reduce_kernel 12, ps_rk_dt_kernel 14 / 10 (double / float), ps_timestep_kernel 13.
+// st_reduce_kernel 12, ps_rk_dt_kernel 14 / 10 (double / float), ps_timestep_kernel 13;
+// ps_project_kernel<double / float, ps_band_args> (the forced projection) 64 / 50 against 58 / 42 unforced, ps_force_gain_kernel 12.
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -475,7 +545,47 @@ hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void
                              int64_t n1, int64_t n2, double nu, int precision, hipStream_t s) {
   const int64_t count = n0 * n1 * n2;
   return by_precision(
-      precision, [&](auto r) { return ps_pointwise(ps_project_kernel<decltype(r)>, count, s, du, u, k0, k1, k2, n1, n2, count, nu); });
+      precision, [&](auto r) { return ps_pointwise(ps_project_kernel<decltype(r), ps_no_force>, count, s, du, u, k0, k1, k2, n1, n2, count, nu, ps_no_force()); });
+}
+
+// The pre-filter of ps_band_force: lo2 <= kk <= hi2 for every mode whose exact shell lies in [blo, bhi], kk being |k|^2 as
+// ps_project_kernel forms it in the field's precision.  In real numbers the band is (blo - 1/2) dk <= |k| < (bhi + 1/2) dk.
+// Against that, relative to |k|^2:
+//   * the exact test's own double arithmetic (three squares, two adds, sqrt, divide, + 0.5) moves its edges by < 8 x 2^-53;
+//   * kk (three products and two adds of non-negative terms, contracted or not) is off by < 3 ulp of `real`: 3 eps;
+//   * the squares formed here in double: < 4 x 2^-53.
+// Both bounds are widened by 16 eps (eps = 2^-23 or 2^-52: more than four times the sum above) and then rounded OUTWARDS
+// to `real`, so the conversion in the kernel is exact.  Below 16 x the smallest normal number kk may have lost bits to
+// underflow: the lower bound gives way to 0 there.  An overflowing upper bound is +inf.  (An overflowing or NaN kk fails
+// the pre-filter; its mode lies beyond every finite hi2, or has a NaN shell.)
+struct ps_band { double lo2, hi2; };
+
+template <typename real>
+ps_band ps_band_bounds(double dk, int blo, int bhi) {
+  const double m = 16.0 * (double)std::numeric_limits<real>::epsilon();
+  const double lo = blo > 0 ? ((double)blo - 0.5) * dk : 0.0, hi = ((double)bhi + 0.5) * dk;
+  double lo2 = lo * lo * (1.0 - m), hi2 = hi * hi * (1.0 + m);
+  if (!(lo2 >= 16.0 * (double)std::numeric_limits<real>::min())) lo2 = 0.0;
+  real l = (real)lo2, h = (real)hi2;
+  if ((double)l > lo2) l = std::nextafter(l, (real)0);
+  if ((double)h < hi2) h = std::nextafter(h, std::numeric_limits<real>::infinity());
+  return {(double)l, (double)h};
+}
+
+hipError_t launch_ps_project_forced(void *du, const void *u, const void *k0, const void *k1, const void *k2, int64_t n0,
+                                    int64_t n1, int64_t n2, double nu, double dk, int blo, int bhi, double gain,
+                                    const double *d_gain, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  return by_precision(precision, [&](auto r) {
+    const ps_band b = ps_band_bounds<decltype(r)>(dk, blo, bhi);
+    return ps_pointwise(ps_project_kernel<decltype(r), ps_band_args>, count, s, du, u, k0, k1, k2, n1, n2, count, nu,
+                        ps_band_args{dk, blo, bhi, b.lo2, b.hi2, gain, d_gain});
+  });
+}
+
+hipError_t launch_ps_force_gain(const double *spec, int blo, int bhi, double eps, double gain_max, double *gain, hipStream_t s) {
+  hipLaunchKernelGGL(ps_force_gain_kernel, dim3(1), dim3(64), 0, s, spec, blo, bhi, eps, gain_max, gain);
+  return hipGetLastError();
 }
 
 hipError_t launch_ps_rk(void *u, const void *u0, void *u1, const void *du, int64_t count, double cb, double ca,
@@ -674,6 +784,31 @@ int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_d
     return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_dt: bad argument");
   if (int rc = check_device()) return rc;
   HIP_TRY(launch_ps_rk_dt(d_u, d_u0, d_u1, d_du, count, cb, ca, d_dt, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_force_gain(const double *d_spec, int nbins, int blo, int bhi, double eps, double gain_max, double *d_gain,
+                       void *stream) {
+  if (!d_spec || !d_gain || nbins < 1 || blo < 0 || bhi < blo || bhi >= nbins || !std::isfinite(eps) || !(eps >= 0) ||
+      !(gain_max > 0))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_force_gain: bad argument");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_force_gain(d_spec, blo, bhi, eps, gain_max, d_gain, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_project_forced(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
+                           int64_t n0, int64_t n1, int64_t n2, double nu, double dk, int blo, int bhi, double gain,
+                           const double *d_gain, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_du_hat || !d_u_hat || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || !(dk > 0) || blo < 0 || bhi < blo ||
+      (!d_gain && !std::isfinite(gain)) || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_project_forced: bad argument");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_project_forced: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_project_forced(d_du_hat, d_u_hat, d_k0, d_k1, d_k2, n0, n1, n2, nu, dk, blo, bhi, gain, d_gain, precision,
+                                   (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -26,6 +26,14 @@ and the physical-space side of the same diagnostics, one read of a real field, b
                                 the step never leaves the device and rk_stage(..., dt=) reads it there, so a
                                 CFL-controlled RK4 step can be captured into one HIP graph
 
+and the term that keeps a flow from decaying, so that all of the above have a stationary state to describe:
+
+    forcing_gain(u_hat, eps, band)   g = min(eps / (2 E_f), gain_max) with E_f the energy in shells blo..bhi (a partial sum of
+                                `spectrum`): the gain of the linear band forcing f_hat = g u_hat that injects energy at the
+                                rate eps; with out= a device double[2] it never leaves the device
+    project(du_hat, u_hat, nu, force=(g, band))   the projection with du_hat += g u_hat in the band fused in behind it: no
+                                extra pass; g a float or that device tensor, so a forced step replays from one HIP graph
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -92,6 +100,7 @@ class SpectralOps:
         self.pshape = tuple(int(n) for n in fft.shape(False))
         self.inv_dx = [float(n) / float(l) for n, l in zip(fft.global_shape(), np.full(3, 2 * np.pi) if L is None else np.asarray(L, dtype=float))]
         self._stats_dev = None
+        self._force_spec = None
 
     def _same_precision(self, precision):
         # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
@@ -104,12 +113,58 @@ class SpectralOps:
         _lib.engine().ps_curl(_t(u_hat), _t(out), self.K, self.shape, _prec(u_hat))
         return out
 
-    def project(self, du_hat, u_hat, nu):
-        """In place: pressure projection and viscous term of the Navier-Stokes right-hand side."""
+    def project(self, du_hat, u_hat, nu, force=None):
+        """In place: pressure projection and viscous term of the Navier-Stokes right-hand side.
+        force=(gain, (blo, bhi)) or (gain, (blo, bhi), dk): the same pass then adds gain * u_hat to du_hat in every mode
+        whose shell floor(|k| / dk + 1/2) (the shells of `spectrum`; dk defaults as there) lies in blo..bhi -- linear band
+        forcing, after the projection and the viscous term, not projected (solenoidal where u_hat is).  gain is a float
+        or a device double tensor (contiguous, at least one element: `forcing_gain(out=)` writes one) whose element 0 the
+        kernel reads when it runs; both are rounded to the field's precision once and give the same bits.  Outside the
+        band the result is bit for bit that of force=None."""
         assert tuple(du_hat.shape) == (3,) + self.shape == tuple(u_hat.shape)
         self._same_precision(_prec(du_hat))
-        _lib.engine().ps_project(_t(du_hat), _t(u_hat), self.K, self.shape, nu, _prec(du_hat))
+        if force is None:
+            _lib.engine().ps_project(_t(du_hat), _t(u_hat), self.K, self.shape, nu, _prec(du_hat))
+            return du_hat
+        assert len(force) in (2, 3), 'force = (gain, (blo, bhi)) or (gain, (blo, bhi), dk)'
+        gain, (blo, bhi) = force[0], force[1]
+        dk = self.dk if len(force) == 2 or force[2] is None else float(force[2])
+        assert dk > 0 and 0 <= int(blo) <= int(bhi)
+        tgain = None
+        if isinstance(gain, (torch.Tensor, DeviceArray)):
+            tgain, gain = _t(gain), 0.0
+            assert tgain.dtype == torch.float64 and tgain.numel() >= 1 and tgain.is_contiguous()
+        else:
+            assert np.isfinite(gain), gain
+        _lib.engine().ps_project_forced(_t(du_hat), _t(u_hat), self.K, self.shape, nu, dk, int(blo), int(bhi), float(gain),
+                                        tgain, _prec(du_hat))
         return du_hat
+
+    def forcing_gain(self, u_hat, eps, band, gain_max=np.inf, dk=None, out=None):
+        """The gain g of the band forcing f_hat = g u_hat (`project(..., force=(g, band))`) that injects energy at the rate
+        eps: g = min(eps / (2 E_f), gain_max) with E_f = sum of E(k) over shells band = (blo, bhi) of `spectrum(u_hat)`,
+        0 where E_f is zero or not finite; the injected power sum w Re(conj(u_hat) . g u_hat) = 2 g E_f is eps unless
+        the clamp binds.
+        out=None: on any grid, from the rank-reduced `spectrum(u_hat, nbins=bhi + 1, dk=dk)` (every rank holds the same
+        bits) and `force_gain`; synchronises and returns (gain, E_f) as Python floats.
+        out = a device double[2] tensor: one-rank grids only (no device-side reduction over ranks); enqueues the spectrum
+        into a tensor this object keeps and then `gfft_ps_force_gain`, which writes the gain to out[0] and E_f to out[1];
+        returns `out`.  Nothing synchronises or, after the first call with a band, allocates, so the call can be captured
+        with the `project(..., force=(out, band))` calls that read the gain."""
+        blo, bhi = int(band[0]), int(band[1])
+        eps, gain_max = float(eps), float(gain_max)
+        assert 0 <= blo <= bhi and np.isfinite(eps) and eps >= 0 and gain_max > 0
+        if out is None:
+            E = self.spectrum(u_hat, nbins=bhi + 1, dk=dk)
+            return force_gain(E, (blo, bhi), eps, gain_max)
+        assert not self.comms, 'the device path of forcing_gain needs a one-rank grid'
+        assert tuple(out.shape) == (2,) and out.dtype == torch.float64 and out.is_contiguous()
+        t = _t(u_hat)
+        if self._force_spec is None or self._force_spec.device != t.device or self._force_spec.shape[1] != bhi + 1:
+            self._force_spec = torch.empty((2, bhi + 1), dtype=torch.float64, device=t.device)
+        self.spectrum(t, nbins=bhi + 1, dk=dk, out=self._force_spec, reduce=False)
+        _lib.engine().ps_force_gain(self._force_spec, bhi + 1, blo, bhi, eps, gain_max, out)
+        return out
 
     def default_nbins(self, dk=None):
         """Shells of width dk that hold every mode: floor(kmax / dk + 1/2) + 1 with the global largest |k|."""
@@ -305,6 +360,24 @@ def timestep_from_rate(rate, cfl, dt_max, dt_min=0.0):
     rate = float(rate)
     want = cfl / rate if (rate > 0 and np.isfinite(rate)) else dt_max
     return float(min(max(want, dt_min), dt_max))
+
+
+def force_gain(E, band, eps, gain_max=np.inf):
+    """The formula of `SpectralOps.forcing_gain` and gfft_ps_force_gain on host numbers, the same arithmetic in the same
+    order: E_f = E[0][blo] + ... + E[0][bhi] added serially (E: [2][nbins] as `spectrum` returns it, or its row 0), gain =
+    min(eps / (2 E_f), gain_max), 0 for an E_f that is zero, negative, infinite or NaN.  Returns (gain, E_f)."""
+    E = np.asarray(E, dtype=np.float64)
+    row = E[0] if E.ndim == 2 else E
+    blo, bhi = int(band[0]), int(band[1])
+    assert 0 <= blo <= bhi < len(row)
+    ef = np.float64(0.0)
+    for b in range(blo, bhi + 1):
+        ef = ef + row[b]
+    if not (ef > 0 and np.isfinite(ef)):
+        return 0.0, float(ef)
+    with np.errstate(over='ignore'):
+        want = np.float64(eps) / (2.0 * ef)
+    return float(min(want, np.float64(gain_max))), float(ef)
 
 
 def moments(stats, npoints):
