@@ -82,7 +82,8 @@ int gfft_device_name(int device, char *buf, size_t len);
  * pairs, 2: real fp32 pairs too), "fuse2_n512" (the n = 512 pairs: 0 off, 1 on 16 lines per tile, 2 [strided -> rows] on 32), "fuse2_mixed" (pairs on planes of 512 x 1024 / 1024 x 512 points), "fuse2_f32_n512" (the complex64 n = 512 pairs), "fuse2_wait_ms" (wall-clock limit of a wait inside a fused
  * launch before the launch voids itself, gfft_async_error below; default 2000); GFFT_FUSE2_DEBUG=1 prints a fused
  * launch's counters.  ("debug_tw_index" / "debug_tw_exp": TEST HOOK -- twiddle tables uploaded while debug_tw_exp > 0
- * carry one entry off by 10^-debug_tw_exp: what the rounding-level guards of tests/ must catch.) */
+ * carry one entry off by 10^-debug_tw_exp: what the rounding-level guards of tests/ must catch; "debug_tw_len" != 0 confines
+ * it to tables of exactly that length -- a packed-real plan's Hermitian table rtw(n) and not its tw(n / 2).) */
 int gfft_set_option(const char *key, int value);
 
 /* ---- serial multi-axis transform plan ------------------------------------------------

@@ -90,7 +90,8 @@ struct Options {
   // TEST HOOK (tests/test_gpu_rounding_guard.py): twiddle tables uploaded while debug_tw_exp > 0 carry ONE wrong entry --
   // the real part of entry debug_tw_index (mod n) is off by 10^-debug_tw_exp -- under their own cache key, so that plans made
   // before / after are untouched.  What the rounding-level guards of the test suite must catch; never set by the product.
-  int debug_tw_index = 1, debug_tw_exp = 0;
+  // debug_tw_len != 0: only the table of exactly that length (a packed-real plan's rtw(n), say, and not its tw(n/2)).
+  int debug_tw_index = 1, debug_tw_exp = 0, debug_tw_len = 0;
   Options() {
     if (const char *s = getenv("GFFT_GRID_CAP")) grid_cap = atoi(s);
     if (const char *s = getenv("GFFT_VARIANT_ROWS")) variant_rows = atoi(s);
@@ -155,7 +156,7 @@ int upload_twiddles(int64_t n, int64_t step, int64_t count, int precision, void 
 
 int get_twiddles(int64_t n, int precision, const void **out) {
   std::lock_guard<std::mutex> lock(g_tw_mutex);
-  const int e = opts().debug_tw_exp;
+  const int e = (opts().debug_tw_len == 0 || opts().debug_tw_len == n) ? opts().debug_tw_exp : 0;
   const int64_t wrong = e > 0 ? ((int64_t)opts().debug_tw_index % n + n) % n : -1;
   auto key = std::make_tuple(n, dev_prec(precision), e > 0 ? (int)(wrong * 64 + (e & 63)) + 1 : 0);
   auto it = g_tw_cache.find(key);
@@ -1943,6 +1944,7 @@ int gfft_set_option(const char *key, int value) {
   else if (!strcmp(key, "profile")) opts().profile = value;
   else if (!strcmp(key, "debug_tw_index")) opts().debug_tw_index = value;
   else if (!strcmp(key, "debug_tw_exp")) opts().debug_tw_exp = value;
+  else if (!strcmp(key, "debug_tw_len")) opts().debug_tw_len = value;
   else if (!strcmp(key, "xcd_swizzle")) opts().xcd_swizzle = value;
   else if (!strcmp(key, "tile_order")) opts().tile_order = value;
   else if (!strcmp(key, "fused3_min_mib")) opts().fused3_min_bytes = (int64_t)value << 20;

@@ -299,3 +299,116 @@ def impulse_errors(n, dt, strided, positions=None, lines=16):
     eb = float(np.abs(back - x).max())
     fft.destroy()
     return ef, eb
+
+
+# real lengths by the kernel family that runs their ROWS (plan.cpp plan_line: real_half_ok, regk_ok, generic_max_n)
+REAL_LENGTHS = {'packed': [32, 64, 512, 2048, 8192, 96, 1536, 40, 1000, 8000, 224, 480],      # 2^k; 3^b 2^k; 5^c 2^k; twice 112, 240
+                'regs': [16, 48],                        # halves 8 and 24 have no packed kernel: full-length register kernels
+                'generic': [7, 9, 15, 121, 343, 1331, 22, 34],
+                'embedded': [9216, 16384],               # real-as-complex
+                'bluestein': [521, 1009]}
+REAL_ROWS = [(n, path) for path, ns in REAL_LENGTHS.items() for n in ns]
+
+
+def real_impulse_errors(n, dt, strided, lines=16, describe=None):
+    """`impulse_errors` for ONE real plan of length n (r2c forward, c2r backward): the packed-real plans read a second
+    table, rtw(n), in their Hermitian pass, and the full-length, generic and embedded real lines go through load / store
+    adapters of their own -- none of which a complex plan builds.
+    Forward: line b holds a unit impulse at j_b, X_b[k] = exp(-2 pi i j_b k / n), k = 0 ... n // 2.
+    Backward, unnormalised: line b holds ONE non-zero bin k_b of amplitude a_b -- each of 0, 1, 2, 3, n // 4, n // 3 + 1,
+    n // 2 - 1, n // 2 once with a = 1 and once with a = i --, x_j = 2 Re(a e^{2 pi i j k / n}) for an interior bin,
+    Re(a) at k = 0 and Re(a) (-1)^j at the Nyquist bin of an even n: a = i there must give zeros.
+    Returns (max |forward - exact|, max |backward - exact| / 2): both in units of the exact answer's peak.  `describe`,
+    a list, receives gfft_plan_describe of the two plans."""
+    from mpi4py_fft_amd import FFT, asdevice
+    rdt = 'd' if dt in 'dD' else 'f'
+    cdt = rdt.upper()
+    h = n // 2 + 1
+    positions = [1, 2, 3, 5, 7, n // 2 + 1, n - 1, n // 3 + 1, n // 4 + 1, 11 % n, n // 5 + 2, n // 7 + 3, 1, n - 2, 13 % n, n // 2 - 1]
+    positions = [int(j) % n for j in positions][:lines]
+    bins = [0, 1, 2, 3, n // 4, n // 3 + 1, n // 2 - 1, n // 2]
+    assert all(0 <= k < h for k in bins), (n, bins)
+    spikes = ([(k, 1.0) for k in bins] + [(k, 1j) for k in bins])[:lines]
+    B = len(positions)
+    assert len(spikes) == B
+    shape, axis = ((n, B), 0) if strided else ((B, n), 1)
+    hshape = (h, B) if strided else (B, h)
+    x = np.zeros(shape, dtype=rdt)
+    want = np.empty(hshape, dtype='D')
+    spec = np.zeros(hshape, dtype=cdt)
+    wantb = np.empty(shape, dtype='d')
+    k = np.arange(h)
+    j = np.arange(n)
+    for b, (jb, (kb, a)) in enumerate(zip(positions, spikes)):
+        col = np.exp(-2j * np.pi * ((jb * k) % n) / n)
+        edge = kb == 0 or 2 * kb == n
+        back = (1.0 if edge else 2.0) * (a * np.exp(2j * np.pi * ((j * kb) % n) / n)).real
+        if strided:
+            x[jb, b], want[:, b], spec[kb, b], wantb[:, b] = 1, col, a, back
+        else:
+            x[b, jb], want[b], spec[b, kb], wantb[b] = 1, col, a, back
+    fft = FFT(shape, (axis,), dtype=rdt)
+    if describe is not None:
+        describe.extend(p._eng.plan_describe(p._plan) for p in (fft.fwd, fft.bck))
+    got = np.asarray(fft.forward(asdevice(x), normalize=False)).astype('D')
+    ef = float(np.abs(got - want).max())
+    back = np.asarray(fft.backward(asdevice(spec), normalize=False)).astype('d')
+    eb = float(np.abs(back - wantb).max()) / 2.0
+    fft.destroy()
+    return ef, eb
+
+
+def real_path(describe):
+    """Which kernel family ran a serial real plan, from gfft_plan_describe's text."""
+    text = '\n'.join(describe)
+    if 'multiply by B' in text:
+        return 'bluestein'
+    if 'embed' in text:
+        return 'embedded'
+    if 'packed-real' in text:
+        return 'packed'
+    if 'kernel=generic' in text:
+        return 'generic'
+    assert 'kernel=regs-' in text, text
+    return 'regs'
+
+
+def dirty_spectrum(shape, dt, seed):
+    """A seeded complex Gaussian half-spectrum that is NOT Hermitian-clean: the DC and Nyquist entries keep their O(1)
+    imaginary parts, as a spectrum does after a nonlinear term."""
+    return O.rng_array(shape, np.dtype(dt).char.upper(), seed)
+
+
+def clean_edges(c, n, axis=-1):
+    """`c` with the imaginary parts a c2r of real length n along `axis` ignores set to zero: DC, and Nyquist for an even n."""
+    c = c.copy()
+    ix = [slice(None)] * c.ndim
+    for kk in ([0, n // 2] if n % 2 == 0 else [0]):
+        ix[axis] = kk
+        c[tuple(ix)] = c[tuple(ix)].real
+    return c
+
+
+def check_pfft_backward_vs_oracle(P, shape, dt, seed=11, **kw):
+    """PFFT.backward on P ranks of a global half-spectrum that is not Hermitian-clean (`dirty_spectrum`) against the
+    float64 oracle on the same spectrum widened to complex128 -- whatever `dt`: numpy runs irfft of complex64 in single
+    precision, so only the 'd' oracle is a high-precision reference."""
+    from mpi4py_fft_amd import PFFT, newDistArray
+    okw = {k: (list(v) if isinstance(v, list) else v) for k, v in kw.items()}
+    offt = O.OPFFT(P, shape, dtype='d', **okw)
+    G = dirty_spectrum(offt.output_shape, dt, seed)
+    ref = offt.backward(offt.scatter(G.astype('D'), forward_output=True))
+    nelem = int(np.prod(offt.input_shape))
+
+    def body(comm):
+        k = {a: (list(b) if isinstance(b, list) else b) for a, b in kw.items()}
+        fft = PFFT(comm, shape, dtype=dt, **k)
+        uh = newDistArray(fft, True)
+        uh[...] = G[fft.local_slice(True)]
+        back = np.asarray(fft.backward(uh)).copy()
+        fft.destroy()
+        return back
+
+    for r, back in enumerate(run_ranks(P, body)):
+        assert back.shape == ref[r].shape and back.dtype == np.dtype(dt), (back.shape, ref[r].shape, back.dtype)
+        assert_close(back.astype('d'), ref[r], dt, nelem, (P, shape, dt, kw, r))
