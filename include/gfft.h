@@ -366,7 +366,29 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    u_hat is.  One pass over the same arrays as gfft_ps_project; outside the band the result is bit for
  *                    bit that of gfft_ps_project.  A captured launch follows whatever d_gain[0] holds at each replay.
  *                    GFFT_ERR_INVALID (before a device is touched) as gfft_ps_project and for dk <= 0, blo < 0, bhi < blo,
- *                    a non-finite `gain` with d_gain NULL; n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues. */
+ *                    a non-finite `gain` with d_gain NULL; n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues.
+ *   gfft_ps_project_dealiased   gfft_ps_project (forced == 0) or gfft_ps_project_forced (forced != 0; dk, blo, bhi, gain, d_gain
+ *                    as there, ignored otherwise) with the dealiasing truncation fused in.  Mode (i0, i1, i2) is KEPT iff
+ *                      d_m0[i0] && d_m1[i1] && d_m2[i2]    three per-axis byte vectors on the device (n0, n1, n2 entries, non-zero =
+ *                                                          keep): a box mask in the sparse form of d_k*; NULL keeps the whole axis
+ *                      and  k0^2 + k1^2 + k2^2 <= kcut^2   as (k0 k0 + k1 k1) + k2 k2 in double from wavenumbers converted to
+ *                                                          double first (the |k|^2 of gfft_ps_spectrum), kcut * kcut formed once
+ *                                                          on the host; the edge is INCLUSIVE; kcut = +inf: no spherical cut,
+ *                                                          at no cost (a NaN wavenumber fails a finite cut)
+ *                    and TRUNCATED otherwise.  A kept mode is bit for bit the result of gfft_ps_project / gfft_ps_project_forced.
+ *                    A truncated mode is +0.0 in both parts of its three components whatever du_hat and u_hat hold there (NaN
+ *                    included): the predicate is evaluated before anything is loaded, and a truncated mode loads nothing.  The
+ *                    2/3 rule is the box mask keeping integer wavenumber n_i iff 3 |n_i| < N_i (strictly: |n_i| <= 21 of N = 64),
+ *                    after which the product of two truncated fields on the N-grid has no aliasing error in the kept modes.
+ *                    One pass, no more bytes than gfft_ps_project.  GFFT_ERR_INVALID (before a device is touched) as
+ *                    gfft_ps_project, for a NaN or negative kcut and, when forced != 0, as gfft_ps_project_forced; n1, n2 > 2^30
+ *                    is GFFT_ERR_UNSUPPORTED.  Only enqueues.
+ *   gfft_ps_dealias  the same truncation alone, in place on d_field = [ncomp][n0][n1][n2] complex: +0.0 to both parts of every
+ *                    component of every truncated mode.  Kept modes are neither read nor written -- no element of the field is
+ *                    read at all, so a NaN, a -0.0 or a denormal in a kept mode stays as it is.  d_k* are read only for a
+ *                    spherical cut and may be NULL when kcut = +inf.  GFFT_ERR_INVALID (before a device is touched) for a null
+ *                    field, ncomp < 1, negative extents, a NaN or negative kcut, a null d_k* unless kcut = +inf, precision;
+ *                    n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
@@ -392,6 +414,14 @@ int gfft_ps_force_gain(const double *d_spec, int nbins, int blo, int bhi, double
 int gfft_ps_project_forced(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
                            int64_t n0, int64_t n1, int64_t n2, double nu, double dk, int blo, int bhi,
                            double gain, const double *d_gain /* NULL: use `gain` */, int precision, void *stream);
+int gfft_ps_project_dealiased(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
+                              const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                              int64_t n0, int64_t n1, int64_t n2, double nu, double kcut,
+                              int forced, double dk, int blo, int bhi, double gain, const double *d_gain,
+                              int precision, void *stream);
+int gfft_ps_dealias(void *d_field, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                    const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                    int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

@@ -85,6 +85,10 @@ def _declare(lib):
         'gfft_ps_force_gain': (c.c_int, [vp, c.c_int, c.c_int, c.c_int, c.c_double, c.c_double, vp, vp]),
         'gfft_ps_project_forced': (c.c_int, [vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_double,
                                              c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
+        'gfft_ps_project_dealiased': (c.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double,
+                                                c.c_double, c.c_int, c.c_double, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
+        'gfft_ps_dealias': (c.c_int, [vp, c.c_int, vp, vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double,
+                                      c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -466,6 +470,32 @@ class HipEngine:
                                            shape[0], shape[1], shape[2], float(nu), float(dk), int(blo), int(bhi),
                                            float(gain), None if tgain is None else tgain.data_ptr(), precision,
                                            current_stream()))
+
+    def ps_project_dealiased(self, tdu, tu, k, m, shape, nu, kcut, force, precision):
+        """gfft_ps_project_dealiased: ps_project (force None) or ps_project_forced (force = (dk, blo, bhi, gain, tgain) as
+        there), keeping the modes with m[0][i0] && m[1][i1] && m[2][i2] (uint8 device vectors; None = the whole axis) and
+        |k| <= kcut (inf: no spherical cut); every other mode of tdu becomes +0 and is not read."""
+        self.require_device(tdu)
+        dk, blo, bhi, gain, tgain = (1.0, 0, 0, 0.0, None) if force is None else force
+        for t in tuple(m) + (tgain,):
+            if t is not None:
+                self.require_device(t)
+        check(lib().gfft_ps_project_dealiased(tdu.data_ptr(), tu.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                              *[None if t is None else t.data_ptr() for t in m],
+                                              shape[0], shape[1], shape[2], float(nu), float(kcut), 0 if force is None else 1,
+                                              float(dk), int(blo), int(bhi), float(gain),
+                                              None if tgain is None else tgain.data_ptr(), precision, current_stream()))
+
+    def ps_dealias(self, tf, ncomp, k, m, shape, kcut, precision):
+        """gfft_ps_dealias: +0 to every truncated mode of tf = complex [ncomp] + shape, in place; kept modes are not touched.
+        m and kcut as for ps_project_dealiased."""
+        self.require_device(tf)
+        for t in m:
+            if t is not None:
+                self.require_device(t)
+        check(lib().gfft_ps_dealias(tf.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                    *[None if t is None else t.data_ptr() for t in m],
+                                    shape[0], shape[1], shape[2], float(kcut), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

@@ -1,8 +1,8 @@
 // The pseudo-spectral layer either side of the transform path: the gfft_ps_* entry points of include/gfft.h (at the end of
 // the file), their launchers and their kernels, each one pass over its operands.
 //   * pointwise (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one temporary per
-//     operator): i K x u_hat, u x w, pressure projection + viscous term (with a band forcing fused in where asked for),
-//     the Runge-Kutta stage update, the time-step controller and the forcing gain.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
+//     operator): i K x u_hat, u x w, pressure projection + viscous term (with a band forcing and the dealiasing
+//     truncation fused in where asked for), the truncation on its own, the Runge-Kutta stage update, the time-step controller and the forcing gain.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
 //     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity) and physical-space statistics (ps_stats_kernel).
@@ -59,8 +59,10 @@ ps_cross_kernel(const real *__restrict__ a, const real *__restrict__ b, real *__
 // The shell of a mode: b = floor(|k| / dk + 0.5), in double from wavenumbers converted to double first (k2sq = |k|^2).  The
 // ONE definition: ps_shell_kernel bins by it and the forced ps_project_kernel forces by it, so the band that is forced is
 // the band whose energy the spectrum reports.  Integer-valued, or NaN for a NaN wavenumber (which compares false everywhere).
+__device__ __forceinline__ double ps_k2sq(double kx, double ky, double kz) { return (kx * kx + ky * ky) + kz * kz; }
+
 __device__ __forceinline__ double ps_shell_of(double kx, double ky, double kz, double dk, double &k2sq) {
-  k2sq = (kx * kx + ky * ky) + kz * kz;
+  k2sq = ps_k2sq(kx, ky, kz);
   return floor(sqrt(k2sq) / dk + 0.5);
 }
 
@@ -109,20 +111,86 @@ struct ps_band_args {
   }
 };
 
+// Which modes ps_project_kernel and ps_dealias_kernel keep (dealiasing): a launch passes a predicate `M` by value.  It has two
+// halves so that a kernel can put other work between them: load() fetches what the predicate needs of a mode beside its
+// wavenumbers, kept() decides from that and the wavenumbers.
+// gfft_ps_project, gfft_ps_project_forced: every mode; nothing is loaded or evaluated.
+struct ps_keep_all {
+  static constexpr bool always = true;
+  struct bytes {};
+  __device__ __forceinline__ bytes load(int64_t, int64_t, int64_t) const { return {}; }
+  template <typename real> __device__ __forceinline__ bool kept(const bytes &, real, real, real) const { return true; }
+};
+
+// gfft_ps_project_dealiased, gfft_ps_dealias: mode (i0, i1, i2) is kept iff m0[i0] && m1[i1] && m2[i2] (a box mask in the
+// sparse form of the wavenumbers: one byte per axis entry, a null vector keeps its whole axis) and |k|^2 <= kcut2, |k|^2 being
+// ps_k2sq -- the double the spectrum bins by -- and kcut2 = kcut * kcut formed once on the host; the edge is inclusive and a
+// NaN wavenumber fails it.  kcut2 = +inf: no spherical cut, and cuts() -- the same in every lane, so a scalar branch -- keeps
+// its conversions and multiplies out of the loop.  The three bytes are loaded together, not short-circuited: two or three
+// cached loads in flight cost less than branches between them.
+struct ps_keep_mask {
+  static constexpr bool always = false;
+  const unsigned char *m0, *m1, *m2;
+  double kcut2;
+  struct bytes { unsigned a, b, c; };
+  __device__ __forceinline__ bytes load(int64_t i0, int64_t i1, int64_t i2) const {
+    return {m0 ? m0[i0] : 1u, m1 ? m1[i1] : 1u, m2 ? m2[i2] : 1u};
+  }
+  __device__ __forceinline__ bool cuts() const { return kcut2 < (double)INFINITY; }
+  template <typename real> __device__ __forceinline__ bool kept(const bytes &m, real kx, real ky, real kz) const {
+    bool k = (m.a != 0) & (m.b != 0) & (m.c != 0);
+    if (cuts()) k = k & (ps_k2sq((double)kx, (double)ky, (double)kz) <= kcut2);
+    return k;
+  }
+};
+
+// what ps_project_kernel looks up for a mode before it touches the fields: its wavenumbers and the predicate's bytes
+template <typename real, typename M> struct ps_mode { real kx, ky, kz; typename M::bytes m; };
+
+template <typename real, typename M>
+__device__ __forceinline__ ps_mode<real, M> ps_mode_of(int64_t e, int64_t n1, int64_t n2, const real *__restrict__ k0,
+                                                       const real *__restrict__ k1, const real *__restrict__ k2, const M &keep) {
+  const int64_t row = e / n2;
+  const int64_t i2 = e - row * n2;
+  const real kz = k2[i2];
+  const int64_t i0 = row / n1;
+  const int64_t i1 = row - i0 * n1;
+  const real ky = k1[i1], kx = k0[i0];
+  return {kx, ky, kz, keep.load(i0, i1, i2)};
+}
+
 // p = sum_i du_i k_i / |k|^2 (|k|^2 = 0 -> 1);  du_j -= k_j p;  du_j -= nu |k|^2 u_j;  then the mode's forcing, if any (A).
 // One pass over nine component arrays either way: pointwise, grid-stride, no LDS, no atomics.
+// With a keep-predicate M other than ps_keep_all the pass also dealiases: the predicate is evaluated from the three
+// wavenumber lookups and the mask bytes BEFORE any load of du or u; a truncated mode loads nothing, stores +0 to its three
+// du components (whatever du and u hold there, NaN included) and is done; a kept mode runs the same body as without a
+// predicate.  Kept and truncated lanes share waves; whole rows and planes outside the box are waves that issue stores alone.
+// The field loads of a mode can only be issued once its lookups have come back; so that the two latencies do not add up in
+// every grid-stride step, the lookups of a lane's NEXT mode are issued in front of the field loads of the current one and
+// are back, with those, before its stores.
 // (Registers: in the list above ps_stats_kernel.)
-template <typename real, typename A>
+template <typename real, typename A, typename M = ps_keep_all>
 __global__ void __launch_bounds__(PS_THREADS)
 ps_project_kernel(cx<real> *__restrict__ du, const cx<real> *__restrict__ u, const real *__restrict__ k0,
                   const real *__restrict__ k1, const real *__restrict__ k2, int64_t n1, int64_t n2,
-                  int64_t count, real nu, A arg) {
+                  int64_t count, real nu, A arg, M keep) {
   const auto force = arg.template bind<real>();
-  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * PS_THREADS) {
-    const int64_t row = e / n2;
-    const real kz = k2[e - row * n2];
-    const int64_t i0 = row / n1;
-    const real ky = k1[row - i0 * n1], kx = k0[i0];
+  const int64_t first = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * PS_THREADS;
+  [[maybe_unused]] ps_mode<real, M> ahead = {};           // the lookups of the lane's next mode
+  if constexpr (!M::always)
+    if (first < count) ahead = ps_mode_of(first, n1, n2, k0, k1, k2, keep);
+  for (int64_t e = first; e < count; e += stride) {
+    const ps_mode<real, M> m = M::always ? ps_mode_of(e, n1, n2, k0, k1, k2, keep) : ahead;          // (a constant condition)
+    const real kx = m.kx, ky = m.ky, kz = m.kz;
+    if constexpr (!M::always) {
+      if (e + stride < count) ahead = ps_mode_of(e + stride, n1, n2, k0, k1, k2, keep);
+      if (!keep.kept(m.m, kx, ky, kz)) {
+        du[e] = {(real)0, (real)0};
+        du[e + count] = {(real)0, (real)0};
+        du[e + 2 * count] = {(real)0, (real)0};
+        continue;
+      }
+    }
     const real kk = kx * kx + ky * ky + kz * kz;
     const real inv = (real)1 / (kk == (real)0 ? (real)1 : kk);
     cx<real> d0 = du[e], d1 = du[e + count], d2 = du[e + 2 * count];
@@ -140,6 +208,27 @@ ps_project_kernel(cx<real> *__restrict__ du, const cx<real> *__restrict__ u, con
     du[e] = d0;
     du[e + count] = d1;
     du[e + 2 * count] = d2;
+  }
+}
+
+// The truncation on its own, in place on f = [ncomp][count]: +0 to every component of every mode that `keep` (above) does
+// not keep.  Kept modes are neither read nor written -- no element of the field is read at all, so whatever a kept mode
+// holds (a NaN, a -0, a denormal) stays --, and the wavenumbers are looked up only where there is a spherical cut.
+// Pointwise, grid-stride, a lane's mode is its flat index; stores only: 16 ncomp bytes per truncated mode.
+template <typename real>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_dealias_kernel(cx<real> *__restrict__ f, int ncomp, const real *__restrict__ k0, const real *__restrict__ k1,
+                  const real *__restrict__ k2, int64_t n1, int64_t n2, int64_t count, ps_keep_mask keep) {
+  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * PS_THREADS) {
+    const int64_t row = e / n2;
+    const int64_t i2 = e - row * n2;
+    const int64_t i0 = row / n1;
+    const int64_t i1 = row - i0 * n1;
+    const ps_keep_mask::bytes m = keep.load(i0, i1, i2);
+    real kx = 0, ky = 0, kz = 0;
+    if (keep.cuts()) { kx = k0[i0]; ky = k1[i1]; kz = k2[i2]; }
+    if (!keep.kept(m, kx, ky, kz))
+      for (int c = 0; c < ncomp; ++c) f[e + c * count] = {(real)0, (real)0};
   }
 }
 
@@ -415,7 +504,9 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // Registers (hipcc -O3, gfx950; no instantiation spills or uses scratch): ps_stats_kernel<double, 2, 3> 70 VGPRs,
 // <float, 4, 3> 70, <double, 2, 4> 90, <float, 4, 4> 98 (the largest), <double, 1, 3> 62, <float, 1, 3> 58;
 // st_reduce_kernel 12, ps_rk_dt_kernel 14 / 10 (double / float), ps_timestep_kernel 13;
-// ps_project_kernel<double / float, ps_band_args> (the forced projection) 64 / 50 against 58 / 42 unforced, ps_force_gain_kernel 12.
+// ps_project_kernel<double / float, ps_band_args> (the forced projection) 64 / 50 against 58 / 42 unforced, ps_force_gain_kernel 12;
+// ps_project_kernel<double / float, ., ps_keep_mask> (the dealiased projection) 70 / 50 unforced and 76 / 60 forced -- the
+// next mode's lookups are live across the body: 7 and 6 waves per SIMD in fp64, 8 in fp32 --, ps_dealias_kernel 24 / 23.
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -545,7 +636,7 @@ hipError_t launch_ps_project(void *du, const void *u, const void *k0, const void
                              int64_t n1, int64_t n2, double nu, int precision, hipStream_t s) {
   const int64_t count = n0 * n1 * n2;
   return by_precision(
-      precision, [&](auto r) { return ps_pointwise(ps_project_kernel<decltype(r), ps_no_force>, count, s, du, u, k0, k1, k2, n1, n2, count, nu, ps_no_force()); });
+      precision, [&](auto r) { return ps_pointwise(ps_project_kernel<decltype(r), ps_no_force>, count, s, du, u, k0, k1, k2, n1, n2, count, nu, ps_no_force(), ps_keep_all()); });
 }
 
 // The pre-filter of ps_band_force: lo2 <= kk <= hi2 for every mode whose exact shell lies in [blo, bhi], kk being |k|^2 as
@@ -579,8 +670,31 @@ hipError_t launch_ps_project_forced(void *du, const void *u, const void *k0, con
   return by_precision(precision, [&](auto r) {
     const ps_band b = ps_band_bounds<decltype(r)>(dk, blo, bhi);
     return ps_pointwise(ps_project_kernel<decltype(r), ps_band_args>, count, s, du, u, k0, k1, k2, n1, n2, count, nu,
-                        ps_band_args{dk, blo, bhi, b.lo2, b.hi2, gain, d_gain});
+                        ps_band_args{dk, blo, bhi, b.lo2, b.hi2, gain, d_gain}, ps_keep_all());
   });
+}
+
+// the projection, forced (the band arguments as above) or not, with the truncation `keep` fused in
+hipError_t launch_ps_project_dealiased(void *du, const void *u, const void *k0, const void *k1, const void *k2, int64_t n0,
+                                       int64_t n1, int64_t n2, double nu, ps_keep_mask keep, bool forced, double dk, int blo,
+                                       int bhi, double gain, const double *d_gain, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    if (!forced)
+      return ps_pointwise(ps_project_kernel<real, ps_no_force, ps_keep_mask>, count, s, du, u, k0, k1, k2, n1, n2, count, nu,
+                          ps_no_force(), keep);
+    const ps_band b = ps_band_bounds<real>(dk, blo, bhi);
+    return ps_pointwise(ps_project_kernel<real, ps_band_args, ps_keep_mask>, count, s, du, u, k0, k1, k2, n1, n2, count, nu,
+                        ps_band_args{dk, blo, bhi, b.lo2, b.hi2, gain, d_gain}, keep);
+  });
+}
+
+hipError_t launch_ps_dealias(void *f, int ncomp, const void *k0, const void *k1, const void *k2, int64_t n0, int64_t n1,
+                             int64_t n2, ps_keep_mask keep, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(ps_dealias_kernel<decltype(r)>, count, s, f, ncomp, k0, k1, k2, n1, n2, count, keep); });
 }
 
 hipError_t launch_ps_force_gain(const double *spec, int blo, int bhi, double eps, double gain_max, double *gain, hipStream_t s) {
@@ -809,6 +923,39 @@ int gfft_ps_project_forced(void *d_du_hat, const void *d_u_hat, const void *d_k0
   if (int rc = check_device()) return rc;
   HIP_TRY(launch_ps_project_forced(d_du_hat, d_u_hat, d_k0, d_k1, d_k2, n0, n1, n2, nu, dk, blo, bhi, gain, d_gain, precision,
                                    (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_project_dealiased(void *d_du_hat, const void *d_u_hat, const void *d_k0, const void *d_k1, const void *d_k2,
+                              const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                              int64_t n0, int64_t n1, int64_t n2, double nu, double kcut,
+                              int forced, double dk, int blo, int bhi, double gain, const double *d_gain,
+                              int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum; the band arguments are looked at only where they are used)
+  if (!d_du_hat || !d_u_hat || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || !(kcut >= 0) ||
+      (forced && (!(dk > 0) || blo < 0 || bhi < blo || (!d_gain && !std::isfinite(gain)))) ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_project_dealiased: bad argument");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_project_dealiased: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_project_dealiased(d_du_hat, d_u_hat, d_k0, d_k1, d_k2, n0, n1, n2, nu, ps_keep_mask{d_m0, d_m1, d_m2, kcut * kcut},
+                                      forced != 0, dk, blo, bhi, gain, d_gain, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_dealias(void *d_field, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                    const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                    int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream) {
+  // (arguments first; the wavenumbers are read only for a spherical cut)
+  if (!d_field || ncomp < 1 || n0 < 0 || n1 < 0 || n2 < 0 || !(kcut >= 0) ||
+      (std::isfinite(kcut) && (!d_k0 || !d_k1 || !d_k2)) || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_dealias: bad argument");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_dealias: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_dealias(d_field, ncomp, d_k0, d_k1, d_k2, n0, n1, n2, ps_keep_mask{d_m0, d_m1, d_m2, kcut * kcut}, precision,
+                            (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -34,9 +34,19 @@ and the term that keeps a flow from decaying, so that all of the above have a st
     project(du_hat, u_hat, nu, force=(g, band))   the projection with du_hat += g u_hat in the band fused in behind it: no
                                 extra pass; g a float or that device tensor, so a forced step replays from one HIP graph
 
+and the truncation that keeps the quadratic term free of aliasing errors over a long run:
+
+    dealias_mask(rule='2/3', kcut=None)   three per-axis byte vectors (the sparse form of a box mask, as K is of the wavenumber
+                                mesh) and a spherical cut |k| <= kcut: rule '2/3' keeps integer wavenumber n_i iff 3 |n_i| < N_i
+    project(du_hat, u_hat, nu, dealias=mask)   the projection (forced or not) with the truncation fused in: a truncated mode
+                                is stored as +0 and none of its six operands is loaded -- fewer bytes than without, no extra pass
+    dealias(field, mask)        the truncation alone, in place (the initial condition): stores to truncated modes, reads nothing
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -76,6 +86,11 @@ def hermitian_weights(fft):
     return torch.as_tensor(w.astype(rdt), device=fft.forward.output_array.device)
 
 
+DealiasMask = collections.namedtuple('DealiasMask', 'm0 m1 m2 kcut')
+DealiasMask.__doc__ = """What `SpectralOps.dealias_mask` returns: per-axis uint8 device vectors over this rank's spectral block (non-zero =
+keep; None = the whole axis) and the spherical cut |k| <= kcut (inf: none)."""
+
+
 def _prec(a):
     return _lib.precision_of(a.dtype)
 
@@ -101,6 +116,11 @@ class SpectralOps:
         self.inv_dx = [float(n) / float(l) for n, l in zip(fft.global_shape(), np.full(3, 2 * np.pi) if L is None else np.asarray(L, dtype=float))]
         self._stats_dev = None
         self._force_spec = None
+        # what dealias_mask needs of the transform: global sizes, this rank's slice of the spectral axes, the device
+        self._N = tuple(int(n) for n in fft.global_shape())
+        self._gshape = tuple(int(n) for n in fft.global_shape(True))
+        self._slice = tuple(fft.local_slice(True))
+        self._real = np.dtype(fft.dtype(False)).kind == 'f'
 
     def _same_precision(self, precision):
         # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
@@ -113,19 +133,73 @@ class SpectralOps:
         _lib.engine().ps_curl(_t(u_hat), _t(out), self.K, self.shape, _prec(u_hat))
         return out
 
-    def project(self, du_hat, u_hat, nu, force=None):
+    def dealias_mask(self, rule='2/3', kcut=None):
+        """The kept set of `project(..., dealias=)` and `dealias` as a `DealiasMask` (m0, m1, m2, kcut): a mode is kept iff
+        m0[i0] and m1[i1] and m2[i2] and |k| <= kcut.
+        rule='2/3': global integer wavenumber n_i is kept iff 3 * |n_i| < N_i -- strictly: |n| <= 21 of N = 64, 15 of 48, 6 of
+        21, never the Nyquist plane; with the looser |n| < 2/3 (N/2 + 1) the quadratic term keeps an O(1) aliasing error.
+        Built from the fftfreq / rfftfreq integers and sliced by fft.local_slice(True), exactly as `local_wavenumbers`
+        slices K.  rule=None: every axis whole (no vectors).  Or a sequence of three boolean arrays of the GLOBAL spectral
+        axis lengths (None for a whole axis), sliced the same way.  kcut=None: no spherical cut.
+        Allocates three small device vectors: build the mask once, outside anything that is captured."""
+        kcut = np.inf if kcut is None else float(kcut)
+        assert kcut >= 0, kcut
+        if rule is None:
+            return DealiasMask(None, None, None, kcut)
+        if isinstance(rule, str):
+            assert rule == '2/3', rule
+            n = [np.fft.fftfreq(N, 1. / N) for N in self._N]
+            if self._real:
+                n[-1] = np.fft.rfftfreq(self._N[-1], 1. / self._N[-1])
+            rule = [3 * np.abs(ni.astype(int)) < N for ni, N in zip(n, self._N)]
+        assert len(rule) == 3, 'rule = three per-axis boolean arrays'
+        dev = self.K[0].device
+        m = []
+        for r, g, sl in zip(rule, self._gshape, self._slice):
+            if r is not None:
+                r = np.asarray(r)
+                assert r.shape == (g,), (r.shape, g)
+                r = torch.as_tensor(np.ascontiguousarray(r[sl] != 0).astype(np.uint8), device=dev)
+            m.append(r)
+        return DealiasMask(m[0], m[1], m[2], kcut)
+
+    def _mask(self, dealias):
+        """((m0, m1, m2), kcut) of a `dealias=` argument, checked against this block"""
+        assert len(dealias) == 4, 'dealias = (m0, m1, m2, kcut): see dealias_mask'
+        m, kcut = tuple(dealias[:3]), dealias[3]
+        kcut = np.inf if kcut is None else float(kcut)
+        assert kcut >= 0, kcut
+        for mi, n in zip(m, self.shape):
+            assert mi is None or (isinstance(mi, torch.Tensor) and mi.dtype in (torch.uint8, torch.bool) and
+                                  tuple(mi.shape) == (n,) and mi.is_contiguous()), 'a mask vector is a uint8 tensor over its local axis'
+        return m, kcut
+
+    def project(self, du_hat, u_hat, nu, force=None, dealias=None):
         """In place: pressure projection and viscous term of the Navier-Stokes right-hand side.
         force=(gain, (blo, bhi)) or (gain, (blo, bhi), dk): the same pass then adds gain * u_hat to du_hat in every mode
         whose shell floor(|k| / dk + 1/2) (the shells of `spectrum`; dk defaults as there) lies in blo..bhi -- linear band
         forcing, after the projection and the viscous term, not projected (solenoidal where u_hat is).  gain is a float
         or a device double tensor (contiguous, at least one element: `forcing_gain(out=)` writes one) whose element 0 the
         kernel reads when it runs; both are rounded to the field's precision once and give the same bits.  Outside the
-        band the result is bit for bit that of force=None."""
+        band the result is bit for bit that of force=None.
+        dealias=a `dealias_mask()` (or any (m0, m1, m2, kcut)): the same pass also truncates -- a kept mode gets bit for bit
+        the result without `dealias`, forced or not; a truncated mode becomes +0 whatever du_hat and u_hat hold there, and
+        nothing of it is loaded.  Nothing synchronises or allocates."""
         assert tuple(du_hat.shape) == (3,) + self.shape == tuple(u_hat.shape)
         self._same_precision(_prec(du_hat))
-        if force is None:
+        fargs = None if force is None else self._force(force)
+        if dealias is not None:
+            m, kcut = self._mask(dealias)
+            _lib.engine().ps_project_dealiased(_t(du_hat), _t(u_hat), self.K, m, self.shape, nu, kcut, fargs, _prec(du_hat))
+        elif fargs is None:
             _lib.engine().ps_project(_t(du_hat), _t(u_hat), self.K, self.shape, nu, _prec(du_hat))
-            return du_hat
+        else:
+            dk, blo, bhi, gain, tgain = fargs
+            _lib.engine().ps_project_forced(_t(du_hat), _t(u_hat), self.K, self.shape, nu, dk, blo, bhi, gain, tgain, _prec(du_hat))
+        return du_hat
+
+    def _force(self, force):
+        """(dk, blo, bhi, gain, tgain) of a `force=` argument: tgain the device tensor that holds the gain, or None"""
         assert len(force) in (2, 3), 'force = (gain, (blo, bhi)) or (gain, (blo, bhi), dk)'
         gain, (blo, bhi) = force[0], force[1]
         dk = self.dk if len(force) == 2 or force[2] is None else float(force[2])
@@ -136,9 +210,16 @@ class SpectralOps:
             assert tgain.dtype == torch.float64 and tgain.numel() >= 1 and tgain.is_contiguous()
         else:
             assert np.isfinite(gain), gain
-        _lib.engine().ps_project_forced(_t(du_hat), _t(u_hat), self.K, self.shape, nu, dk, int(blo), int(bhi), float(gain),
-                                        tgain, _prec(du_hat))
-        return du_hat
+        return dk, int(blo), int(bhi), float(gain), tgain
+
+    def dealias(self, field, mask):
+        """In place: +0 to every mode of `field` ([m] + spectral shape or, a scalar field, the spectral shape) that `mask` (a
+        `dealias_mask()`) does not keep; returns `field`.  Kept modes are neither read nor written: whatever they hold
+        stays.  One kernel of stores; nothing synchronises or allocates."""
+        t, ncomp, precision = self._field(field)
+        m, kcut = self._mask(mask)
+        _lib.engine().ps_dealias(t, ncomp, self.K, m, self.shape, kcut, precision)
+        return field
 
     def forcing_gain(self, u_hat, eps, band, gain_max=np.inf, dk=None, out=None):
         """The gain g of the band forcing f_hat = g u_hat (`project(..., force=(g, band))`) that injects energy at the rate
