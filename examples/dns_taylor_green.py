@@ -27,6 +27,13 @@ measurable beyond |n| = 21: the dealiased energy after 10 steps is 0.12495311751
 MI355X, there is no counterpart in the reference, which does not dealias), the undealiased run's value to all 15 digits.  A
 forced run long enough to fill the spectrum is wrong without the truncation.
 
+`scalar=(kappa, G)` carries a passive scalar along, d theta/dt + u . grad theta = kappa lap theta - G . u, in flux form: every
+right-hand side adds one backward of theta_hat, `spectral.scalar_flux(U, Theta, UT)` on the U the step already has in physical
+space, three forwards and `SpectralOps.scalar_rhs` (with the mean-gradient term and the step's dealiasing mask fused in); its
+Runge-Kutta stages sit beside the velocity's and take the same step.  theta_0 = cos(x) sin(y / 2) cos(z / 2): zero mean, one
+period of each axis of the box (2 pi, 4 pi, 4 pi).  After 10 steps at 64^3 with kappa = nu and G = (1, 0, 0) the variance
+<theta^2> is SCALAR_VARIANCE below (measured on one MI355X; the reference has no scalar).
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -41,10 +48,12 @@ import torch
 
 
 DEALIASED_ENERGY = 0.124953117516743          # solve(dealias='2/3'), M = 6, 10 steps
+SCALAR_VARIANCE = 0.126225641497587           # 'scalar_variance' of solve(scalar=(nu, (1, 0, 0))), M = 6, 10 steps
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
-          transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None):
+          transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
+          scalar=None):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -60,7 +69,12 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     and 'band_energy'.
     dealias='2/3': the initial U_hat and every right-hand side are truncated by the 2/3 rule -- on the fused path by
     `SpectralOps.dealias` and `project(..., dealias=)`, on the fused=False path by the same mask as an array-sized torch
-    expression (the A/B baseline)."""
+    expression (the A/B baseline).
+    scalar=(kappa, G): a passive scalar theta with diffusivity kappa and imposed mean gradient G (three floats, or None) is
+    advanced with the velocity, theta_0 = cos(x) sin(y / 2) cos(z / 2) -- on the fused path by `spectral.scalar_flux` and
+    `SpectralOps.scalar_rhs`, on the fused=False path by array-sized torch expressions (the A/B baseline).  A dict passed as
+    `stats` receives 'scalar_variance' = <theta^2> (fused: 2 * sum(spectrum(T_hat)[0])) and 'scalar_flux' = the three
+    <u_c theta> (fused: sum(cospectrum(U_hat[c], T_hat)[0])).  The velocity, and so the returned energy, is unchanged."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -87,6 +101,11 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     K_over_K2 = K / torch.where(K2 == 0, torch.ones_like(K2), K2)
 
     u, uh, uh0, uh1, du, cu = (a.tensor for a in (U, U_hat, U_hat0, U_hat1, dU, curl))
+    if scalar is not None:
+        kappa, G = float(scalar[0]), (None if scalar[1] is None else tuple(float(g) for g in scalar[1]))
+        Theta = newDistArray(FFT, False)                      # the scalar, physical space
+        T_hat, T_hat0, T_hat1, dT = (newDistArray(FFT) for _ in range(4))
+        th, tht, tht0, tht1, dth = (a.tensor for a in (Theta, T_hat, T_hat0, T_hat1, dT))
     assert dealias in (None, '2/3'), dealias
     mask = None
     if dealias and not fused:
@@ -98,6 +117,9 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             mask = ops.dealias_mask(dealias)
         W_hat = newDistArray(FFT, rank=1)                     # i K x u_hat
         UxW = newDistArray(FFT, False, rank=1)                # u x curl u
+        if scalar is not None:
+            UT = newDistArray(FFT, False, rank=1)             # u theta
+            UT_hat = newDistArray(FFT, rank=1)
 
         force = [None]                                        # project's force= of the current step
 
@@ -111,6 +133,12 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             for j in range(3):
                 FFT.forward(UxW[j], dU[j])
             ops.project(dU, U_hat, nu, force=force[0], dealias=mask)
+            if scalar is not None:                            # U is this stage's velocity in physical space already
+                FFT.backward(T_hat, Theta)
+                spectral.scalar_flux(U, Theta, UT)
+                for j in range(3):
+                    FFT.forward(UT[j], UT_hat[j])
+                ops.scalar_rhs(dT, UT_hat, T_hat, kappa, G, U_hat, dealias=mask)
 
     def fwd(x, out):      # physical (torch expression) -> spectral slice `out`
         out.copy_(FFT.forward(x).tensor)
@@ -132,6 +160,16 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         du.sub_(nu * K2 * uh)
         if dealias:
             du.masked_fill_(~keep, 0)
+        if scalar is not None:
+            bwd(tht, th)
+            dth.zero_()
+            for j in range(3):
+                dth.sub_(1j * K[j] * FFT.forward(u[j] * th).tensor)
+            dth.sub_(kappa * K2 * tht)
+            if G is not None:
+                dth.sub_(G[0] * uh[0] + G[1] * uh[1] + G[2] * uh[2])
+            if dealias:
+                dth.masked_fill_(~keep, 0)
 
     u[0] = torch.sin(X[0]) * torch.cos(X[1]) * torch.cos(X[2])
     u[1] = -torch.cos(X[0]) * torch.sin(X[1]) * torch.cos(X[2])
@@ -142,6 +180,13 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         ops.dealias(U_hat, mask)
     elif dealias:
         uh.masked_fill_(~keep, 0)
+    if scalar is not None:
+        th.copy_(torch.cos(X[0]) * torch.sin(X[1] / 2) * torch.cos(X[2] / 2))
+        fwd(th, tht)
+        if dealias and fused:
+            ops.dealias(T_hat, mask)
+        elif dealias:
+            tht.masked_fill_(~keep, 0)
 
     a = [1. / 6., 1. / 3., 1. / 3., 1. / 6.]
     b = [0.5, 0.5, 1.]
@@ -176,20 +221,34 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             sim_time[0] += h
         uh0.copy_(uh)
         uh1.copy_(uh)
+        if scalar is not None:
+            tht0.copy_(tht)
+            tht1.copy_(tht)
         for rk in range(4):
             if adaptive and device_dt:
                 compute_rhs_fused()
                 spectral.rk_stage(U_hat if rk < 3 else None, U_hat0, U_hat1, dU, b[rk] if rk < 3 else 0.0, a[rk], dt=dt_dev)
+                if scalar is not None:
+                    spectral.rk_stage(T_hat if rk < 3 else None, T_hat0, T_hat1, dT, b[rk] if rk < 3 else 0.0, a[rk], dt=dt_dev)
             elif fused:
                 compute_rhs_fused()
                 spectral.rk_stage(U_hat if rk < 3 else None, U_hat0, U_hat1, dU,
                                   b[rk] * h if rk < 3 else 0.0, a[rk] * h)
+                if scalar is not None:
+                    spectral.rk_stage(T_hat if rk < 3 else None, T_hat0, T_hat1, dT,
+                                      b[rk] * h if rk < 3 else 0.0, a[rk] * h)
             else:
                 compute_rhs()
                 if rk < 3:
                     torch.add(uh0, du, alpha=b[rk] * dt, out=uh)
                 uh1.add_(du, alpha=a[rk] * dt)
+                if scalar is not None:
+                    if rk < 3:
+                        torch.add(tht0, dth, alpha=b[rk] * dt, out=tht)
+                    tht1.add_(dth, alpha=a[rk] * dt)
         uh.copy_(uh1)
+        if scalar is not None:
+            tht.copy_(tht1)
         for i in range(3):
             if fused:
                 FFT.backward(U_hat[i], U[i])
@@ -202,6 +261,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         # first execution, so the step can be captured into a HIP graph and replayed.
         assert fused and world.Get_size() == 1 and dev.type == 'cuda'
         keep = uh.clone()
+        keep_t = tht.clone() if scalar is not None else None
         keep_u = u.clone() if adaptive else None     # the adaptive step READS U: the warm-up must not leave its own there
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):
@@ -209,10 +269,14 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         uh.copy_(keep)
+        if scalar is not None:
+            tht.copy_(keep_t)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             step()
         uh.copy_(keep)
+        if scalar is not None:
+            tht.copy_(keep_t)
         if adaptive:
             u.copy_(keep_u)
             dt_dev.zero_()
@@ -237,6 +301,17 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             last_gain[:] = gain_dev.cpu().tolist()
         if stats is not None:
             stats.update(gain=last_gain[0], band_energy=last_gain[1])
+    if scalar is not None:
+        if fused:
+            variance = 2.0 * float(ops.spectrum(T_hat)[0].sum())
+            sflux = [float(ops.cospectrum(U_hat[c], T_hat)[0].sum()) for c in range(3)]
+        else:
+            bwd(tht, th)
+            npts = float(N[0] * N[1] * N[2])
+            variance = sum(world.allgather_obj(float((th * th).sum().item()))) / npts
+            sflux = [sum(world.allgather_obj(float((u[c] * th).sum().item()))) / npts for c in range(3)]
+        if stats is not None:
+            stats.update(scalar_variance=variance, scalar_flux=sflux)
     elapsed = time.time() - t0
     if verbose and world.Get_rank() == 0:
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
@@ -248,6 +323,8 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         if forced:
             print('  forcing shells %d..%d at eps = %g (%s gain): last gain %.6f on band energy %.6f -> injecting %.6f'
                   % (band + (f_eps, 'device' if device_gain else 'host', last_gain[0], last_gain[1], 2 * last_gain[0] * last_gain[1])))
+    if scalar is not None and verbose and world.Get_rank() == 0:
+        print('  scalar (kappa = %g, G = %s): variance %.15f, flux <u theta> = (%.6e, %.6e, %.6e)' % ((kappa, G, variance) + tuple(sflux)))
     if transfer:
         assert fused and not spectrum
         compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term
@@ -310,6 +387,17 @@ if __name__ == '__main__':
     if w.Get_size() == 1:
         eg = solve(w, verbose=True, dealias='2/3', graph=True)
         assert abs(eg - ed) <= 1e-12, (eg, ed)
+    ss, sb = {}, {}
+    es = solve(w, verbose=True, scalar=(0.000625, (1, 0, 0)), stats=ss)      # a passive scalar against a mean gradient, kappa = nu
+    eb = solve(w, verbose=True, scalar=(0.000625, (1, 0, 0)), stats=sb, fused=False)
+    assert round(es - 0.124953117517, 7) == 0 and round(eb - 0.124953117517, 7) == 0, (es, eb)      # the scalar is passive
+    assert abs(ss['scalar_variance'] - sb['scalar_variance']) <= 1e-10 * sb['scalar_variance'], (ss, sb)
+    assert abs(ss['scalar_variance'] - SCALAR_VARIANCE) <= 1e-9 * SCALAR_VARIANCE, (ss, SCALAR_VARIANCE)
+    assert max(abs(x - y) for x, y in zip(ss['scalar_flux'], sb['scalar_flux'])) <= 1e-10, (ss, sb)
+    if w.Get_size() == 1:
+        sg = {}
+        solve(w, verbose=True, scalar=(0.000625, (1, 0, 0)), stats=sg, graph=True)
+        assert abs(sg['scalar_variance'] - ss['scalar_variance']) <= 1e-12 * ss['scalar_variance'], (sg, ss)
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)

@@ -388,7 +388,31 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    read at all, so a NaN, a -0.0 or a denormal in a kept mode stays as it is.  d_k* are read only for a
  *                    spherical cut and may be NULL when kcut = +inf.  GFFT_ERR_INVALID (before a device is touched) for a null
  *                    field, ncomp < 1, negative extents, a NaN or negative kcut, a null d_k* unless kcut = +inf, precision;
- *                    n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues. */
+ *                    n1, n2 > 2^30 is GFFT_ERR_UNSUPPORTED.  Only enqueues.
+ *   Passive scalars, d theta / dt + u . grad theta = kappa lap theta - G . u (G: an imposed mean gradient, optional), in FLUX
+ *   form: u . grad theta = div(u theta) for solenoidal u -- one backward and three forward transforms per scalar, as the gradient
+ *   form, and no stored gradient.  Both kernels take nscalar = 1 ... 4 scalars at once and read the velocity ONCE for all of them.
+ *   gfft_ps_scalar_flux  flux[s][c][e] = u[c][e] * theta[s][e] on real fields: d_u = [3][count], d_theta = [nscalar][count],
+ *                    d_flux = [nscalar][3][count].  One multiply: bit for bit the correctly rounded product in the field's
+ *                    precision.  3 + nscalar loads and 3 nscalar stores per point; a lane moves 16 bytes per load and store
+ *                    where they divide `count` and all three bases are 16-byte aligned, one element otherwise.  d_flux must
+ *                    not overlap an input.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, nscalar < 1,
+ *                    count < 0, precision; nscalar > 4 is GFFT_ERR_UNSUPPORTED.  Only enqueues.
+ *   gfft_ps_scalar_rhs   per mode and scalar s, in the field's precision, with kk = k0 k0 + k1 k1 + k2 k2 as gfft_ps_project forms it:
+ *                      a = k0 F[s][0] + k1 F[s][1] + k2 F[s][2]                              F = d_flux_hat = [nscalar][3][n0][n1][n2]
+ *                      d[s] = -i a - (kappa[s] kk) theta[s] - (G[s][0] u0 + G[s][1] u1 + G[s][2] u2)      -i a = (Im a, -Re a)
+ *                    d = d_dtheta_hat and theta = d_theta_hat = [nscalar][n0][n1][n2], u = d_u_hat = [3][n0][n1][n2].  kappa
+ *                    (nscalar HOST doubles) and grad (nscalar x 3 HOST doubles, G[s][c] = grad[3 s + c]) travel by value in
+ *                    the launch.  grad NULL: no mean-gradient term, and d_u_hat (which may be NULL) is not read at all; with
+ *                    grad, d_u_hat is loaded once per mode for all scalars.  One pass: 4 nscalar (+ 3) complex loads and
+ *                    nscalar stores per mode.  d_m0/1/2 and kcut select the kept modes exactly as for
+ *                    gfft_ps_project_dealiased (all three NULL and kcut = +inf: every mode, at no cost): the predicate is
+ *                    evaluated before anything of the mode is loaded, a truncated mode loads nothing and stores +0.0 to both
+ *                    parts of its nscalar outputs whatever the inputs hold there (NaN included), a kept mode is bit for bit
+ *                    the result of the call without a mask.  d_dtheta_hat must not overlap an input.  GFFT_ERR_INVALID
+ *                    (before a device is touched) as gfft_ps_project_dealiased and for nscalar < 1, a null kappa, a kappa that
+ *                    is negative or not finite, grad without d_u_hat, a grad that is not finite; nscalar > 4 and n1, n2 > 2^30
+ *                    are GFFT_ERR_UNSUPPORTED.  Only enqueues and allocates nothing, so it can be captured. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
@@ -422,6 +446,14 @@ int gfft_ps_project_dealiased(void *d_du_hat, const void *d_u_hat, const void *d
 int gfft_ps_dealias(void *d_field, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
                     const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
                     int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream);
+int gfft_ps_scalar_flux(const void *d_u /* [3][count] */, const void *d_theta /* [m][count] */,
+                        void *d_flux /* [m][3][count] */, int nscalar, int64_t count, int precision, void *stream);
+int gfft_ps_scalar_rhs(void *d_dtheta_hat /* [m] */, const void *d_flux_hat /* [m][3] */, const void *d_theta_hat /* [m] */,
+                       const void *d_u_hat /* [3], or NULL */, int nscalar,
+                       const double *kappa /* host, m */, const double *grad /* host, m x 3, or NULL */,
+                       const void *d_k0, const void *d_k1, const void *d_k2,
+                       const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                       int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

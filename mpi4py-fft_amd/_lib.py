@@ -89,6 +89,9 @@ def _declare(lib):
                                                 c.c_double, c.c_int, c.c_double, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
         'gfft_ps_dealias': (c.c_int, [vp, c.c_int, vp, vp, vp, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double,
                                       c.c_int, vp]),
+        'gfft_ps_scalar_flux': (c.c_int, [vp, vp, vp, c.c_int, c.c_int64, c.c_int, vp]),
+        'gfft_ps_scalar_rhs': (c.c_int, [vp, vp, vp, vp, c.c_int, c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp,
+                                         vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -496,6 +499,28 @@ class HipEngine:
         check(lib().gfft_ps_dealias(tf.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
                                     *[None if t is None else t.data_ptr() for t in m],
                                     shape[0], shape[1], shape[2], float(kcut), precision, current_stream()))
+
+    def ps_scalar_flux(self, tu, ttheta, tflux, nscalar, count, precision):
+        """gfft_ps_scalar_flux: tflux[s][c] = tu[c] * ttheta[s] on real fields of `count` points per component; tflux
+        overlaps neither input."""
+        for t in (tu, ttheta, tflux):
+            self.require_device(t)
+        check(lib().gfft_ps_scalar_flux(tu.data_ptr(), ttheta.data_ptr(), tflux.data_ptr(), int(nscalar), int(count), precision,
+                                        current_stream()))
+
+    def ps_scalar_rhs(self, tdtheta, tflux, ttheta, tu, nscalar, kappa, grad, k, m, shape, kcut, precision):
+        """gfft_ps_scalar_rhs: tdtheta[s] = -i K . tflux[s] - kappa[s] |K|^2 ttheta[s] - grad[s] . tu for nscalar scalars;
+        kappa = nscalar host floats, grad = nscalar x 3 host floats or None (tu, which may be None, is then not read);
+        m and kcut as for ps_project_dealiased (all None and inf: every mode is kept)."""
+        for t in (tdtheta, tflux, ttheta, tu) + tuple(m):
+            if t is not None:
+                self.require_device(t)
+        kap = (ctypes.c_double * int(nscalar))(*[float(x) for x in kappa])
+        g = None if grad is None else (ctypes.c_double * (3 * int(nscalar)))(*[float(x) for row in grad for x in row])
+        check(lib().gfft_ps_scalar_rhs(tdtheta.data_ptr(), tflux.data_ptr(), ttheta.data_ptr(), None if tu is None else tu.data_ptr(),
+                                       int(nscalar), kap, g, k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                       *[None if t is None else t.data_ptr() for t in m],
+                                       shape[0], shape[1], shape[2], float(kcut), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

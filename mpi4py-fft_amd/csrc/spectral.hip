@@ -2,7 +2,8 @@
 // the file), their launchers and their kernels, each one pass over its operands.
 //   * pointwise (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one temporary per
 //     operator): i K x u_hat, u x w, pressure projection + viscous term (with a band forcing and the dealiasing
-//     truncation fused in where asked for), the truncation on its own, the Runge-Kutta stage update, the time-step controller and the forcing gain.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
+//     truncation fused in where asked for), the truncation on its own, the Runge-Kutta stage update, the time-step controller and the forcing gain; for passive
+//     scalars the flux u theta and the right-hand side -i K . (u theta)^ - kappa |K|^2 theta^ - G . u^.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
 //     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity) and physical-space statistics (ps_stats_kernel).
@@ -507,6 +508,10 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // ps_project_kernel<double / float, ps_band_args> (the forced projection) 64 / 50 against 58 / 42 unforced, ps_force_gain_kernel 12;
 // ps_project_kernel<double / float, ., ps_keep_mask> (the dealiased projection) 70 / 50 unforced and 76 / 60 forced -- the
 // next mode's lookups are live across the body: 7 and 6 waves per SIMD in fp64, 8 in fp32 --, ps_dealias_kernel 24 / 23.
+// ps_scalar_flux_kernel<double, 2, NS = 1 ... 4> 28, 44, 58, 58 and <float, 4, NS> 28, 44, 58, 60; one element per lane: 16 ... 54;
+// ps_scalar_rhs_kernel<double / float, NS, mean gradient?, mask?>, every instantiation 8 waves per SIMD but <double, 2, yes, no>:
+//   NS = 1: 36 / 26 plain, 48 / 38 with the gradient, 48 / 34 masked, 60 / 46 with both;   NS = 2: 56 / 40, 66 / 56 (7 waves in
+//   fp64), 52 / 50, 64 / 56;   NS = 3 and 4 (the scalars in turn): 40 / 26, 52 / 34, 46 / 36, 60 / 42.
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -600,6 +605,102 @@ st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__
     r = part[0];
     for (int w = 1; w < PS_THREADS / 64; ++w) r = st_combine(kind, r, part[w]);
     out[i] = r;
+  }
+}
+
+// ---- passive scalars: d theta / dt + div(u theta) = kappa lap theta - G . u, NS <= SC_MAX scalars per launch --------------
+// The flux form (u . grad theta = div(u theta) for solenoidal u) costs the four transforms per scalar of the gradient form
+// and stores no gradient; its pointwise work is the two kernels below.  NS is a template parameter, as NC is of
+// ps_stats_kernel, so that nothing is indexed at run time; the velocity is read ONCE for all NS scalars.
+// (Registers: in the list above ps_stats_kernel.)
+// Measured on one MI355X (tools/scalar_probe.py, 256^3 fp64, HIP events after a warm-up, minimum of 15 rounds), achieved bytes
+// per second against gfft_probe_copy in the same run (6.08 TB/s), one scalar / three scalars:
+//   ps_scalar_flux_kernel                      5.52 / 5.11 TB/s = 0.91 / 0.84 of the copy
+//   ps_scalar_rhs_kernel, mean gradient        4.55 / 4.80 TB/s = 0.75 / 0.79      without it 5.02 / 4.95 = 0.83 / 0.81
+//   ps_scalar_rhs_kernel, gradient + 2/3 mask  4.24 / 4.41 TB/s = 0.70 / 0.73 of the bytes it does move, in 0.41 / 0.45 of the
+//                                              unmasked pass's time
+// flux + rhs take 0.41 / 0.90 ms against 1.37 / 4.16 ms for the array-sized torch expressions of the example: 3.4x / 4.6x.
+// The right-hand side sits a fifth to a quarter below the copy -- 8 to 19 streams per lane against the copy's two; not tuned.
+constexpr int SC_MAX = 4;
+
+// flux[s][c][e] = u[c][e] * theta[s][e]: one multiply, so the correctly rounded product.  3 + NS loads and 3 NS stores per
+// point, V points (16 bytes, or one scalar: ps_lane_width) per lane, load and store; grid-stride.  flux overlaps no input.
+template <typename real, int V, int NS>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_scalar_flux_kernel(const real *__restrict__ u, const real *__restrict__ theta, real *__restrict__ flux, int64_t count) {
+  using vec = st_load<real, V>;
+  const int64_t nvec = count / V;                        // (count is a multiple of V)
+  for (int64_t i = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * PS_THREADS) {
+    const int64_t e = i * V;
+    vec a[3], t[NS];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a[c] = *reinterpret_cast<const vec *>(u + c * count + e);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) t[s] = *reinterpret_cast<const vec *>(theta + s * count + e);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        vec f;
+#pragma unroll
+        for (int j = 0; j < V; ++j) f.m[j] = a[c].m[j] * t[s].m[j];
+        *reinterpret_cast<vec *>(flux + (s * 3 + c) * count + e) = f;
+      }
+    }
+  }
+}
+
+struct sc_coef { double kappa[SC_MAX], grad[SC_MAX][3]; };          // by value in the launch, as st_scale
+
+// Per mode and scalar s, in the field's precision, kk = |k|^2 as ps_project_kernel forms it:
+//   a = kx F[s][0] + ky F[s][1] + kz F[s][2];   d[s] = -i a - (kappa[s] kk) theta[s] - (G[s][0] u0 + G[s][1] u1 + G[s][2] u2)
+// F = flux [NS][3][count], theta and d = [NS][count], u = [3][count]; d overlaps no input.  The mean-gradient term is the
+// instantiation MG: without it u is not a kernel operand that is ever loaded; with it u is loaded once per mode for all
+// NS scalars.  One pass: 4 NS (+ 3) complex loads and NS stores per mode.  One or two scalars are unrolled, their loads in
+// flight together; three and four are processed in turn (a loop over s: four loads in flight, kappa[s] and G[s] scalar loads
+// from the launch's arguments) -- unrolled, the masked instantiations of three and four scalars ran out of scalar registers
+// for the 16 + 3 + 4 array bases and the coefficients and spilled them; in turn every instantiation keeps 7 or 8 waves per SIMD.
+// The keep-predicate M, its evaluation before any load of the mode, the +0 stores of a truncated mode and the look-ahead of
+// the lane's next mode are those of ps_project_kernel, for the reasons given there.
+template <typename real, int NS, bool MG, typename M>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_scalar_rhs_kernel(cx<real> *__restrict__ d, const cx<real> *__restrict__ flux, const cx<real> *__restrict__ theta,
+                     const cx<real> *__restrict__ u, const real *__restrict__ k0, const real *__restrict__ k1,
+                     const real *__restrict__ k2, int64_t n1, int64_t n2, int64_t count, sc_coef coef, M keep) {
+  constexpr int TURNS = NS <= 2 ? NS : 1;                 // the unroll count of the loop over the scalars
+  const int64_t first = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x, stride = (int64_t)gridDim.x * PS_THREADS;
+  [[maybe_unused]] ps_mode<real, M> ahead = {};           // the lookups of the lane's next mode
+  if constexpr (!M::always)
+    if (first < count) ahead = ps_mode_of(first, n1, n2, k0, k1, k2, keep);
+  for (int64_t e = first; e < count; e += stride) {
+    const ps_mode<real, M> m = M::always ? ps_mode_of(e, n1, n2, k0, k1, k2, keep) : ahead;          // (a constant condition)
+    const real kx = m.kx, ky = m.ky, kz = m.kz;
+    if constexpr (!M::always) {
+      if (e + stride < count) ahead = ps_mode_of(e + stride, n1, n2, k0, k1, k2, keep);
+      if (!keep.kept(m.m, kx, ky, kz)) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) d[e + s * count] = {(real)0, (real)0};
+        continue;
+      }
+    }
+    const real kk = kx * kx + ky * ky + kz * kz;
+    [[maybe_unused]] cx<real> u0, u1, u2;                // held in registers over the scalars
+    if constexpr (MG) { u0 = u[e]; u1 = u[e + count]; u2 = u[e + 2 * count]; }
+#pragma unroll TURNS
+    for (int s = 0; s < NS; ++s) {
+      const cx<real> *__restrict__ f = flux + e + 3 * s * count;
+      const cx<real> f0 = f[0], f1 = f[count], f2 = f[2 * count], th = theta[e + s * count];
+      const real ax = kx * f0.x + ky * f1.x + kz * f2.x;
+      const real ay = kx * f0.y + ky * f1.y + kz * f2.y;
+      const real v = (real)coef.kappa[s] * kk;
+      cx<real> r = {ay - v * th.x, -ax - v * th.y};
+      if constexpr (MG) {
+        const real g0 = (real)coef.grad[s][0], g1 = (real)coef.grad[s][1], g2 = (real)coef.grad[s][2];
+        r.x -= g0 * u0.x + g1 * u1.x + g2 * u2.x;
+        r.y -= g0 * u0.y + g1 * u1.y + g2 * u2.y;
+      }
+      d[e + s * count] = r;
+    }
   }
 }
 
@@ -719,14 +820,17 @@ hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, do
   return hipGetLastError();
 }
 
+// elements per lane and load: `wide` (those of 16 bytes) where they divide `count` and every base is 16-byte aligned, else one
+inline int ps_lane_width(int64_t count, int wide, bool aligned16) { return (count % wide == 0 && aligned16) ? wide : 1; }
+
 // launch geometry of the reductions: V elements per lane and load, one contiguous chunk of whole steps of 256 V per workgroup
 struct sp_geom { int V; int64_t chunk; int nwg; };
 
-// wide = the elements of a 16-byte load (shell kernels: 1 or 2 modes; ps_stats: 2 or 4 reals), taken where they divide
-// `count` and every component of every field that is read starts 16-byte aligned; else one element per lane
+// wide = the elements of a 16-byte load (shell kernels: 1 or 2 modes; ps_stats: 2 or 4 reals), taken by ps_lane_width: where
+// they divide `count` and every component of every field that is read starts 16-byte aligned; else one element per lane
 sp_geom sp_geometry(int64_t count, int wide, bool aligned16) {
   sp_geom g;
-  g.V = (count % wide == 0 && aligned16) ? wide : 1;
+  g.V = ps_lane_width(count, wide, aligned16);
   const int64_t step = (int64_t)PS_THREADS * g.V;
   g.chunk = (count + SP_MAX_WG - 1) / SP_MAX_WG;
   g.chunk = (g.chunk + step - 1) / step * step;
@@ -778,6 +882,43 @@ hipError_t launch_ps_shell(const void *a, const void *b, int ncomp, int op, doub
   });
   if (e != hipSuccess) return e;
   return ps_launch(ps_spectrum_sum_kernel, (2 * nbins + PS_THREADS - 1) / PS_THREADS, 0, s, slabs, g.nwg, 2 * nbins, out);
+}
+
+template <typename real, int V>
+auto sc_flux_kernel(int ns) {
+  return ns == 1 ? ps_scalar_flux_kernel<real, V, 1> : ns == 2 ? ps_scalar_flux_kernel<real, V, 2>
+       : ns == 3 ? ps_scalar_flux_kernel<real, V, 3> : ps_scalar_flux_kernel<real, V, 4>;
+}
+
+// 1 <= ns <= SC_MAX; the lane width is that of launch_ps_stats, over all three bases
+hipError_t launch_ps_scalar_flux(const void *u, const void *theta, void *flux, int ns, int64_t count, int precision, hipStream_t s) {
+  const bool aligned = (uintptr_t)u % 16 == 0 && (uintptr_t)theta % 16 == 0 && (uintptr_t)flux % 16 == 0;
+  const int V = ps_lane_width(count, 16 / precision, aligned);
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    return ps_pointwise(V == W ? sc_flux_kernel<real, W>(ns) : sc_flux_kernel<real, 1>(ns), count / V, s, u, theta, flux, count);
+  });
+}
+
+template <typename real, bool MG, typename M>
+auto sc_rhs_kernel(int ns) {
+  return ns == 1 ? ps_scalar_rhs_kernel<real, 1, MG, M> : ns == 2 ? ps_scalar_rhs_kernel<real, 2, MG, M>
+       : ns == 3 ? ps_scalar_rhs_kernel<real, 3, MG, M> : ps_scalar_rhs_kernel<real, 4, MG, M>;
+}
+
+// 1 <= ns <= SC_MAX; u is read iff `mean_gradient`; masked = false: the ps_keep_all instantiation, `keep` is not looked at
+hipError_t launch_ps_scalar_rhs(void *d, const void *flux, const void *theta, const void *u, int ns, const sc_coef &coef,
+                                bool mean_gradient, const void *k0, const void *k1, const void *k2, int64_t n0, int64_t n1,
+                                int64_t n2, bool masked, ps_keep_mask keep, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    auto go = [&](auto kern, auto pred) { return ps_pointwise(kern, count, s, d, flux, theta, u, k0, k1, k2, n1, n2, count, coef, pred); };
+    if (masked)
+      return mean_gradient ? go(sc_rhs_kernel<real, true, ps_keep_mask>(ns), keep) : go(sc_rhs_kernel<real, false, ps_keep_mask>(ns), keep);
+    return mean_gradient ? go(sc_rhs_kernel<real, true, ps_keep_all>(ns), ps_keep_all()) : go(sc_rhs_kernel<real, false, ps_keep_all>(ns), ps_keep_all());
+  });
 }
 
 // gfft_ps_spectrum and gfft_ps_cospectrum behind their own argument checks (`bad`); fn names the caller in the messages.
@@ -956,6 +1097,46 @@ int gfft_ps_dealias(void *d_field, int ncomp, const void *d_k0, const void *d_k1
   if (int rc = check_device()) return rc;
   HIP_TRY(launch_ps_dealias(d_field, ncomp, d_k0, d_k1, d_k2, n0, n1, n2, ps_keep_mask{d_m0, d_m1, d_m2, kcut * kcut}, precision,
                             (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_scalar_flux(const void *d_u, const void *d_theta, void *d_flux, int nscalar, int64_t count, int precision,
+                        void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_u || !d_theta || !d_flux || nscalar < 1 || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_scalar_flux: bad argument");
+  static_assert(SC_MAX == 4, "the message names the limit");
+  if (nscalar > SC_MAX) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scalar_flux: more than 4 scalars");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_scalar_flux(d_u, d_theta, d_flux, nscalar, count, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_scalar_rhs(void *d_dtheta_hat, const void *d_flux_hat, const void *d_theta_hat, const void *d_u_hat, int nscalar,
+                       const double *kappa, const double *grad, const void *d_k0, const void *d_k1, const void *d_k2,
+                       const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
+                       int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_dtheta_hat || !d_flux_hat || !d_theta_hat || !d_k0 || !d_k1 || !d_k2 || n0 < 0 || n1 < 0 || n2 < 0 || !(kcut >= 0) ||
+      nscalar < 1 || !kappa || (grad && !d_u_hat) || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_scalar_rhs: bad argument");
+  static_assert(SC_MAX == 4, "the message names the limit");
+  if (nscalar > SC_MAX) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scalar_rhs: more than 4 scalars");
+  sc_coef coef = {};
+  for (int s = 0; s < nscalar; ++s) {
+    if (!std::isfinite(kappa[s]) || kappa[s] < 0) return fail(GFFT_ERR_INVALID, "gfft_ps_scalar_rhs: kappa must be finite and >= 0");
+    coef.kappa[s] = kappa[s];
+    for (int c = 0; grad && c < 3; ++c) {
+      if (!std::isfinite(grad[3 * s + c])) return fail(GFFT_ERR_INVALID, "gfft_ps_scalar_rhs: grad must be finite");
+      coef.grad[s][c] = grad[3 * s + c];
+    }
+  }
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scalar_rhs: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  const bool masked = d_m0 || d_m1 || d_m2 || kcut < (double)INFINITY;
+  HIP_TRY(launch_ps_scalar_rhs(d_dtheta_hat, d_flux_hat, d_theta_hat, d_u_hat, nscalar, coef, grad != nullptr, d_k0, d_k1, d_k2,
+                               n0, n1, n2, masked, ps_keep_mask{d_m0, d_m1, d_m2, kcut * kcut}, precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

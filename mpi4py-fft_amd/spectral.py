@@ -42,6 +42,20 @@ and the truncation that keeps the quadratic term free of aliasing errors over a 
                                 is stored as +0 and none of its six operands is loaded -- fewer bytes than without, no extra pass
     dealias(field, mask)        the truncation alone, in place (the initial condition): stores to truncated modes, reads nothing
 
+and the transport of passive scalars, d theta/dt + u . grad theta = kappa lap theta - G . u (G an imposed mean gradient), in
+flux form -- u . grad theta = div(u theta) for solenoidal u: one backward and three forward transforms per scalar, as the
+gradient form, and no stored gradient; up to four scalars (several Schmidt numbers) per call, the velocity read once for all:
+
+    scalar_flux(u, theta, out)  out[s][c] = u[c] * theta[s] (physical space): 3 + m loads and 3 m stores per point
+    scalar_rhs(dtheta_hat, flux_hat, theta_hat, kappa, mean_gradient, u_hat, dealias=mask)
+                                dtheta_hat[s] = -i K . flux_hat[s] - kappa[s] |K|^2 theta_hat[s] - G[s] . u_hat, the truncation
+                                fused in as in `project`; without a mean gradient u_hat is not read at all
+
+    The scalar's diagnostics are the functions above: `spectrum(theta_hat)[0]` is the variance spectrum (sums to
+    <theta^2>/2); the scalar dissipation is chi = 2 kappa <|grad theta|^2> = 2 * kappa * 2 * sum(spectrum(theta_hat)[1]);
+    the scalar flux <u_c theta> is sum(cospectrum(u_hat[c], theta_hat)[0]); `stats(theta)` gives the extrema; `rk_stage`
+    works on any count.
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -220,6 +234,40 @@ class SpectralOps:
         m, kcut = self._mask(mask)
         _lib.engine().ps_dealias(t, ncomp, self.K, m, self.shape, kcut, precision)
         return field
+
+    def scalar_rhs(self, dtheta_hat, flux_hat, theta_hat, kappa, mean_gradient=None, u_hat=None, dealias=None):
+        """The right-hand side of m <= 4 passive scalars in flux form, one pass:
+            dtheta_hat[s] = -1j * (K . flux_hat[s]) - kappa[s] * |K|^2 * theta_hat[s] - mean_gradient[s] . u_hat
+        theta_hat and dtheta_hat are [m] + spectral shape or, one scalar, the spectral shape; flux_hat is the transform of
+        `scalar_flux`'s output, [m][3] + spectral shape (or [3] + spectral shape).  kappa is a float or m floats, finite and
+        >= 0.  mean_gradient is three floats shared by all scalars or m x 3 floats and requires u_hat ([3] + spectral
+        shape); without it u_hat, if given, is not read.  dealias as in `project`: a kept mode gets bit for bit the result
+        without it, a truncated mode becomes +0 and nothing of it is loaded.  dtheta_hat must not overlap an input.
+        Returns dtheta_hat.  Nothing synchronises or allocates."""
+        tth, ns, precision = self._field(theta_hat)
+        td, nd, pd = self._field(dtheta_hat)
+        assert ns <= 4, 'at most 4 scalars per call'
+        assert (nd, pd) == (ns, precision) and td.dim() == tth.dim(), 'dtheta_hat and theta_hat differ in shape or precision'
+        tf = _t(flux_hat)
+        assert tuple(tf.shape) == tuple(tth.shape[:-3]) + (3,) + self.shape, (tuple(tf.shape), tuple(tth.shape))
+        assert tf.is_contiguous(), 'flux_hat is not contiguous'
+        tf, nf, pf = self._field(tf.view((3 * ns,) + self.shape))
+        assert (nf, pf) == (3 * ns, precision), 'flux_hat and theta_hat differ in precision'
+        kap = np.asarray(kappa, dtype=np.float64)
+        kap = np.full(ns, float(kap)) if kap.ndim == 0 else kap
+        assert kap.shape == (ns,) and np.isfinite(kap).all() and (kap >= 0).all(), kappa
+        tu = grad = None
+        if u_hat is not None:
+            tu, nu_, pu = self._field(u_hat)
+            assert (nu_, pu) == (3, precision) and tu.dim() == 4, 'u_hat is a three-component field of the same precision'
+        if mean_gradient is not None:
+            assert tu is not None, 'a mean gradient needs u_hat'
+            grad = np.asarray(mean_gradient, dtype=np.float64)
+            grad = np.tile(grad, (ns, 1)) if grad.shape == (3,) else grad
+            assert grad.shape == (ns, 3) and np.isfinite(grad).all(), mean_gradient
+        m, kcut = ((None, None, None), np.inf) if dealias is None else self._mask(dealias)
+        _lib.engine().ps_scalar_rhs(td, tf, tth, tu, ns, kap, grad, self.K, m, self.shape, kcut, precision)
+        return dtheta_hat
 
     def forcing_gain(self, u_hat, eps, band, gain_max=np.inf, dk=None, out=None):
         """The gain g of the band forcing f_hat = g u_hat (`project(..., force=(g, band))`) that injects energy at the rate
@@ -490,6 +538,24 @@ def cross(a, b, out):
     assert np.dtype(a.dtype).kind == 'f'
     count = int(np.prod(a.shape[1:], dtype=np.int64))
     _lib.engine().ps_cross(_t(a), _t(b), _t(out), count, _prec(a))
+    return out
+
+
+def scalar_flux(u, theta, out):
+    """out[s][c] = u[c] * theta[s]: the advective flux of m <= 4 scalars by one velocity, which is read once for all of them.
+    u is a real field [3] + physical shape; theta is [m] + physical shape and out [m][3] + physical shape, or, for one
+    scalar, the physical shape and [3] + physical shape; all contiguous, of one precision, out overlapping neither input.
+    One multiply per value: the correctly rounded product.  Returns out."""
+    tu, tt, to = _t(u), _t(theta), _t(out)
+    pshape = tuple(tu.shape[1:])
+    assert tu.shape[0] == 3 and tu.dim() >= 2 and tu.dtype in (torch.float32, torch.float64)
+    lead = () if tuple(tt.shape) == pshape else (int(tt.shape[0]),)
+    assert tuple(tt.shape) == lead + pshape and tuple(to.shape) == lead + (3,) + pshape, (tuple(tu.shape), tuple(tt.shape), tuple(to.shape))
+    assert tu.dtype == tt.dtype == to.dtype and tu.is_contiguous() and tt.is_contiguous() and to.is_contiguous()
+    ns = lead[0] if lead else 1
+    assert 1 <= ns <= 4, 'at most 4 scalars per call'
+    count = int(np.prod(pshape, dtype=np.int64))
+    _lib.engine().ps_scalar_flux(tu, tt, to, ns, count, 8 if tu.dtype == torch.float64 else 4)
     return out
 
 
