@@ -412,7 +412,30 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    the result of the call without a mask.  d_dtheta_hat must not overlap an input.  GFFT_ERR_INVALID
  *                    (before a device is touched) as gfft_ps_project_dealiased and for nscalar < 1, a null kappa, a kappa that
  *                    is negative or not finite, grad without d_u_hat, a grad that is not finite; nscalar > 4 and n1, n2 > 2^30
- *                    are GFFT_ERR_UNSUPPORTED.  Only enqueues and allocates nothing, so it can be captured. */
+ *                    are GFFT_ERR_UNSUPPORTED.  Only enqueues and allocates nothing, so it can be captured.
+ *   gfft_ps_rk_stage_if  one Runge-Kutta stage with an integrating factor: the linear term -nu |K|^2 u_hat (viscosity, diffusion)
+ *                    is integrated exactly, so nu k_max^2 h does not limit the step (explicit RK4 needs it <= 2.785); call
+ *                    gfft_ps_project with nu = 0 and gfft_ps_scalar_rhs with kappa = 0 for the right-hand side.  On complex
+ *                    fields [ncomp][n0][n1][n2], ncomp = 1 ... 4, per mode and component c, in the field's precision, with
+ *                    kk = k0 k0 + k1 k1 + k2 k2 as gfft_ps_project forms it, hh = (real)(h / 2), cbh = (real)(cb h), cah = (real)(ca h):
+ *                      E = exp(-(((real)nu[c] kk) hh));   E^2 = E * E;   E^0 = 1 (the constant, whatever E is)
+ *                      u  = E^q0 u0 + (cbh E^qd) du       (skipped when d_u is NULL; q0, qd are still checked)
+ *                      u1 = E^q1 u1 + (cah E^qa) du
+ *                    each update one fused multiply-add on a rounded product, fma(cbh E^qd, du, E^q0 u0), per real part.  The
+ *                    powers are 0, 1 or 2.  Classical IFRK4 with u0 = u1 = u_n before the first stage is, as (cb, ca, q0, qd,
+ *                    q1, qa):  (1/2, 1/6, 1, 1, 2, 2), (1/2, 1/3, 1, 0, 0, 1), (1, 1/3, 2, 1, 0, 1) and, d_u NULL,
+ *                    (-, 1/6, -, -, 0, 0); u1 is then u_{n+1}.  nu (ncomp HOST doubles) travels by value in the launch; all
+ *                    entries equal (a velocity): one exp per mode; otherwise one per component (scalars of several Schmidt
+ *                    numbers in one call); a call whose powers are all 0 evaluates none.  h = d_dt[0], read on the device
+ *                    when the kernel runs (a captured launch follows gfft_ps_timestep), or, d_dt NULL, `h`: the same double
+ *                    gives the same bits both ways.  With every nu[c] = 0 the result is bit for bit that of
+ *                    gfft_ps_rk_stage(..., cb * h, ca * h, ...).  A zero mode stays zero; a factor that underflows to 0 is the
+ *                    correct result.  d_u0 and d_du are only read; d_u and d_u1 overlap nothing else.  One pass: the three loads
+ *                    and two stores per value of gfft_ps_rk_stage and three cached wavenumber lookups per mode.
+ *                    GFFT_ERR_INVALID (before a device is touched) for a null d_u1, d_du, nu or d_k*, d_u without d_u0,
+ *                    ncomp < 1, negative extents, a nu that is negative or not finite, a power outside 0 ... 2, a non-finite h
+ *                    with d_dt NULL, precision; ncomp > 4 and n1, n2 > 2^30 are GFFT_ERR_UNSUPPORTED.  Only enqueues and
+ *                    allocates nothing, so it can be captured. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
@@ -454,6 +477,10 @@ int gfft_ps_scalar_rhs(void *d_dtheta_hat /* [m] */, const void *d_flux_hat /* [
                        const void *d_k0, const void *d_k1, const void *d_k2,
                        const unsigned char *d_m0, const unsigned char *d_m1, const unsigned char *d_m2,
                        int64_t n0, int64_t n1, int64_t n2, double kcut, int precision, void *stream);
+int gfft_ps_rk_stage_if(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int ncomp,
+                        const double *nu /* host, ncomp */, const void *d_k0, const void *d_k1, const void *d_k2,
+                        int64_t n0, int64_t n1, int64_t n2, double cb, double ca, int q0, int qd, int q1, int qa,
+                        double h, const double *d_dt /* NULL: use h */, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

@@ -92,6 +92,8 @@ def _declare(lib):
         'gfft_ps_scalar_flux': (c.c_int, [vp, vp, vp, c.c_int, c.c_int64, c.c_int, vp]),
         'gfft_ps_scalar_rhs': (c.c_int, [vp, vp, vp, vp, c.c_int, c.POINTER(c.c_double), c.POINTER(c.c_double), vp, vp, vp,
                                          vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int, vp]),
+        'gfft_ps_rk_stage_if': (c.c_int, [vp, vp, vp, vp, c.c_int, c.POINTER(c.c_double), vp, vp, vp, c.c_int64, c.c_int64, c.c_int64,
+                                          c.c_double, c.c_double, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -521,6 +523,20 @@ class HipEngine:
                                        int(nscalar), kap, g, k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
                                        *[None if t is None else t.data_ptr() for t in m],
                                        shape[0], shape[1], shape[2], float(kcut), precision, current_stream()))
+
+    def ps_rk_stage_if(self, tu, tu0, tu1, tdu, ncomp, nu, k, shape, cb, ca, powers, h, tdt, precision):
+        """gfft_ps_rk_stage_if: tu = E^q0 tu0 + cb h E^qd tdu (tu None: skipped), tu1 = E^q1 tu1 + ca h E^qa tdu on complex
+        [ncomp] + shape, E = exp(-nu[c] |K|^2 h / 2); nu = ncomp host floats, powers = (q0, qd, q1, qa) in 0 ... 2; h = tdt[0]
+        (device double) or, tdt None, the float `h`."""
+        for t in (tu, tu0, tu1, tdu, tdt):
+            if t is not None:
+                self.require_device(t)
+        v = (ctypes.c_double * int(ncomp))(*[float(x) for x in nu])
+        q0, qd, q1, qa = (int(q) for q in powers)
+        check(lib().gfft_ps_rk_stage_if(None if tu is None else tu.data_ptr(), None if tu0 is None else tu0.data_ptr(),
+                                        tu1.data_ptr(), tdu.data_ptr(), int(ncomp), v, k[0].data_ptr(), k[1].data_ptr(),
+                                        k[2].data_ptr(), shape[0], shape[1], shape[2], float(cb), float(ca), q0, qd, q1, qa,
+                                        float(h), None if tdt is None else tdt.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

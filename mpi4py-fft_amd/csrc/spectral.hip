@@ -2,7 +2,8 @@
 // the file), their launchers and their kernels, each one pass over its operands.
 //   * pointwise (the reference's examples/spectral_dns_solver.py:65-91 does these with numpy expressions, one temporary per
 //     operator): i K x u_hat, u x w, pressure projection + viscous term (with a band forcing and the dealiasing
-//     truncation fused in where asked for), the truncation on its own, the Runge-Kutta stage update, the time-step controller and the forcing gain; for passive
+//     truncation fused in where asked for), the truncation on its own, the Runge-Kutta stage update (plain, and with the integrating factor of the
+//     viscous term), the time-step controller and the forcing gain; for passive
 //     scalars the flux u theta and the right-hand side -i K . (u theta)^ - kappa |K|^2 theta^ - G . u^.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
@@ -263,6 +264,81 @@ ps_rk_dt_kernel(real *__restrict__ u, const real *__restrict__ u0, real *__restr
   ps_rk_body(u, u0, u1, du, count, (real)(cb * h), (real)(ca * h));
 }
 
+// ---- integrating-factor Runge-Kutta stage: the linear term -nu |K|^2 u integrated exactly ---------------------------------
+// With v = exp(nu |K|^2 t) u_hat only the nonlinear term sees RK4, so nu k_max^2 h no longer limits the step.  Per mode and
+// component c of a complex field [ncomp][count], kk = |k|^2 as ps_project_kernel forms it in the field's precision:
+//   E = exp(-(((real)nu_c kk) hh)), hh = (real)(h / 2);   E^2 = E * E;   E^0 = the constant 1
+//   u  = E^q0 u0 + (cbh E^qd) du   (skipped when u is null);   u1 = E^q1 u1 + (cah E^qa) du,   cbh = (real)(cb h), cah = (real)(ca h)
+// each update one explicit fused multiply-add on a rounded product, per real part: fma(cbh E^qd, du, E^q0 u0).  With nu = 0
+// every power is exactly 1 and these are the multiply-adds the compiler makes of ps_rk_body's u0 + cb d and u1 += ca d: the
+// same bits.  The powers q in {0, 1, 2} are the same in every lane (selects between 1, E and E * E); a call whose powers
+// are all 0 -- the last stage of IFRK4 -- evaluates no exp.  A zero mode stays zero; a factor that underflows to 0 is the
+// correct result; E^0 is 1 whatever E is.
+// UNIFORM (every nu_c equal: a velocity): one exp per mode for all components; otherwise one per component (several scalars
+// of different Schmidt numbers in one call).  The components are taken in turn, three loads and two stores of 16 bytes
+// (8 in fp32) each: the 80 bytes per complex value of ps_rk_kernel, plus three cached wavenumber lookups per mode.
+// Pointwise, grid-stride, a lane's mode is its flat index; no LDS, no atomics.  (Registers: in the list above ps_stats_kernel.)
+constexpr int IF_MAX_COMP = 4;
+
+struct ps_if_nu { double v[IF_MAX_COMP]; };          // by value in the launch, as st_scale
+struct ps_if_pow { int q0, qd, q1, qa; };
+
+template <typename real> struct ps_if_step { real hh, cbh, cah; };
+
+// The step of a launch: h = dt[0] where `dt` is given (read when the kernel runs: a captured launch follows what
+// ps_timestep_kernel wrote in front of it), else h_val; the three products are formed in double and rounded once either way,
+// so the same double gives the same bits.
+struct ps_if_args {
+  double cb, ca, h_val;
+  const double *dt;
+  template <typename real> __device__ __forceinline__ ps_if_step<real> bind() const {
+    const double h = dt ? dt[0] : h_val;
+    return {(real)(0.5 * h), (real)(cb * h), (real)(ca * h)};
+  }
+};
+
+__device__ __forceinline__ float ps_exp(float x) { return expf(x); }
+__device__ __forceinline__ double ps_exp(double x) { return exp(x); }
+__device__ __forceinline__ float ps_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double ps_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <typename real>
+__device__ __forceinline__ real ps_if_power(int q, real e, real e2) { return q == 0 ? (real)1 : q == 1 ? e : e2; }
+
+template <typename real, bool UNIFORM>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_rk_if_kernel(cx<real> *__restrict__ u, const cx<real> *__restrict__ u0, cx<real> *__restrict__ u1,
+                const cx<real> *__restrict__ du, int ncomp, const real *__restrict__ k0, const real *__restrict__ k1,
+                const real *__restrict__ k2, int64_t n1, int64_t n2, int64_t count, ps_if_nu nu, ps_if_pow q, ps_if_args arg) {
+  const ps_if_step<real> st = arg.template bind<real>();
+  const bool decays = (u && (q.q0 | q.qd)) || (q.q1 | q.qa);          // some power is not 0: the same in every lane
+  for (int64_t e = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e < count; e += (int64_t)gridDim.x * PS_THREADS) {
+    real kk = 0;
+    if (decays) {
+      const ps_mode<real, ps_keep_all> m = ps_mode_of(e, n1, n2, k0, k1, k2, ps_keep_all());
+      kk = m.kx * m.kx + m.ky * m.ky + m.kz * m.kz;
+    }
+    real f0 = 1, cd = st.cbh, f1 = 1, ad = st.cah;
+    for (int c = 0; c < ncomp; ++c) {
+      if (decays && (!UNIFORM || c == 0)) {
+        const real E = ps_exp(-(((real)nu.v[c] * kk) * st.hh));
+        const real E2 = E * E;
+        f0 = ps_if_power(q.q0, E, E2);
+        cd = st.cbh * ps_if_power(q.qd, E, E2);
+        f1 = ps_if_power(q.q1, E, E2);
+        ad = st.cah * ps_if_power(q.qa, E, E2);
+      }
+      const int64_t i = e + c * count;
+      const cx<real> d = du[i], a = u1[i];
+      if (u) {
+        const cx<real> b = u0[i];
+        u[i] = {ps_fma(cd, d.x, f0 * b.x), ps_fma(cd, d.y, f0 * b.y)};
+      }
+      u1[i] = {ps_fma(ad, d.x, f1 * a.x), ps_fma(ad, d.y, f1 * a.y)};
+    }
+  }
+}
+
 // dt[0] = clamp(cfl / stats[0], dt_min, dt_max) (dt_max where the rate is zero or not finite); dt[1] += dt[0]
 __global__ void ps_timestep_kernel(const double *__restrict__ stats, double cfl, double dt_min, double dt_max,
                                    double *__restrict__ dt) {
@@ -512,6 +588,7 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // ps_scalar_rhs_kernel<double / float, NS, mean gradient?, mask?>, every instantiation 8 waves per SIMD but <double, 2, yes, no>:
 //   NS = 1: 36 / 26 plain, 48 / 38 with the gradient, 48 / 34 masked, 60 / 46 with both;   NS = 2: 56 / 40, 66 / 56 (7 waves in
 //   fp64), 52 / 50, 64 / 56;   NS = 3 and 4 (the scalars in turn): 40 / 26, 52 / 34, 46 / 36, 60 / 42.
+// ps_rk_if_kernel<double / float, UNIFORM> 72 / 44 (7 and 8 waves per SIMD), <double / float, per component> 60 / 30 (8 waves).
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -815,6 +892,20 @@ hipError_t launch_ps_rk_dt(void *u, const void *u0, void *u1, const void *du, in
       precision, [&](auto r) { return ps_pointwise(ps_rk_dt_kernel<decltype(r)>, count, s, u, u0, u1, du, count, cb, ca, dt); });
 }
 
+// 1 <= ncomp <= IF_MAX_COMP; every nu equal: the instantiation with one exp per mode
+hipError_t launch_ps_rk_if(void *u, const void *u0, void *u1, const void *du, int ncomp, const ps_if_nu &nu, const void *k0,
+                           const void *k1, const void *k2, int64_t n0, int64_t n1, int64_t n2, ps_if_pow q, ps_if_args arg,
+                           int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  bool uniform = true;
+  for (int c = 1; c < ncomp; ++c) uniform = uniform && nu.v[c] == nu.v[0];
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    return ps_pointwise(uniform ? ps_rk_if_kernel<real, true> : ps_rk_if_kernel<real, false>, count, s, u, u0, u1, du, ncomp, k0,
+                        k1, k2, n1, n2, count, nu, q, arg);
+  });
+}
+
 hipError_t launch_ps_timestep(const double *stats, double cfl, double dt_min, double dt_max, double *dt, hipStream_t s) {
   hipLaunchKernelGGL(ps_timestep_kernel, dim3(1), dim3(64), 0, s, stats, cfl, dt_min, dt_max, dt);
   return hipGetLastError();
@@ -1039,6 +1130,30 @@ int gfft_ps_rk_stage_dt(void *d_u, const void *d_u0, void *d_u1, const void *d_d
     return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_dt: bad argument");
   if (int rc = check_device()) return rc;
   HIP_TRY(launch_ps_rk_dt(d_u, d_u0, d_u1, d_du, count, cb, ca, d_dt, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_rk_stage_if(void *d_u, const void *d_u0, void *d_u1, const void *d_du, int ncomp, const double *nu, const void *d_k0,
+                        const void *d_k1, const void *d_k2, int64_t n0, int64_t n1, int64_t n2, double cb, double ca, int q0,
+                        int qd, int q1, int qa, double h, const double *d_dt, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  const auto power = [](int q) { return q >= 0 && q <= 2; };
+  if ((d_u && !d_u0) || !d_u1 || !d_du || !nu || !d_k0 || !d_k1 || !d_k2 || ncomp < 1 || n0 < 0 || n1 < 0 || n2 < 0 ||
+      !power(q0) || !power(qd) || !power(q1) || !power(qa) || (!d_dt && !std::isfinite(h)) ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_if: bad argument");
+  static_assert(IF_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > IF_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_rk_stage_if: more than 4 components");
+  ps_if_nu v = {};
+  for (int c = 0; c < ncomp; ++c) {
+    if (!std::isfinite(nu[c]) || nu[c] < 0) return fail(GFFT_ERR_INVALID, "gfft_ps_rk_stage_if: nu must be finite and >= 0");
+    v.v[c] = nu[c];
+  }
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_rk_stage_if: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_rk_if(d_u, d_u0, d_u1, d_du, ncomp, v, d_k0, d_k1, d_k2, n0, n1, n2, ps_if_pow{q0, qd, q1, qa},
+                          ps_if_args{cb, ca, h, d_dt}, precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

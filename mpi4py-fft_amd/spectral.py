@@ -56,6 +56,19 @@ gradient form, and no stored gradient; up to four scalars (several Schmidt numbe
     the scalar flux <u_c theta> is sum(cospectrum(u_hat[c], theta_hat)[0]); `stats(theta)` gives the extrema; `rk_stage`
     works on any count.
 
+and the time integrator that survives a stiff linear term -- a well-resolved run's nu k_max^2, a scalar of low Schmidt number,
+hyperviscosity: explicit RK4 is stable on the negative real axis only for lambda h <= 2.785, and `timestep` limits the step by
+the advective rate alone.  With the integrating factor v = exp(nu |K|^2 t) u_hat the linear term is integrated exactly and only
+the nonlinear term sees RK4:
+
+    rk_stage_if(u, u0, u1, du, nu, cb, ca, powers, h= or dt=)
+                                u = E^q0 u0 + cb h E^qd du (skipped when u is None);  u1 = E^q1 u1 + ca h E^qa du, with
+                                E = exp(-nu |K|^2 h / 2) per mode and powers = (q0, qd, q1, qa) in {0, 1, 2}: the pass of `rk_stage`
+                                and one exp per mode; nu a float (a velocity) or one per component (several scalars)
+    IFRK4                       the four rows (cb, ca, q0, qd, q1, qa) of classical integrating-factor RK4: u0 and u1 start as copies
+                                of u_hat, the right-hand sides come from `project(..., nu=0)` / `scalar_rhs(..., kappa=0)`, the
+                                last row goes with u=None, and u1 ends as the new u_hat
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -269,6 +282,44 @@ class SpectralOps:
         _lib.engine().ps_scalar_rhs(td, tf, tth, tu, ns, kap, grad, self.K, m, self.shape, kcut, precision)
         return dtheta_hat
 
+    def rk_stage_if(self, u, u0, u1, du, nu, cb, ca, powers, h=None, dt=None):
+        """One Runge-Kutta stage with the integrating factor of the linear term -nu |K|^2 u, one pass over the four fields:
+            u  = E^q0 * u0 + cb * h * E^qd * du        (skipped when u is None; u0 may then be None too)
+            u1 = E^q1 * u1 + ca * h * E^qa * du
+        with E = exp(-nu |K|^2 h / 2) per mode and powers = (q0, qd, q1, qa), each 0, 1 or 2 (E^2 is E * E, E^0 the constant
+        1); `IFRK4` holds the four rows of the classical scheme.  The fields are [m] + spectral shape, m <= 4, or, a scalar
+        field, the spectral shape; nu is a float or m floats, finite and >= 0 (all equal: one exp per mode).  Exactly one of
+        h (a float) and dt (a device double tensor whose element 0 the kernel reads when it runs: `timestep(out=)` writes
+        one) gives the step; both give the same bits for the same double.  With nu = 0 the result is bit for bit that of
+        `rk_stage(u, u0, u1, du, cb * h, ca * h)`.  Returns u1.  Nothing synchronises or allocates."""
+        t1, ncomp, precision = self._field(u1)
+        td, nd, pd = self._field(du)
+        assert ncomp <= 4, 'at most 4 components per call'
+        assert (nd, pd) == (ncomp, precision) and td.dim() == t1.dim(), 'du and u1 differ in shape or precision'
+        assert u is None or u0 is not None, 'u needs u0'
+        both = []
+        for f in (u, u0):
+            t = None
+            if f is not None:
+                t, nf, pf = self._field(f)
+                assert (nf, pf) == (ncomp, precision) and t.dim() == t1.dim(), 'the fields differ in shape or precision'
+            both.append(t)
+        tu, tu0 = both
+        v = np.asarray(nu, dtype=np.float64)
+        v = np.full(ncomp, float(v)) if v.ndim == 0 else v
+        assert v.shape == (ncomp,) and np.isfinite(v).all() and (v >= 0).all(), nu
+        powers = tuple(powers)
+        assert len(powers) == 4 and all(int(q) == q and 0 <= q <= 2 for q in powers), powers
+        assert (h is None) != (dt is None), 'exactly one of h and dt'
+        tdt = None
+        if dt is not None:
+            tdt, h = _t(dt), 0.0
+            assert tdt.dtype == torch.float64 and tdt.numel() >= 1 and tdt.is_contiguous()
+        else:
+            assert np.isfinite(h), h
+        _lib.engine().ps_rk_stage_if(tu, tu0, t1, td, ncomp, v, self.K, self.shape, cb, ca, powers, float(h), tdt, precision)
+        return u1
+
     def forcing_gain(self, u_hat, eps, band, gain_max=np.inf, dk=None, out=None):
         """The gain g of the band forcing f_hat = g u_hat (`project(..., force=(g, band))`) that injects energy at the rate
         eps: g = min(eps / (2 E_f), gain_max) with E_f = sum of E(k) over shells band = (blo, bhi) of `spectrum(u_hat)`,
@@ -481,6 +532,15 @@ class SpectralOps:
         self.stats(t, out=st, reduce=False)
         _lib.engine().ps_timestep(st, cfl, dt_min, dt_max, out)
         return out
+
+
+# Classical RK4 on v = exp(lambda t) u_hat, lambda = nu |K|^2, written for u_hat itself; E = exp(-lambda h / 2).  Rows
+# (cb, ca, q0, qd, q1, qa) of `SpectralOps.rk_stage_if`; u0 = u1 = u_n before row 1, which turns u1 into E^2 u_n; row 4 is
+# called with u=None (its cb, q0 and qd do not enter the result) and leaves u_{n+1} in u1.
+IFRK4 = ((1. / 2., 1. / 6., 1, 1, 2, 2),
+         (1. / 2., 1. / 3., 1, 0, 0, 1),
+         (1., 1. / 3., 2, 1, 0, 1),
+         (0., 1. / 6., 0, 0, 0, 0))
 
 
 def timestep_from_rate(rate, cfl, dt_max, dt_min=0.0):
