@@ -41,6 +41,13 @@ run, a scalar of low Schmidt number) no longer limits.  Here nu |k|^2 dt is 2e-5
 largest one, and the two integrators agree far below the
 seventh digit: the energy after 10 steps at 64^3 is IF_ENERGY below (measured on one MI355X).
 
+`gradients=True` reads the small scales of the final state: `SpectralOps.gradient(U_hat, .)` forms all nine i K_j U_hat_i in one pass,
+nine backward transforms give A_ij = d u_i / d x_j, and `SpectralOps.gradient_stats` reduces one read of A to the 20 sums that
+`spectral.gradient_moments` turns into dissipation, enstrophy, derivative skewness and flatness, <Q>, <R> and the Betchov ratio
+<w S w> / (-4/3 <S S S>), which is 1 for a resolved, alias-free run.  The Taylor-Green vortex starts with zero skewness; after 10
+steps at 64^3 with dealias='2/3' the longitudinal skewness is GRADIENT_SKEWNESS below (measured on one MI355X; the reference has
+no such diagnostic).
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -57,11 +64,12 @@ import torch
 DEALIASED_ENERGY = 0.124953117516743          # solve(dealias='2/3'), M = 6, 10 steps
 SCALAR_VARIANCE = 0.126225641497587           # 'scalar_variance' of solve(scalar=(nu, (1, 0, 0))), M = 6, 10 steps
 IF_ENERGY = 0.124953117516741                 # solve(integrator='ifrk4'), M = 6, 10 steps
+GRADIENT_SKEWNESS = -0.064835990474654        # 'gradients'.skewness of solve(gradients=True, dealias='2/3'), M = 6, 10 steps
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
           transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
-          scalar=None, integrator='rk4'):
+          scalar=None, integrator='rk4', gradients=False):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -85,7 +93,11 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     <u_c theta> (fused: sum(cospectrum(U_hat[c], T_hat)[0])).  The velocity, and so the returned energy, is unchanged.
     integrator='ifrk4' (fused path): integrating-factor RK4 -- the right-hand sides are formed with nu = 0 and kappa = 0 and
     the stages are `SpectralOps.rk_stage_if` with nu / kappa, following `spectral.IFRK4`; it combines with every option
-    above.  'rk4' (the default) is the explicit scheme."""
+    above.  'rk4' (the default) is the explicit scheme.
+    gradients=True: a dict passed as `stats` receives 'gradients', the `spectral.gradient_moments` (with nu) of the velocity-gradient
+    tensor of the final state -- on the fused path from `SpectralOps.gradient`, nine backward transforms and
+    `SpectralOps.gradient_stats`, on the fused=False path from array-sized torch expressions (the A/B baseline).  It reads the
+    final U_hat only and combines with every option above; the diagnostic itself runs once, outside any captured step."""
     from mpi4py_fft_amd import PFFT, newDistArray, spectral
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -345,6 +357,42 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                   % (band + (f_eps, 'device' if device_gain else 'host', last_gain[0], last_gain[1], 2 * last_gain[0] * last_gain[1])))
     if scalar is not None and verbose and world.Get_rank() == 0:
         print('  scalar (kappa = %g, G = %s): variance %.15f, flux <u theta> = (%.6e, %.6e, %.6e)' % ((kappa, G, variance) + tuple(sflux)))
+    if gradients:
+        npts = N[0] * N[1] * N[2]
+        if fused:
+            A_hat, A = newDistArray(FFT, rank=2), newDistArray(FFT, False, rank=2)
+            ops.gradient(U_hat, A_hat)                        # all nine i K_j U_hat_i in one pass
+            for i in range(3):
+                for j in range(3):
+                    FFT.backward(A_hat[i][j], A[i][j])
+            gs = ops.gradient_stats(A)                        # rank-reduced; one read of A, no temporaries
+        else:
+            a = torch.empty((3, 3) + tuple(u.shape[1:]), dtype=u.dtype, device=dev)
+            for i in range(3):
+                for j in range(3):
+                    bwd(1j * K[j] * uh[i], a[i][j])
+            at = a.transpose(0, 1)
+            S = (a + at) / 2
+            w = torch.stack([a[2][1] - a[1][2], a[0][2] - a[2][0], a[1][0] - a[0][1]])
+            div = a[0][0] + a[1][1] + a[2][2]
+            ss, ww = (S * S).sum((0, 1)), (w * w).sum(0)
+            Q = (div * div - (a * at).sum((0, 1))) / 2
+            R = -torch.linalg.det(a.permute(2, 3, 4, 0, 1))
+            sss = torch.einsum('ijxyz,jkxyz,kixyz->xyz', S, S, S)
+            wsw = torch.einsum('ixyz,ijxyz,jxyz->xyz', w, S, w)
+            diag = torch.stack([a[0][0], a[1][1], a[2][2]])
+            off = torch.stack([a[0][1], a[1][0], a[0][2], a[2][0], a[1][2], a[2][1]])
+            local = [ss.max(), ww.max(), div.abs().max(), (div * div).sum(), ss.sum(), ww.sum(), (ss * ss).sum(), (ww * ww).sum(),
+                     (ss * ww).sum(), Q.sum(), R.sum(), (Q * Q).sum(), (R * R).sum(), sss.sum(), wsw.sum(), (diag ** 2).sum(),
+                     (diag ** 3).sum(), (diag ** 4).sum(), (off ** 2).sum(), (off ** 4).sum()]
+            parts = world.allgather_obj([float(x.item()) for x in local])
+            gs = np.array([max(q[n] for q in parts) if n < 3 else sum(q[n] for q in parts) for n in range(20)])
+        gm = spectral.gradient_moments(gs, npts, nu)
+        if stats is not None:
+            stats.update(gradients=gm)
+        if verbose and world.Get_rank() == 0:
+            print('  gradients: dissipation %.9e, enstrophy %.9e, skewness %.6e, flatness %.6f, Betchov ratio %.12f, rms div %.1e'
+                  % (gm.dissipation, gm.enstrophy, gm.skewness, gm.flatness, gm.betchov, gm.div_rms))
     if transfer:
         assert fused and not spectrum
         compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term
@@ -435,6 +483,13 @@ if __name__ == '__main__':
         assert abs(eg - ei) <= 1e-12, (eg, ei)
         eg = solve(w, verbose=True, integrator='ifrk4', graph=True, cfl=0.05, device_dt=True)
         assert eg == eia, (eg, eia)                          # the device-side step is the same arithmetic
+    sf, sb = {}, {}
+    solve(w, verbose=True, gradients=True, dealias='2/3', stats=sf)          # the small scales of the final state
+    solve(w, verbose=True, gradients=True, dealias='2/3', stats=sb, fused=False)
+    gf, gb = sf['gradients'], sb['gradients']
+    assert abs(gf.skewness - gb.skewness) <= 1e-10 * abs(gf.skewness) and abs(gf.dissipation - gb.dissipation) <= 1e-10 * gf.dissipation, (gf, gb)
+    assert abs(gf.skewness - GRADIENT_SKEWNESS) <= 1e-9 * abs(GRADIENT_SKEWNESS) and abs(gf.betchov - 1) <= 1e-9, (gf, GRADIENT_SKEWNESS)
+    assert abs(gf.strain - gf.enstrophy) <= 1e-12 * gf.strain and gf.div_rms <= 1e-12, gf
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)

@@ -435,9 +435,57 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    GFFT_ERR_INVALID (before a device is touched) for a null d_u1, d_du, nu or d_k*, d_u without d_u0,
  *                    ncomp < 1, negative extents, a nu that is negative or not finite, a power outside 0 ... 2, a non-finite h
  *                    with d_dt NULL, precision; ncomp > 4 and n1, n2 > 2^30 are GFFT_ERR_UNSUPPORTED.  Only enqueues and
- *                    allocates nothing, so it can be captured. */
+ *                    allocates nothing, so it can be captured.
+ *   The velocity-gradient tensor A_ij = d u_i / d x_j and the small-scale statistics that are functions of it: the spectral
+ *   gradient of up to four fields in one pass, nine backward transforms, and ONE read of A that reduces it to 20 numbers.
+ *   gfft_ps_gradient out[c][j] = i k_j f[c] on complex fields: d_f_hat = [ncomp][n0][n1][n2], d_out = [ncomp][3][n0][n1][n2] (for
+ *                    ncomp = 3 the layout of newDistArray(fft, rank=2)), ncomp = 1 ... 4.  Formed as {-(k_j * Im f), k_j * Re f} in
+ *                    the field's precision: each part is ONE multiply, the correctly rounded product, so the result is defined
+ *                    bit for bit, the sign of a zero included; a NaN stays in its own mode and part.  K is applied as given, the
+ *                    convention of gfft_ps_curl: no special case for the Nyquist columns, whose derivative is not real -- the
+ *                    2/3 mask (gfft_ps_dealias, gfft_ps_project_dealiased) removes them, and a field that has been through it
+ *                    has none.  One pass: ncomp complex loads, 3 ncomp stores and three cached wavenumber lookups per mode.
+ *                    d_out overlaps nothing.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, ncomp < 1,
+ *                    negative extents, precision; ncomp > 4 and n1, n2 > 2^30 are GFFT_ERR_UNSUPPORTED.  An empty block launches
+ *                    nothing.  Only enqueues and allocates nothing, so it can be captured.
+ *   gfft_ps_gradient_stats   statistics of a REAL tensor field d_A = [3][3][count], A[i][j] = d u_i / d x_j (components `count`
+ *                    scalars apart: the nine backward transforms of gfft_ps_gradient's output for a velocity), in ONE read, every
+ *                    value converted to double before any arithmetic.  Per point, with a_ij = A[i][j] and the association
+ *                    written out (the compiler may contract a product and the add that follows it into a fused multiply-add):
+ *                      div = (a00 + a11) + a22                       s01 = 0.5 (a01 + a10), s02 = 0.5 (a02 + a20), s12 = 0.5 (a12 + a21)
+ *                      w0 = a21 - a12, w1 = a02 - a20, w2 = a10 - a01                      (the vorticity)
+ *                      d2 = (a00 a00 + a11 a11) + a22 a22            p01 = s01 s01, p02 = s02 s02, p12 = s12 s12
+ *                      ss = d2 + 2 ((p01 + p02) + p12)                                     S_ij S_ij, S = (A + A^T) / 2
+ *                      ww = (w0 w0 + w1 w1) + w2 w2
+ *                      Q  = 0.5 (div div - (d2 + 2 ((a01 a10 + a02 a20) + a12 a21)))       ((tr A)^2 - tr(A^2)) / 2
+ *                      R  = -((a00 (a11 a22 - a12 a21) - a01 (a10 a22 - a12 a20)) + a02 (a10 a21 - a11 a20))      -det A
+ *                      d3 = (a00 (a00 a00) + a11 (a11 a11)) + a22 (a22 a22)
+ *                      sss = (d3 + 3 ((a00 (p01 + p02) + a11 (p01 + p12)) + a22 (p02 + p12))) + 6 ((s01 s02) s12)      S_ij S_jk S_ki
+ *                      wsw = ((a00 (w0 w0) + a11 (w1 w1)) + a22 (w2 w2)) + 2 ((s01 (w0 w1) + s02 (w0 w2)) + s12 (w1 w2))      w_i S_ij w_j
+ *                    Q and R are the general invariants: no trace-free assumption is made.  d_out = double[GFFT_PS_GRAD_NVAL] on
+ *                    the device, OVERWRITTEN:
+ *                      [0] max ss       [1] max ww        [2] max |div|    [3] sum div div   [4] sum ss
+ *                      [5] sum ww       [6] sum ss ss     [7] sum ww ww    [8] sum ss ww     [9] sum Q
+ *                      [10] sum R       [11] sum Q Q      [12] sum R R     [13] sum sss      [14] sum wsw
+ *                      [15] sum d2                        sum_i A_ii^2     (longitudinal derivatives)
+ *                      [16] sum d3                        sum_i A_ii^3
+ *                      [17] sum ((a00 a00)(a00 a00) + (a11 a11)(a11 a11)) + (a22 a22)(a22 a22)                    sum_i A_ii^4
+ *                      [18] sum ((a01 a01 + a10 a10) + (a02 a02 + a20 a20)) + (a12 a12 + a21 a21)                 sum_{i != j} A_ij^2
+ *                      [19] the same with every a a replaced by (a a)(a a)                                        sum_{i != j} A_ij^4
+ *                    For a solenoidal, alias-free periodic field (Betchov): [4] = [5] / 2, [9] = [10] = 0, [14] = -4/3 [13], and
+ *                    pointwise R = -(sss / 3 + wsw / 4) -- how far a run is from these tells whether it is resolved.
+ *                    NaN: the sums propagate it -- a NaN in one a_ij makes every sum that reads a_ij NaN ([15] ... [17] read the
+ *                    diagonal only, [18] and [19] the rest) --; the maxima follow fmax and skip a point whose value is NaN.
+ *                    Launch geometry, summation order, scratch and repeatability are those of gfft_ps_stats: a lane loads 16
+ *                    bytes per component where they divide `count` and d_A is 16-byte aligned, one element otherwise; the result
+ *                    repeats BIT FOR BIT from one call to the next for the same array, count and alignment; no floating-point
+ *                    atomics; the partial results of the workgroups go through the stream's scratch (no more of it than
+ *                    gfft_ps_stats asks for; allocated by the first call: run it once before capturing it).  An empty block
+ *                    (count = 0) writes zeros.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, count < 0,
+ *                    precision.  Only enqueues. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
+enum { GFFT_PS_GRAD_NVAL = 20 };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
                  int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
 int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream);
@@ -481,6 +529,13 @@ int gfft_ps_rk_stage_if(void *d_u, const void *d_u0, void *d_u1, const void *d_d
                         const double *nu /* host, ncomp */, const void *d_k0, const void *d_k1, const void *d_k2,
                         int64_t n0, int64_t n1, int64_t n2, double cb, double ca, int q0, int qd, int q1, int qa,
                         double h, const double *d_dt /* NULL: use h */, int precision, void *stream);
+int gfft_ps_gradient(const void *d_f_hat /* [ncomp][n0][n1][n2] complex */,
+                     void *d_out /* [ncomp][3][n0][n1][n2] complex */, int ncomp,
+                     const void *d_k0, const void *d_k1, const void *d_k2,
+                     int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
+int gfft_ps_gradient_stats(const void *d_A /* [3][3][count] real, A[i][j] = d u_i / d x_j */,
+                           int64_t count, double *d_out /* [GFFT_PS_GRAD_NVAL], overwritten */,
+                           int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

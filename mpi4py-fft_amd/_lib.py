@@ -17,6 +17,10 @@ LIBPATH = os.path.join(_HERE, 'libgfft.so')
 C2C_FORWARD, C2C_BACKWARD, R2C, C2R = -1, 1, -2, 2
 PS_DOT, PS_HELICITY = 0, 1              # op of gfft_ps_cospectrum
 PS_STATS_HEAD, PS_STATS_PER_COMP = 2, 6 # layout of gfft_ps_stats' output: double[HEAD + PER_COMP * ncomp]
+PS_GRAD_NVAL = 20                       # gfft_ps_gradient_stats' output: double[PS_GRAD_NVAL], indexed by the names below
+(GS_MAX_SS, GS_MAX_WW, GS_MAX_DIV, GS_DIV2, GS_SS, GS_WW, GS_SS2, GS_WW2, GS_SSWW, GS_Q, GS_R, GS_Q2, GS_R2, GS_SSS, GS_WSW,
+ GS_LONG2, GS_LONG3, GS_LONG4, GS_TRANS2, GS_TRANS4) = range(PS_GRAD_NVAL)
+PS_GRAD_NMAX = 3                        # entries 0 ... 2 are maxima, the rest sums
 
 _lib = None
 
@@ -94,6 +98,8 @@ def _declare(lib):
                                          vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_double, c.c_int, vp]),
         'gfft_ps_rk_stage_if': (c.c_int, [vp, vp, vp, vp, c.c_int, c.POINTER(c.c_double), vp, vp, vp, c.c_int64, c.c_int64, c.c_int64,
                                           c.c_double, c.c_double, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
+        'gfft_ps_gradient': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_int, vp]),
+        'gfft_ps_gradient_stats': (c.c_int, [vp, c.c_int64, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -537,6 +543,21 @@ class HipEngine:
                                         tu1.data_ptr(), tdu.data_ptr(), int(ncomp), v, k[0].data_ptr(), k[1].data_ptr(),
                                         k[2].data_ptr(), shape[0], shape[1], shape[2], float(cb), float(ca), q0, qd, q1, qa,
                                         float(h), None if tdt is None else tdt.data_ptr(), precision, current_stream()))
+
+    def ps_gradient(self, tf, tout, ncomp, k, shape, precision):
+        """gfft_ps_gradient: tout[c][j] = i k[j] tf[c] on complex tf = [ncomp] + shape, tout = [ncomp][3] + shape; tout overlaps
+        nothing."""
+        self.require_device(tf)
+        self.require_device(tout)
+        check(lib().gfft_ps_gradient(tf.data_ptr(), tout.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                     shape[0], shape[1], shape[2], precision, current_stream()))
+
+    def ps_gradient_stats(self, ta, count, tout, precision):
+        """gfft_ps_gradient_stats: ta = real [3][3][count], ta[i][j] = d u_i / d x_j; tout = double[PS_GRAD_NVAL] on the device,
+        overwritten."""
+        self.require_device(ta)
+        self.require_device(tout)
+        check(lib().gfft_ps_gradient_stats(ta.data_ptr(), int(count), tout.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

@@ -7,7 +7,8 @@
 //     scalars the flux u theta and the right-hand side -i K . (u theta)^ - kappa |K|^2 theta^ - G . u^.  HBM-bound elementwise work: 16 bytes per lane, grid-stride, wavenumbers from three per-axis vectors instead
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
-//     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity) and physical-space statistics (ps_stats_kernel).
+//     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity), physical-space statistics (ps_stats_kernel) and the
+//     statistics of the velocity-gradient tensor (ps_gradient_stats_kernel, behind the pointwise ps_gradient_kernel: i K_j f_hat).
 #include "../../include/gfft.h"
 #include "gfft_internal.h"
 
@@ -589,6 +590,8 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 //   NS = 1: 36 / 26 plain, 48 / 38 with the gradient, 48 / 34 masked, 60 / 46 with both;   NS = 2: 56 / 40, 66 / 56 (7 waves in
 //   fp64), 52 / 50, 64 / 56;   NS = 3 and 4 (the scalars in turn): 40 / 26, 52 / 34, 46 / 36, 60 / 42.
 // ps_rk_if_kernel<double / float, UNIFORM> 72 / 44 (7 and 8 waves per SIMD), <double / float, per component> 60 / 30 (8 waves).
+// ps_gradient_kernel<double, NC = 1 ... 4> 40, 50, 66, 64 (7 waves per SIMD at NC = 3, else 8) and <float, NC> 28, 40, 48, 54;
+// ps_gradient_stats_kernel<double, 2> 112 and <float, 4> 128 (4 waves per SIMD), <double, 1> 90, <float, 1> 90 (5 waves); gs_reduce_kernel 11.
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -669,10 +672,11 @@ ps_stats_kernel(const real *__restrict__ u, int64_t count, int64_t chunk, st_sca
 
 // out[i] = the nwg workgroup values of slot i combined in the fixed order above; workgroup i of the launch owns value i
 // (nwg == 0, an empty block: the identities 0, -inf, +inf, 0).  At most 8 dependent loads per lane, not 2048.
-__global__ void __launch_bounds__(PS_THREADS)
-st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+// (KIND: the kind map of the caller's values -- st_kind here, gs_kind for the gradient statistics)
+template <int (*KIND)(int)>
+__device__ __forceinline__ void st_reduce_value(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
   __shared__ double part[PS_THREADS / 64];
-  const int i = blockIdx.x, kind = st_kind(i);
+  const int i = blockIdx.x, kind = KIND(i);
   double r = st_identity(kind);
   for (int w = threadIdx.x; w < nwg; w += PS_THREADS) r = st_combine(kind, r, slabs[(int64_t)i * SP_MAX_WG + w]);
   r = st_wave(kind, r);
@@ -683,6 +687,11 @@ st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__
     for (int w = 1; w < PS_THREADS / 64; ++w) r = st_combine(kind, r, part[w]);
     out[i] = r;
   }
+}
+
+__global__ void __launch_bounds__(PS_THREADS)
+st_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+  st_reduce_value<st_kind>(slabs, nwg, out);
 }
 
 // ---- passive scalars: d theta / dt + div(u theta) = kappa lap theta - G . u, NS <= SC_MAX scalars per launch --------------
@@ -779,6 +788,165 @@ ps_scalar_rhs_kernel(cx<real> *__restrict__ d, const cx<real> *__restrict__ flux
       d[e + s * count] = r;
     }
   }
+}
+
+// ---- the velocity-gradient tensor: A_ij = d u_i / d x_j in spectral space, and one read of it in physical space --------------
+// out[c][j][e] = i k_j f[c][e] = {-(k_j f.y), k_j f.x}: one multiply per part, so the correctly rounded product, the sign of
+// a zero included.  f = [NC][count] modes, out = [NC][3][count]; NC loads and 3 NC stores per mode and the three cached
+// wavenumber lookups of ps_curl_kernel, a lane's mode its flat index, grid-stride; out overlaps nothing.  K is applied as given (the
+// convention of ps_curl_kernel): nothing special happens in a Nyquist column, which the 2/3 mask removes.  NC is a template
+// parameter as NS is of ps_scalar_flux_kernel; all NC <= 4 loads of a mode are in flight together.  (Registers: in the list above ps_stats_kernel.)
+// A single field (NC = 1) takes TWO modes per lane and step, a grid stride apart, both loads in flight before the first
+// store: with one 16-byte load per lane the fp64 form was bound by latency, not bytes -- 3.49 TB/s = 0.62 of the copy, two
+// tenths below its yardstick, its median a quarter above its minimum --; with two it runs level with it (below).
+// Measured on one MI355X (tools/gradient_probe.py, 256^3, HIP events after a warm-up, minimum of 15 rounds), achieved bytes per
+// second against gfft_probe_copy in the same run (6.04 TB/s), fp64 / fp32:
+//   ps_gradient_kernel, one field      4.89 / 4.94 TB/s = 0.81 / 0.82 of the copy
+//   ps_gradient_kernel, three fields   4.91 / 5.25 TB/s = 0.81 / 0.87                (ps_scalar_flux_kernel, three scalars, same run: 0.80 / 0.86)
+//   ps_gradient_stats_kernel + reduce  4.18 / 3.70 TB/s = 0.69 / 0.61                (ps_stats_kernel, three components, same run: 0.61 / 0.54)
+// 0.33 ms against 0.48 ms for the nine torch products of a velocity, 0.29 ms against 124 ms for the 20 numbers as torch expressions.
+template <typename real, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_gradient_kernel(const cx<real> *__restrict__ f, cx<real> *__restrict__ out, const real *__restrict__ k0,
+                   const real *__restrict__ k1, const real *__restrict__ k2, int64_t n1, int64_t n2, int64_t count) {
+  constexpr int U = NC == 1 ? 2 : 1;          // modes per lane and step: a single field has two loads in flight, not one
+  const int64_t stride = (int64_t)gridDim.x * PS_THREADS;
+  for (int64_t e0 = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; e0 < count; e0 += U * stride) {
+    real kx[U], ky[U], kz[U];
+    cx<real> v[U][NC];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e = e0 + u * stride;
+      if (e < count) {
+        const int64_t row = e / n2;
+        kz[u] = k2[e - row * n2];
+        const int64_t i0 = row / n1;
+        ky[u] = k1[row - i0 * n1];
+        kx[u] = k0[i0];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) v[u][c] = f[e + c * count];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t e = e0 + u * stride;
+      if (e < count) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          cx<real> *__restrict__ o = out + e + 3 * c * count;
+          o[0] = {-(kx[u] * v[u][c].y), kx[u] * v[u][c].x};
+          o[count] = {-(ky[u] * v[u][c].y), ky[u] * v[u][c].x};
+          o[2 * count] = {-(kz[u] * v[u][c].y), kz[u] * v[u][c].x};
+        }
+      }
+    }
+  }
+}
+
+// A = [3][3][count] reals, a_ij = A[3 i + j] converted to double before any arithmetic.  The GS_NVAL = 20 values, their
+// expressions and associations: include/gfft.h (gfft_ps_gradient_stats).  Geometry, summation order (steps 1 - 4), NaN
+// behaviour and scratch are those of ps_stats_kernel: 16 bytes per lane and component (V = 2 in fp64, 4 in fp32; V = 1 where
+// count % V != 0 or the base is not 16-byte aligned), the nine loads of a step in flight together, the V points of a load
+// processed in turn; slot [value][workgroup] of the slabs, then gs_reduce_kernel.  Values 0 - 2 are maxima of non-negative
+// numbers with the identity 0 (ST_MAX0), the rest sums: an empty block gives zeros.
+// Cost per point beside its 72 bytes (36 in fp32): nine conversions and about 110 fp64 operations -- ten times what
+// ps_stats_kernel does per value, 1.5 (fp64) and 3 (fp32) operations per byte of HBM traffic.  Measured (above
+// ps_gradient_kernel): it runs at the rate of ps_stats_kernel all the same, the arithmetic hidden behind the loads.
+// Registers (in the list above ps_stats_kernel): 20 accumulators (40 VGPRs) and 9 V loaded values (36) leave room for one
+// point's temporaries only if the V points are taken IN TURN.  Left to itself the scheduler interleaves them -- 166 VGPRs in
+// fp64 and 256 in fp32, 3 and 2 waves per SIMD --, so a scheduling barrier closes every point, and an empty asm on each loaded
+// value keeps the conversions of the later points from being hoisted over it: 112 and 128 VGPRs, 4 waves per SIMD.
+constexpr int GS_NVAL = GFFT_PS_GRAD_NVAL, GS_NMAX = 3;
+static_assert(GS_NVAL <= ST_HEAD + ST_PER_COMP * ST_MAX_COMP, "the slabs fit the scratch that gfft_ps_stats asks for");
+
+__host__ __device__ constexpr int gs_kind(int i) { return i < GS_NMAX ? ST_MAX0 : ST_SUM; }
+
+// one point: a[3 i + j] = A_ij
+__device__ __forceinline__ void gs_point(double (&val)[GS_NVAL], const double (&a)[9]) {
+  const double a00 = a[0], a01 = a[1], a02 = a[2], a10 = a[3], a11 = a[4], a12 = a[5], a20 = a[6], a21 = a[7], a22 = a[8];
+  const double div = (a00 + a11) + a22;
+  const double s01 = 0.5 * (a01 + a10), s02 = 0.5 * (a02 + a20), s12 = 0.5 * (a12 + a21);
+  const double w0 = a21 - a12, w1 = a02 - a20, w2 = a10 - a01;
+  const double q00 = a00 * a00, q11 = a11 * a11, q22 = a22 * a22;
+  const double d2 = (q00 + q11) + q22;
+  const double p01 = s01 * s01, p02 = s02 * s02, p12 = s12 * s12;
+  const double ss = d2 + 2.0 * ((p01 + p02) + p12);
+  const double ww = (w0 * w0 + w1 * w1) + w2 * w2;
+  const double Q = 0.5 * (div * div - (d2 + 2.0 * ((a01 * a10 + a02 * a20) + a12 * a21)));
+  const double R = -((a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20)) + a02 * (a10 * a21 - a11 * a20));
+  const double d3 = (a00 * q00 + a11 * q11) + a22 * q22;
+  const double sss = (d3 + 3.0 * ((a00 * (p01 + p02) + a11 * (p01 + p12)) + a22 * (p02 + p12))) + 6.0 * ((s01 * s02) * s12);
+  const double wsw = ((a00 * (w0 * w0) + a11 * (w1 * w1)) + a22 * (w2 * w2)) +
+                     2.0 * ((s01 * (w0 * w1) + s02 * (w0 * w2)) + s12 * (w1 * w2));
+  const double o01 = a01 * a01, o10 = a10 * a10, o02 = a02 * a02, o20 = a20 * a20, o12 = a12 * a12, o21 = a21 * a21;
+  val[0] = fmax(val[0], ss);
+  val[1] = fmax(val[1], ww);
+  val[2] = fmax(val[2], fabs(div));
+  val[3] += div * div;
+  val[4] += ss;
+  val[5] += ww;
+  val[6] += ss * ss;
+  val[7] += ww * ww;
+  val[8] += ss * ww;
+  val[9] += Q;
+  val[10] += R;
+  val[11] += Q * Q;
+  val[12] += R * R;
+  val[13] += sss;
+  val[14] += wsw;
+  val[15] += d2;
+  val[16] += d3;
+  val[17] += (q00 * q00 + q11 * q11) + q22 * q22;
+  val[18] += ((o01 + o10) + (o02 + o20)) + (o12 + o21);
+  val[19] += ((o01 * o01 + o10 * o10) + (o02 * o02 + o20 * o20)) + (o12 * o12 + o21 * o21);
+}
+
+template <typename real, int V>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_gradient_stats_kernel(const real *__restrict__ A, int64_t count, int64_t chunk, double *__restrict__ slabs) {
+  __shared__ double gs_part[PS_THREADS / 64][GS_NVAL];
+  double val[GS_NVAL];
+#pragma unroll
+  for (int i = 0; i < GS_NVAL; ++i) val[i] = st_identity(gs_kind(i));
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (count and chunk are multiples of V: a lane has all V points of a load or none)
+  for (int64_t e0 = begin + (int64_t)threadIdx.x * V; e0 < end; e0 += PS_THREADS * V) {
+    st_load<real, V> v[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) v[c] = *reinterpret_cast<const st_load<real, V> *>(A + c * count + e0);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      double a[9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) {
+        real x = v[c].m[j];
+        asm volatile("" : "+v"(x));                                    // (keeps the conversions of a later point behind the barrier)
+        a[c] = x;                                                      // converted before any arithmetic
+      }
+      gs_point(val, a);
+      __builtin_amdgcn_sched_barrier(0);                               // one point after the other: see above
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < GS_NVAL; ++i) {
+    const double w = st_wave(gs_kind(i), val[i]);
+    if ((threadIdx.x & 63) == 0) gs_part[threadIdx.x >> 6][i] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < GS_NVAL) {
+    const int i = threadIdx.x, kind = gs_kind(i);
+    double r = gs_part[0][i];
+    for (int w = 1; w < PS_THREADS / 64; ++w) r = st_combine(kind, r, gs_part[w][i]);
+    slabs[(int64_t)i * SP_MAX_WG + blockIdx.x] = r;
+  }
+}
+
+// st_reduce_kernel's step 4 with the kind map of the gradient statistics: workgroup i owns value i; nwg == 0, an empty block:
+// the identities, all 0
+__global__ void __launch_bounds__(PS_THREADS)
+gs_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+  st_reduce_value<gs_kind>(slabs, nwg, out);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
@@ -1010,6 +1178,35 @@ hipError_t launch_ps_scalar_rhs(void *d, const void *flux, const void *theta, co
       return mean_gradient ? go(sc_rhs_kernel<real, true, ps_keep_mask>(ns), keep) : go(sc_rhs_kernel<real, false, ps_keep_mask>(ns), keep);
     return mean_gradient ? go(sc_rhs_kernel<real, true, ps_keep_all>(ns), ps_keep_all()) : go(sc_rhs_kernel<real, false, ps_keep_all>(ns), ps_keep_all());
   });
+}
+
+template <typename real>
+auto gr_kernel(int nc) {
+  return nc == 1 ? ps_gradient_kernel<real, 1> : nc == 2 ? ps_gradient_kernel<real, 2>
+       : nc == 3 ? ps_gradient_kernel<real, 3> : ps_gradient_kernel<real, 4>;
+}
+
+// 1 <= ncomp <= GR_MAX_COMP
+constexpr int GR_MAX_COMP = 4;
+hipError_t launch_ps_gradient(const void *f, void *out, int ncomp, const void *k0, const void *k1, const void *k2, int64_t n0,
+                              int64_t n1, int64_t n2, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  const int64_t lanes = ncomp == 1 ? (count + 1) / 2 : count;          // a single field: two modes per lane and step
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(gr_kernel<decltype(r)>(ncomp), lanes, s, f, out, k0, k1, k2, n1, n2, count); });
+}
+
+// the geometry of launch_ps_stats over the one base A; `slabs` = ST_SCRATCH_BYTES of stream-ordered scratch
+hipError_t launch_ps_gradient_stats(const void *A, int64_t count, double *out, double *slabs, int precision, hipStream_t s) {
+  const sp_geom g = sp_geometry(count, 16 / precision, (uintptr_t)A % 16 == 0);
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    return ps_launch(g.V == W ? ps_gradient_stats_kernel<real, W> : ps_gradient_stats_kernel<real, 1>, g.nwg, 0, s, A, count,
+                     g.chunk, slabs);
+  });
+  if (e != hipSuccess) return e;
+  return ps_launch(gs_reduce_kernel, GS_NVAL, 0, s, slabs, g.nwg, out);
 }
 
 // gfft_ps_spectrum and gfft_ps_cospectrum behind their own argument checks (`bad`); fn names the caller in the messages.
@@ -1252,6 +1449,35 @@ int gfft_ps_scalar_rhs(void *d_dtheta_hat, const void *d_flux_hat, const void *d
   const bool masked = d_m0 || d_m1 || d_m2 || kcut < (double)INFINITY;
   HIP_TRY(launch_ps_scalar_rhs(d_dtheta_hat, d_flux_hat, d_theta_hat, d_u_hat, nscalar, coef, grad != nullptr, d_k0, d_k1, d_k2,
                                n0, n1, n2, masked, ps_keep_mask{d_m0, d_m1, d_m2, kcut * kcut}, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_gradient(const void *d_f_hat, void *d_out, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2,
+                     int64_t n0, int64_t n1, int64_t n2, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_f_hat || !d_out || !d_k0 || !d_k1 || !d_k2 || ncomp < 1 || n0 < 0 || n1 < 0 || n2 < 0 ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_gradient: bad argument");
+  static_assert(GR_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > GR_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_gradient: more than 4 components");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_gradient: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_gradient(d_f_hat, d_out, ncomp, d_k0, d_k1, d_k2, n0, n1, n2, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_gradient_stats(const void *d_A, int64_t count, double *d_out, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_A || !d_out || count < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_gradient_stats: bad argument");
+  int rc = check_device();
+  if (rc) return rc;
+  // the slabs of gfft_ps_stats, and no more of the stream's scratch than it asks for: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, ST_SCRATCH_BYTES, &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_gradient_stats(d_A, count, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -69,6 +69,20 @@ the nonlinear term sees RK4:
                                 of u_hat, the right-hand sides come from `project(..., nu=0)` / `scalar_rhs(..., kappa=0)`, the
                                 last row goes with u=None, and u1 ends as the new u_hat
 
+and the small scales in physical space, where a DNS is validated -- everything that is a function of the velocity-gradient
+tensor A_ij = d u_i / d x_j: the spectral gradient in one pass, nine backward transforms, and ONE read of A that reduces it:
+
+    gradient(f_hat, out)        out[c][j] = 1j * K[j] * f_hat[c] for m <= 4 fields at once ([3][3] + spectral shape for a velocity,
+                                [3] + spectral shape for a scalar): m loads and 3 m stores per mode.  K is applied as given, as
+                                in `curl`: the derivative of a Nyquist column is not real, and the 2/3 mask removes those columns
+    gradient_stats(A)           20 numbers from one read of the real [3][3] + physical shape tensor, bit for bit repeatable: the
+                                maxima of S_ij S_ij, |w|^2 and |div u| and the sums of div^2, S_ij S_ij, |w|^2, their squares and
+                                product, the invariants Q and R and their squares, S_ij S_jk S_ki, w_i S_ij w_j and the second
+                                to fourth powers of the longitudinal and transverse derivatives (`_lib.GS_*` name the entries)
+    gradient_moments(gs, npoints, nu)   turns them into dissipation, enstrophy, <Q>, <R>, derivative skewness and flatness,
+                                the intermittency of dissipation and enstrophy, and the Betchov ratio <w S w> / (-4/3 <S S S>),
+                                which is 1 for a solenoidal field that is resolved and alias-free
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -159,6 +173,64 @@ class SpectralOps:
         self._same_precision(_prec(u_hat))
         _lib.engine().ps_curl(_t(u_hat), _t(out), self.K, self.shape, _prec(u_hat))
         return out
+
+    def gradient(self, f_hat, out):
+        """out[c][j] = 1j * K[j] * f_hat[c]: the spectral gradient of m <= 4 fields in one pass.  f_hat is [m] + spectral shape
+        and out [m][3] + spectral shape (for m = 3 the layout of newDistArray(fft, rank=2): out[i][j] transforms back to
+        A_ij = d u_i / d x_j), or, a scalar field, the spectral shape and [3] + spectral shape; contiguous, complex, of the
+        transform's precision, out overlapping nothing.  Each part of each value is one multiply: the correctly rounded
+        product, bit for bit.  K is applied as given (the convention of `curl`): a Nyquist column is not treated specially;
+        the 2/3 mask removes it.  Returns out.  Nothing synchronises or allocates."""
+        t, ncomp, precision = self._field(f_hat)
+        assert ncomp <= 4, 'at most 4 components per call'
+        to = _t(out)
+        assert tuple(to.shape) == tuple(t.shape[:-3]) + (3,) + self.shape, (tuple(to.shape), tuple(t.shape))
+        assert to.is_contiguous(), 'out is not contiguous'
+        to, no, po = self._field(to.view((3 * ncomp,) + self.shape))
+        assert (no, po) == (3 * ncomp, precision), 'out and f_hat differ in precision'
+        _lib.engine().ps_gradient(t, to, ncomp, self.K, self.shape, precision)
+        return out
+
+    def gradient_stats(self, A, out=None, reduce=True):
+        """Statistics of the velocity-gradient tensor in one read: float64 [20], indexed by `_lib.GS_*`,
+            [0] max S_ij S_ij   [1] max |w|^2   [2] max |div u|          (S = (A + A^T) / 2, w = curl u, div u = tr A)
+            [3] sum div^2   [4] sum S_ij S_ij   [5] sum |w|^2   [6] sum (S_ij S_ij)^2   [7] sum |w|^4   [8] sum S_ij S_ij |w|^2
+            [9] sum Q   [10] sum R   [11] sum Q^2   [12] sum R^2         (Q = ((tr A)^2 - tr A^2) / 2, R = -det A)
+            [13] sum S_ij S_jk S_ki   [14] sum w_i S_ij w_j
+            [15 ... 17] sum_i A_ii^2, A_ii^3, A_ii^4   [18], [19] sum_{i != j} A_ij^2, A_ij^4
+        (`gradient_moments` reads them; include/gfft.h has the exact expressions).  A is a contiguous real tensor or DistArray
+        of shape [3][3] + fft.shape(False) in the transform's precision, A[i][j] = d u_i / d x_j: the nine backward transforms
+        of `gradient(u_hat, .)`.  Every value is converted to double first.  A NaN in A[i][j] makes every sum that reads it NaN;
+        the maxima follow fmax and skip it.
+
+        `reduce` and `out` as in `stats`: reduce=True combines over the ranks of the grid on the host (entries 0 - 2 with
+        np.maximum, the rest added in rank order, one grid axis after the other, so every rank holds identical bits), which
+        synchronises; reduce=False only enqueues and returns the device tensor (`out`, a contiguous double tensor of 20
+        entries, or a new one), so it can be captured after one call outside the capture.  The result repeats bit for bit from
+        one call to the next."""
+        t = _t(A)
+        assert tuple(t.shape) == (3, 3) + self.pshape, (tuple(t.shape), self.pshape)
+        assert t.is_contiguous() and t.dtype in (torch.float32, torch.float64), 'gradient_stats needs a contiguous real tensor'
+        precision = 8 if t.dtype == torch.float64 else 4
+        self._same_precision(precision)
+        if out is None:
+            out = torch.empty(_lib.PS_GRAD_NVAL, dtype=torch.float64, device=t.device)
+        assert tuple(out.shape) == (_lib.PS_GRAD_NVAL,) and out.dtype == torch.float64 and out.is_contiguous()
+        count = int(np.prod(self.pshape, dtype=np.int64))
+        _lib.engine().ps_gradient_stats(t, count, out, precision)
+        return self._reduce_gradient_stats(out) if reduce else out
+
+    def _reduce_gradient_stats(self, out):
+        """`_reduce_stats` for the layout of gradient_stats: maxima first, then sums"""
+        vals = out.cpu().numpy()                       # (waits for the kernels)
+        _lib.check_async()
+        is_max = np.arange(len(vals)) < _lib.PS_GRAD_NMAX
+        for c in self.comms:                           # one grid axis after the other: the same order on every rank
+            parts = c.allgather_obj(vals)
+            vals = parts[0].copy()
+            for p in parts[1:]:
+                vals = np.where(is_max, np.maximum(vals, p), vals + p)
+        return vals
 
     def dealias_mask(self, rule='2/3', kcut=None):
         """The kept set of `project(..., dealias=)` and `dealias` as a `DealiasMask` (m0, m1, m2, kcut): a mode is kept iff
@@ -582,6 +654,37 @@ def moments(stats, npoints):
     c4 = m4 - 4 * m1 * m3 + 6 * m1 * m1 * m2 - 3 * m1 ** 4
     with np.errstate(divide='ignore', invalid='ignore'):
         return np.stack([m1, var, c3 / var ** 1.5, c4 / (var * var)], axis=1)
+
+
+GradientMoments = collections.namedtuple('GradientMoments', 'strain enstrophy Q R dissipation skewness flatness transverse_flatness '
+                                         'dissipation_flatness enstrophy_flatness strain_enstrophy_correlation betchov div_rms')
+GradientMoments.__doc__ = """What `gradient_moments` returns: strain = <S_ij S_ij>, enstrophy = <|w|^2> / 2, Q = <Q>, R = <R>,
+dissipation = 2 nu <S_ij S_ij> (None without nu), skewness and flatness of the longitudinal derivatives d u_i / d x_i (averaged
+over i), transverse_flatness of d u_i / d x_j, i != j, dissipation_flatness = <(S_ij S_ij)^2> / <S_ij S_ij>^2, enstrophy_flatness =
+<|w|^4> / <|w|^2>^2, strain_enstrophy_correlation = <S_ij S_ij |w|^2> / (<S_ij S_ij> <|w|^2>), betchov = <w_i S_ij w_j> / (-4/3
+<S_ij S_jk S_ki>) and div_rms = sqrt(<(div u)^2>)."""
+
+
+def gradient_moments(gs, npoints, nu=None):
+    """The small-scale statistics from `SpectralOps.gradient_stats` (rank-reduced) and the GLOBAL number of points, as a
+    `GradientMoments`.  With S_n = gs[n] and n = npoints: skewness = (S16 / 3n) / (S15 / 3n)^(3/2), flatness = (S17 / 3n) /
+    (S15 / 3n)^2 (3 for a Gaussian, 3/2 for a sine; the skewness of a turbulent field is about -0.5), transverse_flatness =
+    (S19 / 6n) / (S18 / 6n)^2.  For a solenoidal, resolved, alias-free periodic field strain = enstrophy, Q = R = 0 and
+    betchov = 1.  A ratio whose denominator vanishes is nan or inf, as in `moments`.  Host numpy."""
+    s = np.asarray(gs, dtype=np.float64)
+    assert s.shape == (_lib.PS_GRAD_NVAL,), s.shape
+    n = float(npoints)
+    ss, ww = s[_lib.GS_SS] / n, s[_lib.GS_WW] / n
+    l2, l3, l4 = (s[i] / (3 * n) for i in (_lib.GS_LONG2, _lib.GS_LONG3, _lib.GS_LONG4))
+    t2, t4 = s[_lib.GS_TRANS2] / (6 * n), s[_lib.GS_TRANS4] / (6 * n)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return GradientMoments(
+            strain=float(ss), enstrophy=float(ww / 2), Q=float(s[_lib.GS_Q] / n), R=float(s[_lib.GS_R] / n),
+            dissipation=None if nu is None else float(2 * nu * ss),
+            skewness=float(l3 / l2 ** 1.5), flatness=float(l4 / (l2 * l2)), transverse_flatness=float(t4 / (t2 * t2)),
+            dissipation_flatness=float((s[_lib.GS_SS2] / n) / (ss * ss)), enstrophy_flatness=float((s[_lib.GS_WW2] / n) / (ww * ww)),
+            strain_enstrophy_correlation=float((s[_lib.GS_SSWW] / n) / (ss * ww)),
+            betchov=float(np.float64(s[_lib.GS_WSW]) / (-4.0 / 3.0 * s[_lib.GS_SSS])), div_rms=float(np.sqrt(s[_lib.GS_DIV2] / n)))
 
 
 def flux(T):
