@@ -83,7 +83,9 @@ int gfft_device_name(int device, char *buf, size_t len);
  * launch before the launch voids itself, gfft_async_error below; default 2000); GFFT_FUSE2_DEBUG=1 prints a fused
  * launch's counters.  ("debug_tw_index" / "debug_tw_exp": TEST HOOK -- twiddle tables uploaded while debug_tw_exp > 0
  * carry one entry off by 10^-debug_tw_exp: what the rounding-level guards of tests/ must catch; "debug_tw_len" != 0 confines
- * it to tables of exactly that length -- a packed-real plan's Hermitian table rtw(n) and not its tw(n / 2).) */
+ * it to tables of exactly that length -- a packed-real plan's Hermitian table rtw(n) and not its tw(n / 2).
+ * "debug_r2r_index" / "debug_r2r_exp" / "debug_r2r_post": the same TEST HOOK for the pre (0) / post (1) tables of the
+ * real-to-real kinds.) */
 int gfft_set_option(const char *key, int value);
 
 /* ---- serial multi-axis transform plan ------------------------------------------------

@@ -92,6 +92,11 @@ struct Options {
   // before / after are untouched.  What the rounding-level guards of the test suite must catch; never set by the product.
   // debug_tw_len != 0: only the table of exactly that length (a packed-real plan's rtw(n), say, and not its tw(n/2)).
   int debug_tw_index = 1, debug_tw_exp = 0, debug_tw_len = 0;
+  // TEST HOOK (tests/test_gpu_r2r_guard.py): the same for the pre / post tables of the real-to-real kinds (get_r2r_tables) --
+  // tables uploaded while debug_r2r_exp > 0 carry ONE wrong entry: the real part of entry debug_r2r_index (mod n) of `pre`
+  // (debug_r2r_post = 0) or `post` (1) is off by 10^-debug_r2r_exp -- under their own cache key, so that plans made
+  // before / after are untouched.  What the rounding-level guards of the test suite must catch; never set by the product.
+  int debug_r2r_index = 1, debug_r2r_exp = 0, debug_r2r_post = 0;
   Options() {
     if (const char *s = getenv("GFFT_GRID_CAP")) grid_cap = atoi(s);
     if (const char *s = getenv("GFFT_VARIANT_ROWS")) variant_rows = atoi(s);
@@ -1053,7 +1058,7 @@ int plan_embedded(gfft_plan_s *pl, const Line &L, bool bluestein) {
 // whatever plan_line picks for N, so every length works; the cost is that of a length-N complex
 // transform per n real samples -- these kinds are a convenience of the API, not its hot path.
 struct R2RTables { void *pre, *post; };
-std::map<std::tuple<int, int64_t, int>, R2RTables> g_r2r_cache;
+std::map<std::tuple<int, int64_t, int, int64_t>, R2RTables> g_r2r_cache;   // (kind, n, precision + device, test-hook signature)
 
 int64_t r2r_logical_n(int kind, int64_t n) {
   if (kind == GFFT_REDFT00) return 2 * (n - 1);
@@ -1063,7 +1068,10 @@ int64_t r2r_logical_n(int kind, int64_t n) {
 
 int get_r2r_tables(int kind, int64_t n, int prec, R2RTables *out) {
   std::lock_guard<std::mutex> lock(g_tw_mutex);
-  auto key = std::make_tuple(kind, n, dev_prec(prec));
+  const int e = opts().debug_r2r_exp;
+  const int64_t wrong = e > 0 ? ((int64_t)opts().debug_r2r_index % n + n) % n : -1;
+  const bool wrong_post = opts().debug_r2r_post != 0;
+  auto key = std::make_tuple(kind, n, dev_prec(prec), e > 0 ? ((wrong * 64 + (e & 63)) * 2 + (wrong_post ? 1 : 0)) + 1 : (int64_t)0);
   auto it = g_r2r_cache.find(key);
   if (it == g_r2r_cache.end()) {
     const long double PI = 3.14159265358979323846264338327950288L;
@@ -1089,6 +1097,7 @@ int get_r2r_tables(int kind, int64_t n, int prec, R2RTables *out) {
       }
       ar[j] = pr; ai[j] = pi_; br[j] = qr; bi[j] = qi;
     }
+    if (wrong >= 0) (wrong_post ? br : ar)[wrong] += (long double)std::pow(10.0, -e);   // (test hook, Options::debug_r2r_exp)
     auto upload = [&](const std::vector<long double> &xr, const std::vector<long double> &xi, void **dst) -> int {
       std::vector<unsigned char> h(xr.size() * 2 * prec);
       for (size_t j = 0; j < xr.size(); ++j) {
@@ -1945,6 +1954,9 @@ int gfft_set_option(const char *key, int value) {
   else if (!strcmp(key, "debug_tw_index")) opts().debug_tw_index = value;
   else if (!strcmp(key, "debug_tw_exp")) opts().debug_tw_exp = value;
   else if (!strcmp(key, "debug_tw_len")) opts().debug_tw_len = value;
+  else if (!strcmp(key, "debug_r2r_index")) opts().debug_r2r_index = value;
+  else if (!strcmp(key, "debug_r2r_exp")) opts().debug_r2r_exp = value;
+  else if (!strcmp(key, "debug_r2r_post")) opts().debug_r2r_post = value;
   else if (!strcmp(key, "xcd_swizzle")) opts().xcd_swizzle = value;
   else if (!strcmp(key, "tile_order")) opts().tile_order = value;
   else if (!strcmp(key, "fused3_min_mib")) opts().fused3_min_bytes = (int64_t)value << 20;

@@ -30,7 +30,10 @@ def rounding_tol(dt, nelem, factor=2.0):
     the worst case sits at 0.71 eps log2(nelem) -- 7-point lines --, the BASELINE sizes at 0.1 ... 0.4.  The contract tolerances
     (north_star: 1e-10 round trip / 2e-10 forward in fp64; 1e-4 / 2e-4 in fp32) are 10^3 ... 10^5 times looser: a kernel
     that lost three digits would pass them.  The reference's own serial tests ask for the same level
-    (/root/reference/tests/test_libfft.py:17, abstol f = 5e-5, d = 1e-14 on O(1) data)."""
+    (/root/reference/tests/test_libfft.py:17, abstol f = 5e-5, d = 1e-14 on O(1) data).
+    Three transform families are held to it, each with an impulse family of its own beside the random-data comparisons: complex
+    (`impulse_errors`), real r2c / c2r (`real_impulse_errors`) and real-to-real DCT / DST (`r2r_impulse_errors`; there `nelem`
+    counts the LOGICAL points N = 2 (n -+ 1) or 2 n of the complex transform a kind runs on, tests/test_gpu_r2r.py)."""
     return factor * EPS[dt] * max(1.0, float(np.log2(max(2.0, float(nelem)))))
 
 
@@ -371,6 +374,128 @@ def real_path(describe):
         return 'generic'
     assert 'kernel=regs-' in text, text
     return 'regs'
+
+
+# ---- the real-to-real family (DCT / DST I-IV): FFTW kind numbers, mpi4py_fft_amd.fftw.FFTW_REDFT00 ... FFTW_RODFT11 ----
+REDFT00, REDFT01, REDFT10, REDFT11, RODFT00, RODFT01, RODFT10, RODFT11 = 3, 4, 5, 6, 7, 8, 9, 10
+R2R_NAMES = {3: 'REDFT00', 4: 'REDFT01', 5: 'REDFT10', 6: 'REDFT11', 7: 'RODFT00', 8: 'RODFT01', 9: 'RODFT10', 10: 'RODFT11'}
+# logical lengths N by the path that runs them (plan.cpp plan_r2r_line): the MODE_R2R load / store adapters of the register
+# kernels (powers of two 64 ... 4096 -- the floor and the cap of pow2_r2r_supported --, 3^b 2^k, 5^c 2^k) and the embed /
+# extract fallback: below the floor, just past the cap, 5^4 2^3 above 4096, a 3 x 5 x 2^k length (those kernels have no
+# adapters), generic lengths with radix 7 and 11, and 2 x 521 through Bluestein
+R2R_LENGTHS = {'adapter': [64, 128, 512, 4096, 48, 768, 3456, 20, 500, 4000],
+               'fallback': [16, 32, 8192, 5000, 240, 14, 242],
+               'bluestein': [1042]}
+R2R_MAPPINGS = ('rows', 'cols', 'middle')
+
+
+def r2r_points(kind, N):
+    """Points n of a line of `kind` whose logical (complex) length is N: N = 2 (n - 1), 2 (n + 1) or 2 n."""
+    assert N % 2 == 0, N
+    return N // 2 + 1 if kind == REDFT00 else N // 2 - 1 if kind == RODFT00 else N // 2
+
+
+def r2r_positions(n):
+    """The impulse positions of `impulse_errors` with the duplicate 1 replaced by 0: both weight-1 edges of REDFT00 (0,
+    n - 1), REDFT01 (0) and RODFT01 (n - 1) are hit."""
+    return [int(j) % n for j in (1, 2, 3, 5, 7, n // 2 + 1, n - 1, n // 3 + 1, n // 4 + 1, 11 % n, n // 5 + 2, n // 7 + 3, 0, n - 2,
+                                 13 % n, n // 2 - 1)]
+
+
+def r2r_exact_impulse(kind, n, j):
+    """The unnormalised transform (FFTW's definition, scipy's norm=None) of the unit impulse at j of n points, k = 0 ... n - 1:
+    evaluated in np.longdouble with the integer product of the phase reduced modulo its period first, returned as float64.
+      REDFT00  c cos(pi j k / (n - 1)), c = 1 at j in {0, n - 1}, else 2       RODFT00  2 sin(pi (j + 1)(k + 1) / (n + 1))
+      REDFT10  2 cos(pi (2j + 1) k / (2n))                                     RODFT10  2 sin(pi (2j + 1)(k + 1) / (2n))
+      REDFT01  c cos(pi j (2k + 1) / (2n)), c = 1 at j = 0, else 2             RODFT01  (-1)^k at j = n - 1, else 2 sin(pi (j + 1)(2k + 1) / (2n))
+      REDFT11  2 cos(pi (2j + 1)(2k + 1) / (4n))                               RODFT11  2 sin(pi (2j + 1)(2k + 1) / (4n))
+    (tests/test_r2r_exact_host.py holds these against scipy.)"""
+    ld = np.longdouble
+    pi = ld(4) * np.arctan(ld(1))
+    j = int(j)
+    assert 0 <= j < n and (n >= 2 or kind != REDFT00), (kind, n, j)
+    k = np.arange(n, dtype=np.int64)
+
+    def phase(m, half):               # pi m / half, m reduced modulo the period 2 half
+        return pi * (m % (2 * half)).astype(ld) / ld(half)
+    if kind == REDFT00:
+        y = (1 if j in (0, n - 1) else 2) * np.cos(phase(j * k, n - 1))
+    elif kind == REDFT10:
+        y = 2 * np.cos(phase((2 * j + 1) * k, 2 * n))
+    elif kind == REDFT01:
+        y = (1 if j == 0 else 2) * np.cos(phase(j * (2 * k + 1), 2 * n))
+    elif kind == REDFT11:
+        y = 2 * np.cos(phase((2 * j + 1) * (2 * k + 1), 4 * n))
+    elif kind == RODFT00:
+        y = 2 * np.sin(phase((j + 1) * (k + 1), n + 1))
+    elif kind == RODFT10:
+        y = 2 * np.sin(phase((2 * j + 1) * (k + 1), 2 * n))
+    elif kind == RODFT01:
+        y = (1 - 2 * (k % 2)).astype(ld) if j == n - 1 else 2 * np.sin(phase((j + 1) * (2 * k + 1), 2 * n))
+    else:
+        assert kind == RODFT11, kind
+        y = 2 * np.sin(phase((2 * j + 1) * (2 * k + 1), 4 * n))
+    return np.asarray(y, dtype=np.float64)
+
+
+def r2r_impulse_case(kind, N, mapping):
+    """(shape, axis, x, want) of the impulse family of one r2r plan: n = r2r_points(kind, N) points along `axis`, line b holds a
+    unit impulse at r2r_positions(n)[b mod 16], `want` its exact response in float64.  No batch is a multiple of a kernel
+    tile (T = 1 ... 16 rows, 2 ... 32 columns), so the tail code of every adapter runs: 'rows' (19, n); 'cols' (n, 19);
+    'middle' (3, n, 7) -- 3 slabs of 7 strided lines."""
+    n = r2r_points(kind, N)
+    shape, axis = {'rows': ((19, n), 1), 'cols': ((n, 19), 0), 'middle': ((3, n, 7), 1)}[mapping]
+    pos = r2r_positions(n)
+    lead = shape[:axis] + shape[axis + 1:]
+    lines = int(np.prod(lead))
+    xl, wl = np.zeros((lines, n)), np.empty((lines, n))          # one line per row, in the order of the other axes
+    exact = {}
+    for b in range(lines):
+        j = pos[b % len(pos)]
+        if j not in exact:
+            exact[j] = r2r_exact_impulse(kind, n, j)
+        xl[b, j] = 1
+        wl[b] = exact[j]
+    x, want = (np.ascontiguousarray(np.moveaxis(v.reshape(lead + (n,)), -1, axis)) for v in (xl, wl))
+    assert x.shape == shape and x.sum() == lines
+    return shape, axis, x, want
+
+
+def r2r_impulse_errors(kind, N, dt, mapping, describe=None):
+    """Table and adapter integrity of ONE r2r plan of logical length N (plan.cpp plan_r2r_line): every kind computes
+    y[k] = Re(post[k] DFT_N(pre x)[idx0 + k]), so each output of a unit impulse at j is the bare product
+    pre[j] w^((pos0 + j)(idx0 + k)) post[k] -- a wrong entry of either table, a wrong index shift, a zero-fill or a store
+    that runs past its line (the type-1 kinds have a line pitch n != N / 2) shows at full size, and in the neighbouring
+    line: every line is checked, and the output starts as NaN, so an entry left unwritten shows too.
+    Out of place through fftw.get_planned_FFT.  Returns max |got - exact| over all lines, in units of 1 (the exact
+    answer's peak is 2); `describe`, a list, receives gfft_plan_describe of the plan."""
+    from mpi4py_fft_amd import fftw, asdevice
+    rdt = 'd' if dt in 'dD' else 'f'
+    shape, axis, x, want = r2r_impulse_case(kind, N, mapping)
+    a = asdevice(x.astype(rdt))
+    b = asdevice(np.full(shape, np.nan, dtype=rdt))
+    plan = fftw.get_planned_FFT(a, b, (axis,), [kind])
+    if describe is not None:
+        describe.append(plan._eng.plan_describe(plan._plan))
+    got = np.asarray(plan()).astype('d')
+    plan.destroy()
+    assert got.shape == want.shape
+    err = np.abs(got - want).max()
+    return float('inf') if np.isnan(err) else float(err)
+
+
+def r2r_path(describe, N, mapping):
+    """Which implementation ran a serial r2r plan, from gfft_plan_describe's text: 'adapter' is ONE register-kernel pass of
+    length N in the mapping's own kernel; the fallback is embed ... extract around a complex plan, with Bluestein's
+    multiplication in between for lengths with a large prime factor."""
+    text = '\n'.join(describe)
+    if 'embed' in text:
+        assert 'extract' in text, text
+        return 'bluestein' if 'multiply by B' in text else 'fallback'
+    passes = [ln for ln in text.splitlines() if 'kernel=' in ln]
+    assert len(passes) == 1 and ' n=%d ' % N in passes[0], text
+    assert ('kernel=regs-rows' if mapping == 'rows' else 'kernel=regs-cols') in passes[0], text
+    return 'adapter'
 
 
 def dirty_spectrum(shape, dt, seed):

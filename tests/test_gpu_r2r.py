@@ -55,11 +55,15 @@ def test_all_kinds_against_scipy(typ, dt):
             got = np.asarray(plan())
             assert got.dtype == A.dtype and got.shape == A.shape
             assert np.abs(got - want).max() <= tol * np.abs(want).max(), (planner.__name__, typ, shape, axes)
+            # ... and at rounding level: 2 eps log2 of the LOGICAL points (the complex transforms these kinds run on)
+            nelem = int(np.prod([O.r2r_logical_n(table[typ], shape[ax]) for ax in axes]))
+            cases.assert_close(got, want, dt, nelem, (planner.__name__, typ, shape, axes))
             # inverse: idct(dct(x)) * M == x   (tests/test_fftw.py:135-138)
             inv = iplanner(plan.output_array, axes=axes, type=typ)
             M = fftw.get_normalization(plan.kind, shape, axes)
             back = np.asarray(inv()) * M
             assert np.abs(back - A).max() <= tol * 10 * max(1.0, np.abs(A).max()), (planner.__name__, typ, shape, axes)
+            cases.assert_roundtrip(back.astype('d'), A.astype('d'), dt, nelem, (planner.__name__, typ, shape, axes, 'round trip'))
             assert inv.kind == tuple(fftw.inverse[k] for k in plan.kind)
             plan.destroy()
             inv.destroy()
@@ -78,6 +82,7 @@ def test_mixed_kinds_per_axis_and_in_place():
             want = O.r2r_1d(want, ax, k)
         got = np.asarray(plan())
         assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), kinds
+        cases.assert_close(got, want, 'd', int(np.prod([O.r2r_logical_n(k, shape[ax]) for ax, k in zip(axes, kinds)])), kinds)
         plan.destroy()
 
 
@@ -99,13 +104,19 @@ def test_libfft_transforms_dict(dt):
     tol = 1e-12 if dt == 'd' else 1e-4
     for shape, axes in (((12, 10), (1,)), ((12, 10), (0, 1)), ((6, 8, 10), (1, 2))):
         fft = FFT(shape, axes, dtype=dt, transforms={tuple(axes): (dctn, idctn)})
-        ref = O.OFFT(shape, axes, dt, r2r=fftw.FFTW_REDFT01)
+        # the 'd' oracle on the input widened to float64, whatever `dt`: r2r_1d keeps float32 input in float32, so the 'f'
+        # oracle is no high-precision reference (the trap cases.check_pfft_backward_vs_oracle documents for irfft)
+        ref = O.OFFT(shape, axes, 'd', r2r=fftw.FFTW_REDFT01)
         A = O.rng_array(shape, dt, 2)
         B = np.asarray(fft.forward(asdevice(A)))
-        want = ref.forward(A)
+        want = ref.forward(A.astype('d'))
+        assert want.dtype == np.float64
         assert B.dtype == A.dtype and np.abs(B - want).max() <= tol * max(1e-30, np.abs(want).max())
-        A2 = np.asarray(fft.backward(asdevice(want)))
+        nelem = int(np.prod([O.r2r_logical_n(fftw.FFTW_REDFT01, shape[ax]) for ax in axes]))
+        cases.assert_close(B.astype('d'), want, dt, nelem, (shape, axes, dt))
+        A2 = np.asarray(fft.backward(asdevice(want.astype(dt))))
         assert np.abs(A2 - A).max() <= tol * 10
+        cases.assert_roundtrip(A2.astype('d'), A.astype('d'), dt, nelem, (shape, axes, dt, 'backward of the exact spectrum'))
         fft.destroy()
 
 
@@ -145,6 +156,8 @@ def test_pfft_with_r2r_transforms(P):
             assert uh.shape == want[r].shape and uh.dtype == want[r].dtype, (shape, axes)
             assert np.abs(uh - want[r]).max() <= 1e-12 * max(1e-30, np.abs(want[r]).max()), (shape, axes)
             assert np.abs(back - G[sl]).max() <= 1e-12, (shape, axes)
+            cases.assert_close(uh, want[r], 'd', int(np.prod(shape)), (shape, axes, P, r))
+            cases.assert_roundtrip(back, G[sl], 'd', int(np.prod(shape)), (shape, axes, P, r))
 
 
 def test_hermitian_planners():

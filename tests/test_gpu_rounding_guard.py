@@ -14,6 +14,9 @@ This file holds the impulse family over every kernel family and both precisions 
 `tests/cases.py real_impulse_errors`), whose Hermitian pass reads a table no complex plan does -- and the proof that the guards bite: one
 twiddle entry off by 1e-9 (fp64) / 1e-5 (fp32), injected through the library's test hook (`gfft_set_option
 "debug_tw_exp"`, plan.cpp get_twiddles), fails them while the contract tolerances alone let it through.
+The third family, the real-to-real kinds (DCT / DST I-IV), reads two tables of its own (plan.cpp get_r2r_tables) through load /
+store adapters no other plan uses: its impulse family, and the proof through a hook of its own ("debug_r2r_exp"), are in
+tests/test_gpu_r2r_guard.py (`tests/cases.py r2r_impulse_errors`).
 Reference tolerance for the same kind of check: /root/reference/tests/test_libfft.py:17 (abstol f = 5e-5, d = 1e-14).
 """
 import numpy as np
