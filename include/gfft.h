@@ -293,6 +293,21 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *   gfft_ps_cross    out = a x b, real fields, count = n0*n1*n2 per component   cross, :69-74
  *   gfft_ps_project  P = sum(du*K/|K|^2); du -= P*K; du -= nu*|K|^2*u_hat      compute_rhs, :88-90
  *   gfft_ps_rk_stage u = u0 + cb*du (skipped when d_u is NULL); u1 += ca*du; `count` real scalars   :112-116
+ *                    The contract of these four.  Layouts: d_u_hat, d_du_hat and d_out of gfft_ps_curl are complex
+ *                    [3][n0][n1][n2], contiguous, of `precision` (GFFT_F32 / GFFT_F64), as are the vectors d_k0/1/2 (real); d_a,
+ *                    d_b and d_out of gfft_ps_cross are real [3][count]; the four operands of gfft_ps_rk_stage are `count`
+ *                    contiguous real scalars each (a complex field counts twice its values).  Every value is formed in the
+ *                    field's precision: nu, cb and ca are converted to it once.  K is applied as given: no wavenumber is
+ *                    treated specially but |K|^2 = 0, which the projection divides by 1 instead (du comes back in value).
+ *                    Real and imaginary parts never mix except through the factor i of the curl, so a NaN in one part of one
+ *                    operand of a mode reaches the parts of that mode it feeds and no other mode.
+ *                    Read only: d_u_hat, d_k0/1/2, d_a, d_b, d_u0, d_du.  Written: d_out (every element; not read), d_du_hat
+ *                    (in place, mode by mode), d_u (every element; not read) and d_u1 (in place).  d_out overlaps no input;
+ *                    d_du_hat does not overlap d_u_hat; d_u and d_u1 overlap each other and the other operands nowhere (d_u0
+ *                    is read only when d_u is given).  An empty block (n0 n1 n2 = 0, count = 0) launches nothing and is
+ *                    GFFT_OK.  GFFT_ERR_INVALID before a device is touched for: a null pointer -- any but d_u, and d_u0 when
+ *                    d_u is NULL --, a negative extent or count, a precision other than GFFT_F32 / GFFT_F64.  All four
+ *                    only enqueue on `stream`: no synchronisation, no allocation.
  *   gfft_ps_spectrum shell spectrum of u_hat[ncomp][n0][n1][n2] in ONE read, every mode in double whatever the precision:
  *                      b = floor(sqrt(k0^2 + k1^2 + k2^2) / dk + 0.5)      (modes with b >= nbins are dropped)
  *                      e = 0.5 * w2[i2] * sum_c |u_hat_c|^2                (d_w2 NULL: weight 1)

@@ -132,12 +132,24 @@ DealiasMask.__doc__ = """What `SpectralOps.dealias_mask` returns: per-axis uint8
 keep; None = the whole axis) and the spherical cut |k| <= kcut (inf: none)."""
 
 
-def _prec(a):
-    return _lib.precision_of(a.dtype)
-
-
 def _t(a):
     return a.tensor if isinstance(a, DeviceArray) else a
+
+
+_REAL, _COMPLEX = (torch.float32, torch.float64), (torch.complex64, torch.complex128)
+
+
+def _operands(kinds, *fields):
+    """(tensors, precision) of the operands of one pointwise kernel: all of ONE dtype among `kinds` and contiguous, which is
+    what the kernel takes for granted -- it indexes every operand as it indexes the first.  None stays None."""
+    ts = [None if f is None else _t(f) for f in fields]
+    given = [t for t in ts if t is not None]
+    assert all(isinstance(t, torch.Tensor) for t in given), 'the operands are device arrays or tensors'
+    dtype = given[0].dtype
+    assert dtype in kinds, dtype
+    assert all(t.dtype == dtype for t in given), 'the operands differ in dtype: %s' % [t.dtype for t in given]
+    assert all(t.is_contiguous() for t in given), 'an operand is not contiguous'
+    return ts, (8 if dtype in (torch.float64, torch.complex128) else 4)
 
 
 class SpectralOps:
@@ -168,10 +180,12 @@ class SpectralOps:
         assert precision == (8 if self.K[0].dtype == torch.float64 else 4), 'field and transform differ in precision'
 
     def curl(self, u_hat, out):
-        """out = 1j * (K x u_hat); both [3] + spectral shape, complex."""
+        """out = 1j * (K x u_hat); both [3] + spectral shape, complex, contiguous, of the transform's precision; out overlaps
+        nothing.  K is applied as given.  Returns out."""
         assert tuple(u_hat.shape) == (3,) + self.shape == tuple(out.shape)
-        self._same_precision(_prec(u_hat))
-        _lib.engine().ps_curl(_t(u_hat), _t(out), self.K, self.shape, _prec(u_hat))
+        (tu, to), precision = _operands(_COMPLEX, u_hat, out)
+        self._same_precision(precision)
+        _lib.engine().ps_curl(tu, to, self.K, self.shape, precision)
         return out
 
     def gradient(self, f_hat, out):
@@ -283,18 +297,20 @@ class SpectralOps:
         band the result is bit for bit that of force=None.
         dealias=a `dealias_mask()` (or any (m0, m1, m2, kcut)): the same pass also truncates -- a kept mode gets bit for bit
         the result without `dealias`, forced or not; a truncated mode becomes +0 whatever du_hat and u_hat hold there, and
-        nothing of it is loaded.  Nothing synchronises or allocates."""
+        nothing of it is loaded.  du_hat and u_hat are complex, contiguous, of one dtype -- the transform's precision -- and
+        do not overlap.  Nothing synchronises or allocates."""
         assert tuple(du_hat.shape) == (3,) + self.shape == tuple(u_hat.shape)
-        self._same_precision(_prec(du_hat))
+        (tdu, tu), precision = _operands(_COMPLEX, du_hat, u_hat)
+        self._same_precision(precision)
         fargs = None if force is None else self._force(force)
         if dealias is not None:
             m, kcut = self._mask(dealias)
-            _lib.engine().ps_project_dealiased(_t(du_hat), _t(u_hat), self.K, m, self.shape, nu, kcut, fargs, _prec(du_hat))
+            _lib.engine().ps_project_dealiased(tdu, tu, self.K, m, self.shape, nu, kcut, fargs, precision)
         elif fargs is None:
-            _lib.engine().ps_project(_t(du_hat), _t(u_hat), self.K, self.shape, nu, _prec(du_hat))
+            _lib.engine().ps_project(tdu, tu, self.K, self.shape, nu, precision)
         else:
             dk, blo, bhi, gain, tgain = fargs
-            _lib.engine().ps_project_forced(_t(du_hat), _t(u_hat), self.K, self.shape, nu, dk, blo, bhi, gain, tgain, _prec(du_hat))
+            _lib.engine().ps_project_forced(tdu, tu, self.K, self.shape, nu, dk, blo, bhi, gain, tgain, precision)
         return du_hat
 
     def _force(self, force):
@@ -696,11 +712,12 @@ def flux(T):
 
 
 def cross(a, b, out):
-    """out = a x b for real fields of shape [3] + local physical shape."""
+    """out = a x b for real fields of shape [3] + local physical shape: contiguous, of one precision, out overlapping
+    neither input.  Returns out."""
     assert a.shape[0] == 3 and tuple(a.shape) == tuple(b.shape) == tuple(out.shape)
-    assert np.dtype(a.dtype).kind == 'f'
+    (ta, tb, to), precision = _operands(_REAL, a, b, out)
     count = int(np.prod(a.shape[1:], dtype=np.int64))
-    _lib.engine().ps_cross(_t(a), _t(b), _t(out), count, _prec(a))
+    _lib.engine().ps_cross(ta, tb, to, count, precision)
     return out
 
 
@@ -725,14 +742,16 @@ def scalar_flux(u, theta, out):
 def rk_stage(u, u0, u1, du, cb, ca, dt=None):
     """u = u0 + cb*du (skipped when u is None); u1 += ca*du -- one pass over the four arrays.
     dt: a device double tensor; the coefficients are then cb * dt[0] and ca * dt[0], multiplied on the device (bit for
-    bit the result of passing the host products), so a captured stage follows a step that `timestep(out=)` wrote."""
-    mult = 2 if np.dtype(du.dtype).kind == 'c' else 1
-    count = int(np.prod(du.shape, dtype=np.int64)) * mult
+    bit the result of passing the host products), so a captured stage follows a step that `timestep(out=)` wrote.
+    The fields have any one shape and one dtype, real or complex (a complex value is two reals to the kernel), and are
+    contiguous; u needs u0 (u0 without u is not read); u and u1 overlap nothing else."""
+    assert u is None or u0 is not None, 'u needs u0'
+    (tu, tu0, tu1, tdu), precision = _operands(_REAL + _COMPLEX, u, u0, u1, du)
+    assert all(t is None or tuple(t.shape) == tuple(tdu.shape) for t in (tu, tu0, tu1)), 'the fields differ in shape'
+    count = int(tdu.numel()) * (2 if tdu.dtype in _COMPLEX else 1)
     if dt is not None:
         dt = _t(dt)
         assert dt.dtype == torch.float64 and dt.numel() >= 1 and dt.is_contiguous()
-        _lib.engine().ps_rk_stage_dt(None if u is None else _t(u), None if u0 is None else _t(u0), _t(u1), _t(du),
-                                     count, cb, ca, dt, _prec(du))
+        _lib.engine().ps_rk_stage_dt(tu, tu0, tu1, tdu, count, cb, ca, dt, precision)
         return
-    _lib.engine().ps_rk_stage(None if u is None else _t(u), None if u0 is None else _t(u0), _t(u1), _t(du),
-                              count, cb, ca, _prec(du))
+    _lib.engine().ps_rk_stage(tu, tu0, tu1, tdu, count, cb, ca, precision)
