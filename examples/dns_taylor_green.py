@@ -48,6 +48,12 @@ nine backward transforms give A_ij = d u_i / d x_j, and `SpectralOps.gradient_st
 steps at 64^3 with dealias='2/3' the longitudinal skewness is GRADIENT_SKEWNESS below (measured on one MI355X; the reference has
 no such diagnostic).
 
+`pdfs=True` (with `gradients=True`) adds the distributions those moments compress, from the same A: the joint histogram of the
+invariants (R, Q) by `SpectralOps.gradient_pdf` on a plane scaled by <Q_w> = <|w|^2> / 4, and the PDF of the longitudinal
+derivatives pooled over the three directions, three `SpectralOps.histogram` calls added; counts are integers, so one rank and
+many give the same tables.  `solve(w, verbose=True, gradients=True, pdfs=True, dealias='2/3')` prints the shares of the four
+(R, Q) quadrants.
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -65,11 +71,12 @@ DEALIASED_ENERGY = 0.124953117516743          # solve(dealias='2/3'), M = 6, 10 
 SCALAR_VARIANCE = 0.126225641497587           # 'scalar_variance' of solve(scalar=(nu, (1, 0, 0))), M = 6, 10 steps
 IF_ENERGY = 0.124953117516741                 # solve(integrator='ifrk4'), M = 6, 10 steps
 GRADIENT_SKEWNESS = -0.064835990474654        # 'gradients'.skewness of solve(gradients=True, dealias='2/3'), M = 6, 10 steps
+PDF_BINS, PDF_R, PDF_Q, PDF_SIGMAS = 128, 4.0, 6.0, 6.0     # solve(pdfs=True): bins per axis; the (R, Q) plane in <Q_w>^(3/2), <Q_w>; the derivative range
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
           transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
-          scalar=None, integrator='rk4', gradients=False):
+          scalar=None, integrator='rk4', gradients=False, pdfs=False):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -97,8 +104,17 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     gradients=True: a dict passed as `stats` receives 'gradients', the `spectral.gradient_moments` (with nu) of the velocity-gradient
     tensor of the final state -- on the fused path from `SpectralOps.gradient`, nine backward transforms and
     `SpectralOps.gradient_stats`, on the fused=False path from array-sized torch expressions (the A/B baseline).  It reads the
-    final U_hat only and combines with every option above; the diagnostic itself runs once, outside any captured step."""
-    from mpi4py_fft_amd import PFFT, newDistArray, spectral
+    final U_hat only and combines with every option above; the diagnostic itself runs once, outside any captured step.
+    pdfs=True (needs gradients=True and the fused path): the distributions behind those moments, from the same A -- a dict passed
+    as `stats` receives 'pdfs', a dict with 'rq' (the `spectral.joint_pdf` of the invariants (R, Q) on +-PDF_R <Q_w>^(3/2) x
+    +-PDF_Q <Q_w>, <Q_w> = <|w|^2> / 4 from the sums of `gradient_stats`, PDF_BINS^2 bins, by `SpectralOps.gradient_pdf`),
+    'longitudinal' (the `spectral.pdf` of d u_i / d x_i pooled over i on +-PDF_SIGMAS standard deviations, PDF_BINS bins: three
+    `SpectralOps.histogram` calls added), the int64 tables themselves ('rq_counts', 'longitudinal_counts'), their ranges
+    ('rq_range', 'longitudinal_range') and 'quadrants', the shares of the in-range points in the four quarters of the table: (lower
+    half of the R range, upper half of the Q range), (upper, upper), (lower, lower), (upper, lower).  The halves meet at 0 to
+    within the rounding of the bin rule: a point with R or Q exactly 0 may count on either side."""
+    from mpi4py_fft_amd import PFFT, _lib, newDistArray, spectral
+    assert not pdfs or (gradients and fused), 'pdfs needs gradients=True and the fused path'
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
     FFT = PFFT(world, N, collapse=False)                      # real input: r2c along axis 2
@@ -393,6 +409,24 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         if verbose and world.Get_rank() == 0:
             print('  gradients: dissipation %.9e, enstrophy %.9e, skewness %.6e, flatness %.6f, Betchov ratio %.12f, rms div %.1e'
                   % (gm.dissipation, gm.enstrophy, gm.skewness, gm.flatness, gm.betchov, gm.div_rms))
+        if pdfs:
+            qw = float(gs[_lib.GS_WW]) / npts / 4.0           # <Q_w> = <|w|^2> / 4: the scale of the (R, Q) plane
+            rq_range = ((-PDF_R * qw ** 1.5, PDF_R * qw ** 1.5), (-PDF_Q * qw, PDF_Q * qw))
+            rq = ops.gradient_pdf(A, 'R', 'Q', range=rq_range, bins=PDF_BINS)          # rank-reduced; one read of A
+            sigma = float(np.sqrt(gs[_lib.GS_LONG2] / (3.0 * npts)))                   # of d u_i / d x_i, pooled over i
+            lrange = (-PDF_SIGMAS * sigma, PDF_SIGMAS * sigma)
+            lcounts = sum(ops.histogram(A[i][i], lrange, PDF_BINS) for i in range(3))  # counts add: the pooled PDF
+            table = rq[:PDF_BINS * PDF_BINS].reshape(PDF_BINS, PDF_BINS)
+            h = PDF_BINS // 2                                  # bins below h: the lower half of a range (0 itself: bin h or h - 1, as t rounds)
+            inside = max(int(table.sum()), 1)
+            quadrants = tuple(float(q.sum()) / inside for q in (table[:h, h:], table[h:, h:], table[:h, :h], table[h:, :h]))
+            if stats is not None:
+                stats.update(pdfs=dict(rq=spectral.joint_pdf(rq, rq_range, PDF_BINS), rq_counts=rq, rq_range=rq_range,
+                                       longitudinal=spectral.pdf(lcounts, lrange), longitudinal_counts=lcounts,
+                                       longitudinal_range=lrange, quadrants=quadrants))
+            if verbose and world.Get_rank() == 0:
+                print('  (R, Q) table by halves of its ranges: R lower, Q upper %.4f;  R upper, Q upper %.4f;  R lower, Q lower %.4f;  R upper, Q lower %.4f  (%d of %d points outside)'
+                      % (quadrants + (int(rq[-2]), npts)))
     if transfer:
         assert fused and not spectrum
         compute_rhs_fused(0.0)                                # dU = N_hat: no viscous term

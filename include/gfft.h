@@ -499,10 +499,52 @@ int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *s
  *                    atomics; the partial results of the workgroups go through the stream's scratch (no more of it than
  *                    gfft_ps_stats asks for; allocated by the first call: run it once before capturing it).  An empty block
  *                    (count = 0) writes zeros.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, count < 0,
- *                    precision.  Only enqueues. */
+ *                    precision.  Only enqueues.
+ *   The distributions behind those moments: histograms in ONE read, as int64 counts.  Counts are integers, so a result is exact,
+ *   independent of the order in which the points arrive, repeats bit for bit and adds over ranks in any order.
+ *   THE BIN RULE, the same everywhere: for a value x, converted to double before any arithmetic, a range [lo, hi) and
+ *   w = (double)nbins / (hi - lo), formed ONCE on the host,
+ *                      t = (x - lo) * w          (a subtraction, then a multiply: nothing a compiler may contract, so one
+ *                                                 defined sequence of IEEE double operations that any host can restate)
+ *                      x NaN        -> the NaN slot
+ *                      t < 0        -> below
+ *                      t >= nbins   -> above     (+inf, hi itself and a value within rounding of hi: the upper edge is exclusive)
+ *                      otherwise    -> bin (int)t
+ *   gfft_ps_histogram   the histograms of the ncomp <= 4 components of a REAL field d_u = [ncomp][count] (the layout of
+ *                    gfft_ps_stats) in one read, component c over its own range [lo[c], hi[c]) (HOST doubles, by value in the
+ *                    launch) with `nbins` bins each.  d_out = int64[ncomp][nbins + GFFT_PS_PDF_TAIL] on the device, OVERWRITTEN:
+ *                    out[c][0 .. nbins - 1] the bins, then out[c][nbins] = below, [nbins + 1] = above, [nbins + 2] = NaN; the
+ *                    entries of every component add up to `count`.
+ *   gfft_ps_gradient_pdf   the histogram of one, or the joint histogram of two, of the per-point quantities of
+ *                    gfft_ps_gradient_stats on d_A = [3][3][count]: GFFT_PS_Q_SS, _WW, _DIV, _Q, _R, _SSS, _WSW name ss, ww, div,
+ *                    Q, R, sss and wsw with the expressions and associations written out above.  Here FMA contraction is
+ *                    switched OFF: every operation of those expressions is rounded on its own, so each quantity is exactly
+ *                    the value the same expression gives in IEEE double arithmetic on any host, and the counts can be compared
+ *                    for equality (gfft_ps_gradient_stats itself stays as it is).  Only the quantities named by qx and qy are
+ *                    evaluated; A is read once.  A NaN in a_ij reaches the quantities that read a_ij only (div reads the
+ *                    diagonal alone, ww everything but the diagonal).
+ *                    qy == GFFT_PS_Q_NONE (then nby must be 1, ylo and yhi are ignored): d_out = int64[nbx + 3], laid out as one
+ *                    component of gfft_ps_histogram.  Otherwise the joint table d_out = int64[nbx * nby + 2]: bin bx * nby + by,
+ *                    then [nbx nby] = outside, counted when either coordinate is below or above its range, then [nbx nby + 1]
+ *                    = NaN, counted when either quantity is NaN (this wins over outside).  The entries add up to `count`.
+ *                    Both: the launch geometry of gfft_ps_stats (16 bytes per lane and component where they divide `count` and
+ *                    the base is 16-byte aligned, one element otherwise); 32-bit counters in a workgroup's LDS, bumped by
+ *                    integer LDS adds, go through the stream's scratch (about 32 MiB at most, a quarter of what
+ *                    gfft_ps_spectrum asks for at its bin limit; allocated by a stream's first call: run it once before capturing it) and are summed to
+ *                    int64; no floating-point atomics.  An empty block (count = 0) writes zeros to all of d_out.
+ *                    GFFT_ERR_INVALID (before a device is touched) for a null pointer, ncomp < 1, count < 0, a bin count < 1, a
+ *                    range that is not finite, has lo >= hi or whose hi - lo or w is not finite, an unknown quantity, qx ==
+ *                    GFFT_PS_Q_NONE, qy == GFFT_PS_Q_NONE with nby != 1, precision.  GFFT_ERR_UNSUPPORTED for ncomp > 4, nbins
+ *                    > 4096 (gfft_ps_histogram: per component), nbx > 4096 in a 1-D and nbx * nby > 16384 in a joint
+ *                    gfft_ps_gradient_pdf (64 KiB of 32-bit counters: the LDS a workgroup gets without opting in to more), and
+ *                    for a count so large that one workgroup's chunk would reach 2^32 points (2^41 points and beyond).
+ *                    Both only enqueue: no synchronisation, no allocation after the stream's first call. */
 enum { GFFT_PS_DOT = 0, GFFT_PS_HELICITY = 1 };
 enum { GFFT_PS_STATS_HEAD = 2, GFFT_PS_STATS_PER_COMP = 6 };
 enum { GFFT_PS_GRAD_NVAL = 20 };
+enum { GFFT_PS_PDF_TAIL = 3 };   /* after the bins of a 1-D histogram: [below] [above] [NaN] */
+enum { GFFT_PS_Q_NONE = -1, GFFT_PS_Q_SS = 0, GFFT_PS_Q_WW, GFFT_PS_Q_DIV, GFFT_PS_Q_Q, GFFT_PS_Q_R,
+       GFFT_PS_Q_SSS, GFFT_PS_Q_WSW, GFFT_PS_Q_COUNT };
 int gfft_ps_curl(const void *d_u_hat, void *d_out, const void *d_k0, const void *d_k1, const void *d_k2,
                  int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
 int gfft_ps_cross(const void *d_a, const void *d_b, void *d_out, int64_t count, int precision, void *stream);
@@ -553,6 +595,13 @@ int gfft_ps_gradient(const void *d_f_hat /* [ncomp][n0][n1][n2] complex */,
 int gfft_ps_gradient_stats(const void *d_A /* [3][3][count] real, A[i][j] = d u_i / d x_j */,
                            int64_t count, double *d_out /* [GFFT_PS_GRAD_NVAL], overwritten */,
                            int precision, void *stream);
+int gfft_ps_histogram(const void *d_u /* [ncomp][count] real */, int ncomp, int64_t count,
+                      const double *lo, const double *hi /* host, ncomp each */, int nbins,
+                      int64_t *d_out /* [ncomp][nbins + 3], overwritten */, int precision, void *stream);
+int gfft_ps_gradient_pdf(const void *d_A /* [3][3][count] real */, int64_t count,
+                         int qx, double xlo, double xhi, int nbx,
+                         int qy, double ylo, double yhi, int nby,
+                         int64_t *d_out, int precision, void *stream);
 
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:

@@ -21,6 +21,10 @@ PS_GRAD_NVAL = 20                       # gfft_ps_gradient_stats' output: double
 (GS_MAX_SS, GS_MAX_WW, GS_MAX_DIV, GS_DIV2, GS_SS, GS_WW, GS_SS2, GS_WW2, GS_SSWW, GS_Q, GS_R, GS_Q2, GS_R2, GS_SSS, GS_WSW,
  GS_LONG2, GS_LONG3, GS_LONG4, GS_TRANS2, GS_TRANS4) = range(PS_GRAD_NVAL)
 PS_GRAD_NMAX = 3                        # entries 0 ... 2 are maxima, the rest sums
+PS_PDF_TAIL = 3                         # behind the bins of a 1-D histogram: [below] [above] [NaN]
+PS_Q_NONE = -1                          # gfft_ps_gradient_pdf's quantities, named as in gfft_ps_gradient_stats
+PS_Q_SS, PS_Q_WW, PS_Q_DIV, PS_Q_Q, PS_Q_R, PS_Q_SSS, PS_Q_WSW, PS_Q_COUNT = range(8)
+PS_PDF_MAX_BINS, PS_PDF_MAX_JOINT = 4096, 16384      # bins of a 1-D table (per component) and of a joint one
 
 _lib = None
 
@@ -100,6 +104,10 @@ def _declare(lib):
                                           c.c_double, c.c_double, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
         'gfft_ps_gradient': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_int, vp]),
         'gfft_ps_gradient_stats': (c.c_int, [vp, c.c_int64, vp, c.c_int, vp]),
+        'gfft_ps_histogram': (c.c_int, [vp, c.c_int, c.c_int64, c.POINTER(c.c_double), c.POINTER(c.c_double), c.c_int, vp,
+                                        c.c_int, vp]),
+        'gfft_ps_gradient_pdf': (c.c_int, [vp, c.c_int64, c.c_int, c.c_double, c.c_double, c.c_int, c.c_int, c.c_double,
+                                           c.c_double, c.c_int, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -558,6 +566,24 @@ class HipEngine:
         self.require_device(ta)
         self.require_device(tout)
         check(lib().gfft_ps_gradient_stats(ta.data_ptr(), int(count), tout.data_ptr(), precision, current_stream()))
+
+    def ps_histogram(self, tu, ncomp, count, lo, hi, nbins, tout, precision):
+        """gfft_ps_histogram: tu = real [ncomp][count]; lo, hi = ncomp host floats each; tout = int64[ncomp][nbins + PS_PDF_TAIL]
+        on the device, overwritten."""
+        self.require_device(tu)
+        self.require_device(tout)
+        los = (ctypes.c_double * int(ncomp))(*[float(x) for x in lo])
+        his = (ctypes.c_double * int(ncomp))(*[float(x) for x in hi])
+        check(lib().gfft_ps_histogram(tu.data_ptr(), int(ncomp), int(count), los, his, int(nbins), tout.data_ptr(), precision,
+                                      current_stream()))
+
+    def ps_gradient_pdf(self, ta, count, qx, xr, nbx, qy, yr, nby, tout, precision):
+        """gfft_ps_gradient_pdf: ta = real [3][3][count]; qx, qy among PS_Q_* (qy = PS_Q_NONE: the 1-D table of qx, nby = 1);
+        xr, yr = (lo, hi); tout = int64[nbx + PS_PDF_TAIL] or int64[nbx * nby + 2] on the device, overwritten."""
+        self.require_device(ta)
+        self.require_device(tout)
+        check(lib().gfft_ps_gradient_pdf(ta.data_ptr(), int(count), int(qx), float(xr[0]), float(xr[1]), int(nbx), int(qy),
+                                         float(yr[0]), float(yr[1]), int(nby), tout.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

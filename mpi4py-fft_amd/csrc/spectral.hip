@@ -8,7 +8,9 @@
 //     of three array-sized meshes (the reference's K is a (3, n0, n1, n2) float array: 1.5x the velocity);
 //   * reductions, sharing one launch geometry (sp_geometry) and the stream's scratch for their per-workgroup slabs: shell sums
 //     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity), physical-space statistics (ps_stats_kernel) and the
-//     statistics of the velocity-gradient tensor (ps_gradient_stats_kernel, behind the pointwise ps_gradient_kernel: i K_j f_hat).
+//     statistics of the velocity-gradient tensor (ps_gradient_stats_kernel, behind the pointwise ps_gradient_kernel: i K_j f_hat);
+//   * histograms over the same geometry: integer counts in a workgroup's LDS table (ps_histogram_kernel: the components of a
+//     real field; ps_gradient_pdf_kernel: one or two of the gradient invariants per point), summed to int64 by pd_sum_kernel.
 #include "../../include/gfft.h"
 #include "gfft_internal.h"
 
@@ -592,6 +594,9 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // ps_rk_if_kernel<double / float, UNIFORM> 72 / 44 (7 and 8 waves per SIMD), <double / float, per component> 60 / 30 (8 waves).
 // ps_gradient_kernel<double, NC = 1 ... 4> 40, 50, 66, 64 (7 waves per SIMD at NC = 3, else 8) and <float, NC> 28, 40, 48, 54;
 // ps_gradient_stats_kernel<double, 2> 112 and <float, 4> 128 (4 waves per SIMD), <double, 1> 90, <float, 1> 90 (5 waves); gs_reduce_kernel 11.
+// ps_histogram_kernel<double, 2, NC = 1 ... 4> 54, 58, 60, 64 and <float, 4, NC> the same (8 waves per SIMD), one element per lane 54 ... 64;
+// ps_gradient_pdf_kernel<double, 2, 1-D / joint> 78 / 84 (6 / 5 waves per SIMD) and <float, 4, .> 92 / 98 (5 / 4 waves), <., 1, .> 58 / 62 (8 waves);
+// pd_sum_kernel 48 (8 waves).
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -949,6 +954,225 @@ gs_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__
   st_reduce_value<gs_kind>(slabs, nwg, out);
 }
 
+// ---- one-pass PDFs: histograms of a real field and (joint) histograms of the gradient invariants -------------------------
+// Counts are integers: the result is exact, independent of arrival order, bit for bit repeatable and additive over ranks.
+// The bin rule (include/gfft.h), for x converted to double before any arithmetic and w = (double)nbins / (hi - lo) formed ONCE
+// on the host:  t = (x - lo) * w;  x NaN -> the NaN slot;  t < 0 -> below;  t >= nbins -> above (+inf and a value within
+// rounding of hi included: the upper edge is exclusive);  otherwise bin (int)t.  A subtraction followed by a multiply cannot
+// be contracted: one defined sequence of IEEE operations.  pd_bin returns the slot: 0 ... nbins - 1, nbins (below),
+// nbins + 1 (above), nbins + 2 (NaN) -- a bin index is < nbins by the comparison itself, never by a clamp.
+// Geometry: that of ps_stats_kernel (256 lanes, one contiguous chunk of whole steps of 256 V points per workgroup, 16 bytes
+// per lane and component; V = 1 where count % V != 0 or the base is not 16-byte aligned), except that a table beyond
+// 4096 counters takes fewer workgroups (pd_max_wg: 512 at the 16384 counters of a 128 x 128 joint table -- two 64 KiB
+// tables are resident per CU, and the slabs stay a fortieth of the bytes of A at 256^3 instead of a tenth).
+// Counting: the bins are 32-bit counters in the workgroup's LDS table, bumped by no-return LDS integer adds (ds_add_u32);
+// the tails (below / above / NaN, or outside / NaN of a joint table) are lane registers, combined once at the end through
+// the then idle table.  A workgroup counts at most its chunk, which the entry points keep below 2^32 points
+// (GFFT_ERR_UNSUPPORTED beyond: count >= 2^32 x pd_max_wg, 2^41 points at the fewest workgroups).
+// Workgroup tables go to slabs [workgroup][counters + tails] in the stream's scratch (at most 2048 x (4096 + 12) or 512 x
+// (16384 + 2) 32-bit words, 32.1 MiB: a quarter of the 128 MiB gfft_ps_spectrum asks for at ITS bin limit; at equal bins a
+// four-component table asks for the spectrum's 32768 nbins bytes plus 96 KiB of tails) and pd_sum_kernel adds them to int64
+// and OVERWRITES d_out.  Chosen over 64-bit atomics on d_out behind a
+// zeroing step: the slab route is the one the shell sums already take (one scratch, no memset node in a captured graph),
+// its cost is a fixed number of streamed bytes, and 2048 workgroups hitting the 259 words of a small table with device-scope
+// atomics is exactly the same-address traffic the LDS table exists to avoid.  No floating-point atomics anywhere.
+// Per-point quantities of the gradient PDFs: gp_quantity, the expressions of gs_point with FMA contraction switched OFF, so
+// each is exactly the IEEE double sequence written in gfft.h (what tests/gradient_ref.pointwise computes); only the
+// quantities named by the call are evaluated (a workgroup-uniform switch per point), A is read once, all nine components.
+// Measured on one MI355X (tools/pdf_probe.py, 256^3, HIP events after a warm-up, minimum of 15 rounds; in brackets eight
+// calls back to back between one pair of events, per call -- a single call also pays what the host spends between the
+// first event and the launch), fp64 / fp32, the copy of the same run at 5.90 TB/s:
+//   (a) histogram, m = 3, 256 bins, normal field   0.157 / 0.111 ms (0.113 / 0.078)      gfft_ps_stats, same array:          0.097 / 0.060 ms (0.081 / 0.054)
+//   (b) the same, constant field (worst case)      0.226 / 0.220 ms (0.207 / 0.207)
+//   (c) gradient_pdf, Q, 256 bins                  0.263 / 0.156 ms (0.246 / 0.150)      gfft_ps_gradient_stats, same array: 0.217 / 0.125 ms (0.211 / 0.120)
+//   (c) gradient_pdf, (R, Q), 128 x 128            0.242 / 0.139 ms (0.227 / 0.131)
+//   (d) torch on the device: histc x 3 43.2 / 0.35 ms; Q as expressions + histc 19.5 / 2.6 ms; R, Q + an index expression +
+//       bincount 4.9 / 3.6 ms (torch.histogramdd has no device kernel)
+// (a) is 1.4 x the moment kernel back to back (1.6 - 1.9 x as single calls), (c) 1.1 - 1.25 x.  What bounded the first
+// form was not the counting: pd_sum_kernel walked 2048 slabs with 8 loads in flight per lane, 75 us whatever the precision
+// ((a) 0.201 / 0.161 ms then, (c) Q 0.306 / 0.200); see its comment.
+// Contention: the LDS adds of lanes that hit one counter serialise, (b) against (a).  Both remedies were built, measured in
+// the same probe (kernels alone, fp64 / fp32; the plain add in that run (a) 0.136 / 0.102, (b) 0.229 / 0.228) and taken out again:
+//   a copy of the table per wave (tables up to 4096 counters), added up at the flush
+//              (a) 0.139 / 0.108  (b) 0.251 / 0.251 -- the conflict is between the lanes of one wave, not between waves: no gain
+//   runs of equal bins within a row of 16 lanes counted by their last lane (the scheme of sp_wave_add; a DPP move, a ballot, a subtraction)
+//              (a) 0.139 / 0.119  (b) 0.139 / 0.117 -- the worst case falls to the common one, which pays 2 / 17 % for it;
+//              (c) is unchanged either way (one add per point beside ~100 fp64 operations)
+// Kept: one add per lane and value -- (b) is the recorded worst case, a field of one value, and stays within 2.6 x (fp64)
+// and 4 x (fp32) of the moment kernel; a real PDF's peak holds a few per cent of the points.  The merge is the one to take
+// up again if a caller's fields are mostly constant (DESIGN_HISTORY.md 6g).
+constexpr int PD_MAX_BINS = 4096, PD_MAX_COUNTERS = 16384;          // 64 KiB of 32-bit counters: the LDS a workgroup gets without opting in
+constexpr int PD_MAX_TAILS = GFFT_PS_PDF_TAIL * ST_MAX_COMP;        // 12: the table is never allocated smaller than this
+static_assert(PD_MAX_BINS == SP_MAX_BINS && PD_MAX_COUNTERS * sizeof(uint32_t) == 2 * SP_MAX_BINS * sizeof(double), "the LDS of the shell kernels");
+
+struct pd_ranges { double lo[ST_MAX_COMP], w[ST_MAX_COMP]; };       // by value in the launch
+
+__device__ __forceinline__ int pd_bin(double x, double lo, double w, int nbins) {
+  const double t = (x - lo) * w;
+  return x != x ? nbins + 2 : t < 0.0 ? nbins : t >= (double)nbins ? nbins + 1 : (int)t;
+}
+
+// the words of LDS a table of ncounters takes
+__host__ __device__ constexpr int pd_words(int ncounters) { return ncounters > PD_MAX_TAILS ? ncounters : PD_MAX_TAILS; }
+
+// the table (ncounters words) to this workgroup's slab, then the NT tails of the lanes behind it
+template <int NT>
+__device__ __forceinline__ void pd_flush(uint32_t *__restrict__ tab, int ncounters, const uint32_t (&tail)[NT],
+                                         uint32_t *__restrict__ slabs) {
+  __syncthreads();
+  uint32_t *slab = slabs + (int64_t)blockIdx.x * (ncounters + NT);
+  for (int i = threadIdx.x; i < ncounters; i += PS_THREADS) slab[i] = tab[i];
+  __syncthreads();
+  if (threadIdx.x < NT) tab[threadIdx.x] = 0;          // (the table holds at least PD_MAX_TAILS words)
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+    if (tail[i]) atomicAdd(&tab[i], tail[i]);
+  __syncthreads();
+  if (threadIdx.x < NT) slab[ncounters + threadIdx.x] = tab[threadIdx.x];
+}
+
+// u = [NC][count] reals; table [NC][nbins], tails [NC][below, above, NaN]
+template <typename real, int V, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_histogram_kernel(const real *__restrict__ u, int64_t count, int64_t chunk, pd_ranges rg, int nbins, uint32_t *__restrict__ slabs) {
+  extern __shared__ uint32_t pd_table[];
+  const int ncounters = NC * nbins;
+  for (int i = threadIdx.x; i < pd_words(ncounters); i += PS_THREADS) pd_table[i] = 0;
+  __syncthreads();
+  uint32_t tail[GFFT_PS_PDF_TAIL * NC];
+#pragma unroll
+  for (int i = 0; i < GFFT_PS_PDF_TAIL * NC; ++i) tail[i] = 0;
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (count and chunk are multiples of V: a lane has all V points of a load or none)
+  for (int64_t e0 = begin + (int64_t)threadIdx.x * V; e0 < end; e0 += PS_THREADS * V) {
+    st_load<real, V> v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = *reinterpret_cast<const st_load<real, V> *>(u + c * count + e0);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const double x = v[c].m[j];                    // converted before any arithmetic
+        const int b = pd_bin(x, rg.lo[c], rg.w[c], nbins);
+        if (b < nbins) atomicAdd(&pd_table[c * nbins + b], 1u);
+        tail[3 * c + 0] += b == nbins;
+        tail[3 * c + 1] += b == nbins + 1;
+        tail[3 * c + 2] += b == nbins + 2;
+      }
+    }
+  }
+  pd_flush(pd_table, ncounters, tail, slabs);
+}
+
+// One quantity of one point, a[3 i + j] = A_ij: the expressions and associations of gs_point (include/gfft.h), every
+// operation rounded on its own -- contraction is off in this function, and stays off where it is inlined.
+__device__ __forceinline__ double gp_quantity(int q, const double (&a)[9]) {
+#pragma clang fp contract(off)
+  const double a00 = a[0], a01 = a[1], a02 = a[2], a10 = a[3], a11 = a[4], a12 = a[5], a20 = a[6], a21 = a[7], a22 = a[8];
+  switch (q) {
+    case GFFT_PS_Q_DIV:
+      return (a00 + a11) + a22;
+    case GFFT_PS_Q_WW: {
+      const double w0 = a21 - a12, w1 = a02 - a20, w2 = a10 - a01;
+      return (w0 * w0 + w1 * w1) + w2 * w2;
+    }
+    case GFFT_PS_Q_Q: {
+      const double div = (a00 + a11) + a22;
+      const double d2 = (a00 * a00 + a11 * a11) + a22 * a22;
+      return 0.5 * (div * div - (d2 + 2.0 * ((a01 * a10 + a02 * a20) + a12 * a21)));
+    }
+    case GFFT_PS_Q_R:
+      return -((a00 * (a11 * a22 - a12 * a21) - a01 * (a10 * a22 - a12 * a20)) + a02 * (a10 * a21 - a11 * a20));
+    default:
+      break;
+  }
+  const double s01 = 0.5 * (a01 + a10), s02 = 0.5 * (a02 + a20), s12 = 0.5 * (a12 + a21);
+  const double p01 = s01 * s01, p02 = s02 * s02, p12 = s12 * s12;
+  const double q00 = a00 * a00, q11 = a11 * a11, q22 = a22 * a22;
+  if (q == GFFT_PS_Q_SS) return ((q00 + q11) + q22) + 2.0 * ((p01 + p02) + p12);
+  if (q == GFFT_PS_Q_SSS) {
+    const double d3 = (a00 * q00 + a11 * q11) + a22 * q22;
+    return (d3 + 3.0 * ((a00 * (p01 + p02) + a11 * (p01 + p12)) + a22 * (p02 + p12))) + 6.0 * ((s01 * s02) * s12);
+  }
+  const double w0 = a21 - a12, w1 = a02 - a20, w2 = a10 - a01;          // GFFT_PS_Q_WSW
+  return ((a00 * (w0 * w0) + a11 * (w1 * w1)) + a22 * (w2 * w2)) + 2.0 * ((s01 * (w0 * w1) + s02 * (w0 * w2)) + s12 * (w1 * w2));
+}
+
+// A = [3][3][count] reals.  JOINT: table [nbx][nby], tails [outside, NaN] (NaN wins); else table [nbx], tails [below, above, NaN]
+struct gp_axis { int q; double lo, w; int nbins; };
+
+template <typename real, int V, bool JOINT>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_gradient_pdf_kernel(const real *__restrict__ A, int64_t count, int64_t chunk, gp_axis ax, gp_axis ay, uint32_t *__restrict__ slabs) {
+  extern __shared__ uint32_t pd_table[];
+  constexpr int NT = JOINT ? 2 : GFFT_PS_PDF_TAIL;
+  const int ncounters = JOINT ? ax.nbins * ay.nbins : ax.nbins;
+  for (int i = threadIdx.x; i < pd_words(ncounters); i += PS_THREADS) pd_table[i] = 0;
+  __syncthreads();
+  uint32_t tail[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) tail[i] = 0;
+  const int64_t begin = (int64_t)blockIdx.x * chunk;
+  const int64_t end = begin + chunk < count ? begin + chunk : count;
+  // (count and chunk are multiples of V: a lane has all V points of a load or none)
+  for (int64_t e0 = begin + (int64_t)threadIdx.x * V; e0 < end; e0 += PS_THREADS * V) {
+    st_load<real, V> v[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) v[c] = *reinterpret_cast<const st_load<real, V> *>(A + c * count + e0);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      double a[9];
+#pragma unroll
+      for (int c = 0; c < 9; ++c) a[c] = v[c].m[j];            // converted before any arithmetic
+      const int bx = pd_bin(gp_quantity(ax.q, a), ax.lo, ax.w, ax.nbins);
+      if constexpr (JOINT) {
+        const int by = pd_bin(gp_quantity(ay.q, a), ay.lo, ay.w, ay.nbins);
+        const bool nan = bx == ax.nbins + 2 || by == ay.nbins + 2;
+        const bool in = bx < ax.nbins && by < ay.nbins;
+        if (in) atomicAdd(&pd_table[bx * ay.nbins + by], 1u);
+        tail[0] += !in && !nan;
+        tail[1] += nan;
+      } else {
+        if (bx < ax.nbins) atomicAdd(&pd_table[bx], 1u);
+        tail[0] += bx == ax.nbins;
+        tail[1] += bx == ax.nbins + 1;
+        tail[2] += bx == ax.nbins + 2;
+      }
+    }
+  }
+  pd_flush(pd_table, ncounters, tail, slabs);
+}
+
+// The slabs [nwg][nrow * rowlen + nrow * ntail] added over the workgroups into out = int64 [nrow][rowlen + ntail], OVERWRITTEN
+// (nwg == 0, an empty block: zeros).  A workgroup owns 16 outputs; its sixteen rows of 16 lanes take every sixteenth slab each
+// (64 contiguous bytes per row and slab), sixteen loads in flight, and meet in LDS: 128 loads per lane in 8 rounds at 2048
+// slabs.  This kernel is latency, not bytes (6 MiB of slabs for a 3 x 256 table): with 32 outputs x 8 rows and eight loads in
+// flight (32 rounds) it cost 75 us at 256^3, as much as the counting itself -- measured, tools/pdf_probe.py, the difference
+// to gfft_ps_stats being the same 75 us in fp64 and fp32.  Integer sums: the order does not matter.
+constexpr int PD_SUM_OUT = 16, PD_SUM_ROWS = PS_THREADS / PD_SUM_OUT;
+__global__ void __launch_bounds__(PS_THREADS)
+pd_sum_kernel(const uint32_t *__restrict__ slabs, int nwg, int nrow, int rowlen, int ntail, int64_t *__restrict__ out) {
+  __shared__ unsigned long long part[PD_SUM_ROWS][PD_SUM_OUT];
+  const int n = nrow * (rowlen + ntail), table = nrow * rowlen;
+  const int o = threadIdx.x % PD_SUM_OUT, r = threadIdx.x / PD_SUM_OUT;
+  const int i = blockIdx.x * PD_SUM_OUT + o;
+  unsigned long long s = 0;
+  if (i < n) {
+#pragma unroll 16
+    for (int w = r; w < nwg; w += PD_SUM_ROWS) s += slabs[(int64_t)w * n + i];
+  }
+  part[r][o] = s;
+  __syncthreads();
+  if (r == 0 && i < n) {
+    for (int k = 1; k < PD_SUM_ROWS; ++k) s += part[k][o];
+    const int row = i < table ? i / rowlen : (i - table) / ntail;
+    const int col = i < table ? i - row * rowlen : rowlen + (i - table) - row * ntail;
+    out[(int64_t)row * (rowlen + ntail) + col] = (int64_t)s;
+  }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // f(real()) with the element type of `precision`: a launcher names its kernel and arguments once
 template <typename F>
@@ -1207,6 +1431,76 @@ hipError_t launch_ps_gradient_stats(const void *A, int64_t count, double *out, d
   });
   if (e != hipSuccess) return e;
   return ps_launch(gs_reduce_kernel, GS_NVAL, 0, s, slabs, g.nwg, out);
+}
+
+// ---- the PDFs: geometry, scratch and launchers ----
+// workgroups (= slabs) of a table of `ncounters` 32-bit words: SP_MAX_WG up to 4096 words, then in inverse proportion (512 at 16384)
+inline int pd_max_wg(int ncounters) { return ncounters <= 4096 ? SP_MAX_WG : (int)((int64_t)SP_MAX_WG * 4096 / ncounters); }
+
+// sp_geometry with that many workgroups at most
+sp_geom pd_geometry(int64_t count, int wide, bool aligned16, int max_wg) {
+  sp_geom g;
+  g.V = ps_lane_width(count, wide, aligned16);
+  const int64_t step = (int64_t)PS_THREADS * g.V;
+  g.chunk = (count + max_wg - 1) / max_wg;          // (count passed pd_chunk_fits: nothing overflows)
+  g.chunk = (g.chunk + step - 1) / step * step;
+  g.nwg = count ? (int)((count + g.chunk - 1) / g.chunk) : 0;
+  return g;
+}
+
+// a workgroup's 32-bit counters hold its chunk: whole steps of at most 1024 points
+inline bool pd_chunk_fits(int64_t count, int max_wg) { return count / max_wg + 1 + 1024 < ((int64_t)1 << 32); }
+
+inline size_t pd_scratch_bytes(int ncounters, int ntails) { return (size_t)pd_max_wg(ncounters) * (ncounters + ntails) * sizeof(uint32_t); }
+
+inline size_t pd_lds_bytes(int ncounters) { return (size_t)pd_words(ncounters) * sizeof(uint32_t); }
+
+template <typename real, int V>
+auto pd_hist_kernel(int ncomp) {
+  return ncomp == 1 ? ps_histogram_kernel<real, V, 1> : ncomp == 2 ? ps_histogram_kernel<real, V, 2>
+       : ncomp == 3 ? ps_histogram_kernel<real, V, 3> : ps_histogram_kernel<real, V, 4>;
+}
+
+// 1 <= ncomp <= ST_MAX_COMP, ncomp * nbins <= PD_MAX_COUNTERS; `slabs` = pd_scratch_bytes(ncomp nbins, 3 ncomp) of stream-ordered scratch
+hipError_t launch_ps_histogram(const void *u, int ncomp, int64_t count, const pd_ranges &rg, int nbins, int64_t *out,
+                               uint32_t *slabs, int precision, hipStream_t s) {
+  const int ncounters = ncomp * nbins;
+  const sp_geom g = pd_geometry(count, 16 / precision, (uintptr_t)u % 16 == 0, pd_max_wg(ncounters));
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    return ps_launch(g.V == W ? pd_hist_kernel<real, W>(ncomp) : pd_hist_kernel<real, 1>(ncomp), g.nwg, pd_lds_bytes(ncounters), s,
+                     u, count, g.chunk, rg, nbins, slabs);
+  });
+  if (e != hipSuccess) return e;
+  const int n = ncomp * (nbins + GFFT_PS_PDF_TAIL);
+  return ps_launch(pd_sum_kernel, (n + PD_SUM_OUT - 1) / PD_SUM_OUT, 0, s, slabs, g.nwg, ncomp, nbins, (int)GFFT_PS_PDF_TAIL, out);
+}
+
+// ay.q == GFFT_PS_Q_NONE: the 1-D table of ax; `slabs` = pd_scratch_bytes(counters, 3 or 2)
+hipError_t launch_ps_gradient_pdf(const void *A, int64_t count, const gp_axis &ax, const gp_axis &ay, int64_t *out,
+                                  uint32_t *slabs, int precision, hipStream_t s) {
+  const bool joint = ay.q != GFFT_PS_Q_NONE;
+  const int ncounters = joint ? ax.nbins * ay.nbins : ax.nbins, ntail = joint ? 2 : (int)GFFT_PS_PDF_TAIL;
+  const sp_geom g = pd_geometry(count, 16 / precision, (uintptr_t)A % 16 == 0, pd_max_wg(ncounters));
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    auto go = [&](auto kern) { return ps_launch(kern, g.nwg, pd_lds_bytes(ncounters), s, A, count, g.chunk, ax, ay, slabs); };
+    if (joint) return g.V == W ? go(ps_gradient_pdf_kernel<real, W, true>) : go(ps_gradient_pdf_kernel<real, 1, true>);
+    return g.V == W ? go(ps_gradient_pdf_kernel<real, W, false>) : go(ps_gradient_pdf_kernel<real, 1, false>);
+  });
+  if (e != hipSuccess) return e;
+  return ps_launch(pd_sum_kernel, (ncounters + ntail + PD_SUM_OUT - 1) / PD_SUM_OUT, 0, s, slabs, g.nwg, 1, ncounters, ntail, out);
+}
+
+// lo < hi, both finite, hi - lo finite; w = nbins / (hi - lo), formed here once, finite
+inline bool pd_range(double lo, double hi, int nbins, double &w) {
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return false;
+  const double span = hi - lo;
+  if (!std::isfinite(span)) return false;
+  w = (double)nbins / span;
+  return std::isfinite(w);
 }
 
 // gfft_ps_spectrum and gfft_ps_cospectrum behind their own argument checks (`bad`); fn names the caller in the messages.
@@ -1482,6 +1776,58 @@ int gfft_ps_gradient_stats(const void *d_A, int64_t count, double *d_out, int pr
   rc = scratch_get((hipStream_t)stream, ST_SCRATCH_BYTES, &slabs);
   if (rc) return rc;
   HIP_TRY(launch_ps_gradient_stats(d_A, count, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_histogram(const void *d_u, int ncomp, int64_t count, const double *lo, const double *hi, int nbins, int64_t *d_out,
+                      int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_u || !lo || !hi || !d_out || ncomp < 1 || count < 0 || nbins < 1 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_histogram: bad argument");
+  static_assert(ST_MAX_COMP == 4 && PD_MAX_BINS == 4096, "the messages name the limits");
+  if (ncomp > ST_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_histogram: more than 4 components");
+  pd_ranges rg = {};
+  for (int c = 0; c < ncomp; ++c) {
+    rg.lo[c] = lo[c];
+    if (!pd_range(lo[c], hi[c], nbins, rg.w[c])) return fail(GFFT_ERR_INVALID, "gfft_ps_histogram: a range must be finite with lo < hi");
+  }
+  if (nbins > PD_MAX_BINS) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_histogram: more than 4096 bins");
+  const int ncounters = ncomp * nbins, ntails = GFFT_PS_PDF_TAIL * ncomp;
+  if (!pd_chunk_fits(count, pd_max_wg(ncounters))) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_histogram: more than 2^32 points per workgroup");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' tables live in the stream's shared scratch: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, pd_scratch_bytes(ncounters, ntails), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_histogram(d_u, ncomp, count, rg, nbins, d_out, static_cast<uint32_t *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_gradient_pdf(const void *d_A, int64_t count, int qx, double xlo, double xhi, int nbx, int qy, double ylo, double yhi,
+                         int nby, int64_t *d_out, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  const bool joint = qy != GFFT_PS_Q_NONE;
+  if (!d_A || !d_out || count < 0 || nbx < 1 || nby < 1 || qx < 0 || qx >= GFFT_PS_Q_COUNT || qy < GFFT_PS_Q_NONE ||
+      qy >= GFFT_PS_Q_COUNT || (!joint && nby != 1) || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_gradient_pdf: bad argument");
+  gp_axis ax = {qx, xlo, 0.0, nbx}, ay = {qy, 0.0, 1.0, 1};
+  if (!pd_range(xlo, xhi, nbx, ax.w)) return fail(GFFT_ERR_INVALID, "gfft_ps_gradient_pdf: a range must be finite with lo < hi");
+  if (joint) {
+    ay = {qy, ylo, 0.0, nby};
+    if (!pd_range(ylo, yhi, nby, ay.w)) return fail(GFFT_ERR_INVALID, "gfft_ps_gradient_pdf: a range must be finite with lo < hi");
+  }
+  static_assert(PD_MAX_BINS == 4096 && PD_MAX_COUNTERS == 16384, "the messages name the limits");
+  if (!joint && nbx > PD_MAX_BINS) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_gradient_pdf: more than 4096 bins");
+  if (joint && (int64_t)nbx * nby > PD_MAX_COUNTERS) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_gradient_pdf: more than 16384 joint bins");
+  const int ncounters = joint ? nbx * nby : nbx, ntails = joint ? 2 : (int)GFFT_PS_PDF_TAIL;
+  if (!pd_chunk_fits(count, pd_max_wg(ncounters))) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_gradient_pdf: more than 2^32 points per workgroup");
+  int rc = check_device();
+  if (rc) return rc;
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, pd_scratch_bytes(ncounters, ntails), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_gradient_pdf(d_A, count, ax, ay, d_out, static_cast<uint32_t *>(slabs), precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

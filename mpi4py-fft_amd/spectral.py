@@ -83,10 +83,19 @@ tensor A_ij = d u_i / d x_j: the spectral gradient in one pass, nine backward tr
                                 the intermittency of dissipation and enstrophy, and the Betchov ratio <w S w> / (-4/3 <S S S>),
                                 which is 1 for a solenoidal field that is resolved and alias-free
 
+and the distributions those moments compress -- integer counts from one read, exact and additive over ranks:
+
+    histogram(u, range, nbins)  per component of a real field the `nbins` bins of [lo, hi) and the counts below, above and NaN
+    gradient_pdf(A, x, y, range, bins)   the histogram of one of ss, ww, div, Q, R, sss, wsw, or the joint histogram of two of
+                                them -- gradient_pdf(A, 'R', 'Q', ...) is the teardrop --, the quantities formed per point
+                                without fused multiply-adds so that the counts equal a numpy restatement exactly
+    pdf(counts, range), joint_pdf(counts, ranges, bins)   bin centres, the density and the shares outside the range
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
 import collections
+import math
 
 import numpy as np
 import torch
@@ -150,6 +159,29 @@ def _operands(kinds, *fields):
     assert all(t.dtype == dtype for t in given), 'the operands differ in dtype: %s' % [t.dtype for t in given]
     assert all(t.is_contiguous() for t in given), 'an operand is not contiguous'
     return ts, (8 if dtype in (torch.float64, torch.complex128) else 4)
+
+
+QUANTITIES = {'ss': _lib.PS_Q_SS, 'ww': _lib.PS_Q_WW, 'div': _lib.PS_Q_DIV, 'Q': _lib.PS_Q_Q, 'R': _lib.PS_Q_R,
+              'sss': _lib.PS_Q_SSS, 'wsw': _lib.PS_Q_WSW}          # the x / y of SpectralOps.gradient_pdf
+
+
+def _ranges(rng, m):
+    """m (lo, hi) pairs of floats from one pair or m of them; what gfft_ps_histogram refuses is refused here
+    (plain Python floats: these run between a caller's launches)"""
+    rng = tuple(rng)
+    if len(rng) == 2 and np.ndim(rng[0]) == 0 and np.ndim(rng[1]) == 0:
+        rng = (rng,) * m
+    assert len(rng) == m and all(np.ndim(r) == 1 and len(r) == 2 for r in rng), 'range = (lo, hi) or %d such pairs' % m
+    out = [(float(lo), float(hi)) for lo, hi in rng]
+    assert all(math.isfinite(lo) and math.isfinite(hi) and lo < hi and math.isfinite(hi - lo) for lo, hi in out), 'a range must be finite with lo < hi'
+    return out
+
+
+def _nbins(n, most, *ranges):
+    """a bin count 1 ... most whose width w = n / (hi - lo) is finite on every range given"""
+    assert isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= n <= most, 'bins = 1 ... %d' % most
+    assert all(math.isfinite(float(n) / (hi - lo)) for lo, hi in ranges), 'bins / (hi - lo) overflows'
+    return int(n)
 
 
 class SpectralOps:
@@ -245,6 +277,81 @@ class SpectralOps:
             for p in parts[1:]:
                 vals = np.where(is_max, np.maximum(vals, p), vals + p)
         return vals
+
+    def histogram(self, u, range, nbins, out=None, reduce=True):
+        """Histograms of a real physical-space field in one read: int64 [m][nbins + 3] ([nbins + 3] for a scalar field) --
+        per component the `nbins` bins of [lo, hi), then the counts below, above (hi itself included: the upper edge is
+        exclusive) and NaN; every component adds up to the number of points.  u as for `stats`: [m] + fft.shape(False), m <= 4,
+        or a scalar field of that shape; `range` is one (lo, hi) for all components or m pairs; nbins <= 4096.
+        The bin rule (include/gfft.h), in double: t = (x - lo) * w with w = nbins / (hi - lo); bin int(t) for 0 <= t < nbins.
+        Counts are exact: independent of order, the same from call to call and on any split over ranks.
+
+        `reduce` and `out` as in `stats`: reduce=True adds the counts over the ranks of the grid on the host, one grid axis
+        after the other (exact; every rank holds the same array), which synchronises; reduce=False only enqueues and returns
+        the device tensor (`out`, a contiguous int64 tensor of the shape above, or a new one), so it can be captured after one
+        call outside the capture.  `pdf(counts, range)` turns a row into a density.
+        Pooled PDFs need no kernel of their own: the longitudinal-derivative PDF is histogram(A[i][i]) for i = 0, 1, 2 added,
+        the transverse one the six off-diagonal slices added (A[i] is a [3] + shape field: one call per row, three ranges
+        alike)."""
+        t, ncomp, precision = self._real_field(u)
+        assert ncomp <= 4, 'at most 4 components per call'
+        ranges = _ranges(range, ncomp)
+        nbins = _nbins(nbins, _lib.PS_PDF_MAX_BINS, *ranges)
+        shape = (nbins + _lib.PS_PDF_TAIL,) if t.dim() == 3 else (ncomp, nbins + _lib.PS_PDF_TAIL)
+        out = self._counts_out(out, shape, t.device)
+        count = int(np.prod(self.pshape, dtype=np.int64))
+        _lib.engine().ps_histogram(t, ncomp, count, [r[0] for r in ranges], [r[1] for r in ranges], nbins, out, precision)
+        return self._reduce_counts(out) if reduce else out
+
+    def gradient_pdf(self, A, x, y=None, range=None, bins=None, out=None, reduce=True):
+        """The histogram of one, or the joint histogram of two, of the per-point quantities of `gradient_stats` in one read of
+        A ([3][3] + fft.shape(False), as for `gradient_stats`): x and y among 'ss', 'ww', 'div', 'Q', 'R', 'sss', 'wsw'
+        (S_ij S_ij, |w|^2, tr A, the invariants Q and R, S_ij S_jk S_ki, w_i S_ij w_j), evaluated in double with every
+        operation rounded on its own (no fused multiply-add), so the counts equal a numpy restatement exactly.
+        y=None: `range` = (lo, hi), `bins` an int <= 4096; int64 [bins + 3] laid out as one row of `histogram`.
+        Otherwise `range` = ((xlo, xhi), (ylo, yhi)), `bins` an int (both axes) or a pair with nbx * nby <= 16384; int64
+        [nbx * nby + 2]: bin bx * nby + by, then the points outside (either coordinate below or above its range), then those
+        where either quantity is NaN (which wins over outside); `joint_pdf` reshapes and normalises it.  The bin rule, `reduce`
+        and `out` are those of `histogram`.  gradient_pdf(A, 'R', 'Q', ...) is the teardrop."""
+        t = _t(A)
+        assert tuple(t.shape) == (3, 3) + self.pshape, (tuple(t.shape), self.pshape)
+        assert t.is_contiguous() and t.dtype in (torch.float32, torch.float64), 'gradient_pdf needs a contiguous real tensor'
+        precision = 8 if t.dtype == torch.float64 else 4
+        self._same_precision(precision)
+        assert x in QUANTITIES and (y is None or y in QUANTITIES), (x, y)
+        assert range is not None and bins is not None, 'gradient_pdf needs range= and bins='
+        if y is None:
+            (xr,) = _ranges(range, 1)
+            nbx, nby, qy, yr = _nbins(bins, _lib.PS_PDF_MAX_BINS, xr), 1, _lib.PS_Q_NONE, (0.0, 1.0)
+            shape = (nbx + _lib.PS_PDF_TAIL,)
+        else:
+            assert len(range) == 2 and all(np.ndim(r) == 1 for r in range), 'range = ((xlo, xhi), (ylo, yhi))'
+            xr, yr = _ranges(range, 2)
+            assert np.ndim(bins) == 0 or len(bins) == 2, 'bins = an int or (nbx, nby)'
+            bx, by = (bins, bins) if np.ndim(bins) == 0 else bins
+            nbx, nby = _nbins(bx, _lib.PS_PDF_MAX_JOINT, xr), _nbins(by, _lib.PS_PDF_MAX_JOINT, yr)
+            assert nbx * nby <= _lib.PS_PDF_MAX_JOINT, 'at most 16384 joint bins'
+            qy = QUANTITIES[y]
+            shape = (nbx * nby + 2,)
+        out = self._counts_out(out, shape, t.device)
+        count = int(np.prod(self.pshape, dtype=np.int64))
+        _lib.engine().ps_gradient_pdf(t, count, QUANTITIES[x], xr, nbx, qy, yr, nby, out, precision)
+        return self._reduce_counts(out) if reduce else out
+
+    @staticmethod
+    def _counts_out(out, shape, device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int64, device=device)
+        assert tuple(out.shape) == tuple(shape) and out.dtype == torch.int64 and out.is_contiguous(), (tuple(out.shape), shape)
+        return out
+
+    def _reduce_counts(self, out):
+        """This rank's counts added over the ranks of the grid, on the host: exact, the same array on every rank"""
+        counts = out.cpu().numpy()                     # (waits for the kernels)
+        _lib.check_async()
+        for c in self.comms:                           # one grid axis after the other
+            counts = np.sum(c.allgather_obj(counts), axis=0, dtype=np.int64)
+        return counts
 
     def dealias_mask(self, rule='2/3', kcut=None):
         """The kept set of `project(..., dealias=)` and `dealias` as a `DealiasMask` (m0, m1, m2, kcut): a mode is kept iff
@@ -701,6 +808,43 @@ def gradient_moments(gs, npoints, nu=None):
             dissipation_flatness=float((s[_lib.GS_SS2] / n) / (ss * ss)), enstrophy_flatness=float((s[_lib.GS_WW2] / n) / (ww * ww)),
             strain_enstrophy_correlation=float((s[_lib.GS_SSWW] / n) / (ss * ww)),
             betchov=float(np.float64(s[_lib.GS_WSW]) / (-4.0 / 3.0 * s[_lib.GS_SSS])), div_rms=float(np.sqrt(s[_lib.GS_DIV2] / n)))
+
+
+Pdf = collections.namedtuple('Pdf', 'centres density below above nan')
+Pdf.__doc__ = """What `pdf` returns: the bin centres, the density counts / (n width) with n the number of non-NaN points, tails
+included -- so the density integrates to the share of them that lies in the range --, and the counts below, above and NaN."""
+JointPdf = collections.namedtuple('JointPdf', 'xcentres ycentres density outside nan')
+JointPdf.__doc__ = """What `joint_pdf` returns: the bin centres of both axes, the density [nbx][nby] = counts / (n wx wy) with n the
+number of non-NaN points, those outside included, and the counts outside and NaN."""
+
+
+def pdf(counts, range):
+    """A density from one row of `SpectralOps.histogram` or a 1-D `SpectralOps.gradient_pdf` (rank-reduced: int64 [nbins + 3])
+    and its (lo, hi), as a `Pdf`.  Rows may be added first (a pooled PDF).  Host numpy; a row without a non-NaN point gives
+    nan densities."""
+    c = np.asarray(counts)
+    assert c.ndim == 1 and len(c) > _lib.PS_PDF_TAIL and c.dtype.kind in 'iu', (c.shape, c.dtype)
+    nbins = len(c) - _lib.PS_PDF_TAIL
+    lo, hi = float(range[0]), float(range[1])
+    width = (hi - lo) / nbins
+    n = float(c[:nbins + 2].sum())
+    with np.errstate(divide='ignore', invalid='ignore'):
+        density = c[:nbins] / (n * width)
+    return Pdf(lo + (np.arange(nbins) + 0.5) * width, density, int(c[nbins]), int(c[nbins + 1]), int(c[nbins + 2]))
+
+
+def joint_pdf(counts, ranges, bins):
+    """A 2-D density from a joint `SpectralOps.gradient_pdf` (rank-reduced: int64 [nbx * nby + 2]), its ((xlo, xhi), (ylo, yhi))
+    and its bins (an int or a pair), as a `JointPdf`.  Host numpy."""
+    nbx, nby = (int(bins), int(bins)) if np.ndim(bins) == 0 else (int(bins[0]), int(bins[1]))
+    c = np.asarray(counts)
+    assert c.shape == (nbx * nby + 2,) and c.dtype.kind in 'iu', (c.shape, c.dtype, nbx, nby)
+    (xlo, xhi), (ylo, yhi) = ((float(a), float(b)) for a, b in ranges)
+    wx, wy = (xhi - xlo) / nbx, (yhi - ylo) / nby
+    n = float(c[:nbx * nby + 1].sum())
+    with np.errstate(divide='ignore', invalid='ignore'):
+        density = c[:nbx * nby].reshape(nbx, nby) / (n * wx * wy)
+    return JointPdf(xlo + (np.arange(nbx) + 0.5) * wx, ylo + (np.arange(nby) + 0.5) * wy, density, int(c[nbx * nby]), int(c[nbx * nby + 1]))
 
 
 def flux(T):
