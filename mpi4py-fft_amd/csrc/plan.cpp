@@ -1,5 +1,6 @@
-// libgfft.so: C ABI (include/gfft.h) + the planner.  (The pseudo-spectral entry points live next to their kernels in spectral.hip
-// and report errors, find the device and get scratch through the four functions gfft_internal.h declares from here.)
+// libgfft.so: the planner.  (The C ABI of include/gfft.h is api.cpp; what the two share is plan_internal.h.  The error state of
+// the calling thread lives here, with gfft_last_error() beside it: api.cpp and the pseudo-spectral entry points in spectral.hip
+// report errors, find the device and get scratch through the four functions gfft_internal.h declares from here.)
 //
 // The planner is the device-side counterpart of fftw_planxfftn() (mpi4py_fft/fftw/
 // fftw_planxfftn.c:10-77): it turns (sizes, axes, kind) into one strided+batched 1-D pass per
@@ -11,20 +12,12 @@
 //   * longer composite n                 -> four-step: two strided passes + fused twiddle
 //   * anything else (large prime factors, long real transforms) -> Bluestein / complex embedding
 //   * 3-D all-axes plans on one rank     -> plan_fused3: pass order + padded-pitch workspace
-#include "../../include/gfft.h"
-#include "gfft_internal.h"
+#include "plan_internal.h"
 
-#include <atomic>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
-#include <tuple>
-#include <mutex>
 #include <string>
-#include <thread>
-#include <vector>
 
 using namespace gfft;
 
@@ -35,7 +28,9 @@ bool g_device_checked = false;
 
 }  // namespace
 
-// what the pseudo-spectral entry points in spectral.hip share with the ones here (declared in gfft_internal.h)
+extern "C" const char *gfft_last_error(void) { return g_last_error.c_str(); }
+
+// what the entry points in api.cpp and spectral.hip share (declared in gfft_internal.h)
 namespace gfft {
 
 int fail(int code, const std::string &msg) {
@@ -60,57 +55,7 @@ int check_device() {
   return GFFT_OK;
 }
 
-}  // namespace gfft
-
-namespace {
-
-// ---- tunables ---------------------------------------------------------------------------
-struct Options {
-  int grid_cap = 0;          // workgroups per launch at most; 0 = 4096, and 16384 for the passes of complex 3-D schedules
-  int variant_rows = 0;
-  int variant_cols = 0;
-  int force_generic = 0;
-  int xcd_swizzle = -1;      // XCD-contiguous tile order in the pow2 kernels: 0 off, 1 on, -1 auto
-  int tile_order = -1;       // order in time of tiles and rows inside an XCD-contiguous walk (PassDesc::order): -1 = each plan's own, >= 0: this one (0 = plain); read at launch time (A/B on one plan)
-  int profile = 0;           // record HIP events around every pass (bench.py roofline leg)
-  int fused3 = 1;            // reorder + padded-pitch workspace for 3-D all-axes plans
-  int debug_flat = 0;        // gfft_debug_pass: tiles over the flattened (mid, inner) index
-  int flat_out = 1;          // forward r2c 3-D plans: far-axis last pass with flattened tiles
-  int mixv_variant = 0;      // A/B: alternative kernels of the unequal-width lengths (tools/gen_mixv_tables.py)
-  int mixv = 1;              // one-pass kernels for 3 x 5 x 2^k lengths (fft_mixv_*.hip); 0: the two-pass plans of rounds 1-4 (A/B)
-  int wtile = 1;             // tile-major workspace under the complex 3-D pair schedule (plan_fused3; A/B)
-  int plane2d = 1;           // planes of 32^2 / 64^2 points: both passes in one launch, the plane in LDS (fft_plane2d.hip; 0: two passes, A/B)
-  int fuse2 = 1;             // pass pairs in one persistent launch, handed over through the Infinity Cache (fft_fused_f64.hip)
-  int fuse2_ring = 0, fuse2_lag = 0;   // slots of the hand-off ring / planes the producer runs ahead; 0 = auto (fused2_ring)
-  int fuse2_kinds = 2046;    // which pairs (bit = FusedKind): measured per kind, see fused2_pair (bits 1-10; 0, [rows -> strided] of the 3-D schedule, off)
-  int fuse2_f32 = 1;         // 1: complex64 pairs (fft_fused_f32.hip); 2: the real fp32 pairs too (fft_fused_real_f32.hip: measured level, off)
-  int fuse2_wait_ms = 2000;  // wall-clock limit of one wait inside a fused launch before the launch is voided (0: at once -- test hook)
-  int debug_tile_lg = 0, debug_tile_side = 0, debug_tile_stride = 0;   // gfft_debug_pass: tile-major lines (rows passes)
-  int64_t fused3_min_bytes = 32 << 20;
-  // TEST HOOK (tests/test_gpu_rounding_guard.py): twiddle tables uploaded while debug_tw_exp > 0 carry ONE wrong entry --
-  // the real part of entry debug_tw_index (mod n) is off by 10^-debug_tw_exp -- under their own cache key, so that plans made
-  // before / after are untouched.  What the rounding-level guards of the test suite must catch; never set by the product.
-  // debug_tw_len != 0: only the table of exactly that length (a packed-real plan's rtw(n), say, and not its tw(n/2)).
-  int debug_tw_index = 1, debug_tw_exp = 0, debug_tw_len = 0;
-  // TEST HOOK (tests/test_gpu_r2r_guard.py): the same for the pre / post tables of the real-to-real kinds (get_r2r_tables) --
-  // tables uploaded while debug_r2r_exp > 0 carry ONE wrong entry: the real part of entry debug_r2r_index (mod n) of `pre`
-  // (debug_r2r_post = 0) or `post` (1) is off by 10^-debug_r2r_exp -- under their own cache key, so that plans made
-  // before / after are untouched.  What the rounding-level guards of the test suite must catch; never set by the product.
-  int debug_r2r_index = 1, debug_r2r_exp = 0, debug_r2r_post = 0;
-  Options() {
-    if (const char *s = getenv("GFFT_GRID_CAP")) grid_cap = atoi(s);
-    if (const char *s = getenv("GFFT_VARIANT_ROWS")) variant_rows = atoi(s);
-    if (const char *s = getenv("GFFT_VARIANT_COLS")) variant_cols = atoi(s);
-    if (const char *s = getenv("GFFT_FORCE_GENERIC")) force_generic = atoi(s);
-    if (const char *s = getenv("GFFT_FUSED3")) fused3 = atoi(s);
-    if (const char *s = getenv("GFFT_XCD_SWIZZLE")) xcd_swizzle = atoi(s);
-    if (const char *s = getenv("GFFT_FUSE2")) fuse2 = atoi(s);
-    if (const char *s = getenv("GFFT_FUSE2_RING")) fuse2_ring = atoi(s);
-    if (const char *s = getenv("GFFT_FUSE2_LAG")) fuse2_lag = atoi(s);
-    if (const char *s = getenv("GFFT_FUSE2_KINDS")) fuse2_kinds = atoi(s);
-    if (const char *s = getenv("GFFT_FUSE2_WAIT_MS")) fuse2_wait_ms = atoi(s);
-  }
-};
+// ---- the planner: what plan_internal.h declares is called from api.cpp, the rest stays in this file -----------------
 Options &opts() {
   static Options o;
   return o;
@@ -118,10 +63,10 @@ Options &opts() {
 
 // ---- twiddle tables (device resident, shared by plans) ------------------------------------
 // (per device: the key's precision slot also carries the ordinal of the device the table lives on)
+namespace {
 int dev_prec(int precision) { return precision + (current_device() << 8); }
 std::mutex g_tw_mutex;
 std::map<std::tuple<int64_t, int, int>, void *> g_tw_cache;       // (n, precision + device, test-hook signature) -> W_n^k, k<n
-struct BigTw { void *hi, *lo; int L; };
 std::map<std::pair<int64_t, int>, BigTw> g_bigtw_cache;     // (big_n, precision)
 
 // exp(-2 pi i k / n) for k in [k0, k0 + count*step) step `step`, in long double, stored as `precision`
@@ -158,6 +103,7 @@ int upload_twiddles(int64_t n, int64_t step, int64_t count, int precision, void 
   *out = d;
   return GFFT_OK;
 }
+}  // namespace
 
 int get_twiddles(int64_t n, int precision, const void **out) {
   std::lock_guard<std::mutex> lock(g_tw_mutex);
@@ -175,7 +121,7 @@ int get_twiddles(int64_t n, int precision, const void **out) {
   return GFFT_OK;
 }
 
-int get_bigtw(int64_t big_n, int precision, BigTw *out) {
+static int get_bigtw(int64_t big_n, int precision, BigTw *out) {
   std::lock_guard<std::mutex> lock(g_tw_mutex);
   auto key = std::make_pair(big_n, dev_prec(precision));
   auto it = g_bigtw_cache.find(key);
@@ -195,63 +141,11 @@ int get_bigtw(int64_t big_n, int precision, BigTw *out) {
   return GFFT_OK;
 }
 
-// ---- plan -------------------------------------------------------------------------------
-// Buffers a pass may read/write.  IN/OUT are the caller's arrays; the other three are regions of
-// one plan-owned scratch allocation (made at the first execute):
-//   WS   an array-sized workspace: the padded-pitch W of the 3-D schedule, or the complex staging
-//        of a multi-axis c2r (so the caller's input is never written)
-//   FS   the transposed intermediate of a four-step axis
-//   AUX  the embedding buffer of a Bluestein / real-as-complex axis
-//   RING the hand-off ring (+ its counters) of a fused pass pair (PK_FUSED2)
-//   FS2  the intermediate of the outer level of a three-pass axis (lengths beyond 2^24, plan_long)
-enum Buf { BUF_IN = 0, BUF_OUT = 1, BUF_WS = 2, BUF_FS = 3, BUF_AUX = 4, BUF_RING = 5, BUF_FS2 = 6, BUF_COUNT = 7 };
-
-enum PassKind { PK_FFT = 0, PK_EMBED, PK_MULB, PK_EXTRACT, PK_FUSED2, PK_PLANE2D };    // PK_PLANE2D: both passes of small planes on chip (fft_plane2d.hip)
-
-struct Pass {
-  PassKind kind = PK_FFT;
-  PassDesc d{};
-  Factors f{};
-  bool regk = false, cols = false;   // register-resident kernel family (else fft_generic); mapping
-  int src = BUF_IN, dst = BUF_OUT;
-  bool carries_scale = false;        // the plan's scale factor is applied by this pass
-  bool logical_first = false;        // first kernel of a transformed axis (profiling/report)
-  PointDesc pt{};                    // PK_EMBED / PK_MULB / PK_EXTRACT geometry
-  double extra_scale = 1.0;          // e.g. 1/M of Bluestein's inverse
-  // packed-real passes keep the full-length form of the same line (MODE_R2C / MODE_C2R with the
-  // zero-imaginary / mirror adapters) for what only that form can fuse: truncation / padding
-  bool has_full = false;
-  PassDesc full{};
-  int64_t data_inner = 0;            // columns of d.inner that carry data (0 = all): byte accounting
-  // guru plans: blocks of the transformed axis per side and the distance between their starts
-  // (gfft_plan_set_tiles re-derives the block jumps from them)
-  int blocks[2] = {1, 1};
-  int64_t bstride[2] = {0, 0};
-  // PK_FUSED2: `d` = pass A on ONE plane, `d2` = pass B on one plane, `fused` = the planes (fft_pow2_impl.h
-  // fft_fused2_kernel); fused.ctr and the ring's address are filled in at execution
-  PassDesc d2{};
-  FusedDesc fused{};
-  int fused_kind = 0;
-  const FusedPair *pair = nullptr;   // the kernel pair, resolved when the plan was made (fused2_pair)
-  PassDesc *dev_descs = nullptr;     // {d, d2} in device memory (owned by the plan: gfft_plan_s::device_allocs)
-  // the same two passes as stand-alone launches (gfft_plan_s::alt[alt_first], [alt_first + 1]): what the plan runs
-  // once a fused launch has given up a wait; alt_buf / alt_bytes = the scratch region only that form needs
-  int alt_first = -1;
-  int alt_buf = -1;
-  size_t alt_bytes = 0;
-  double bytes2 = 0;                 // algorithmic bytes of pass B (gfft_plan_pass_info reports A + B)
-};
-
-// Turn two consecutive passes A -> B into one fused launch when a kernel pair exists: dA / dB are the passes
-// cut down to one plane, the plane strides say where plane p starts on A's input and B's output side.
-bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const PassDesc &dA, const PassDesc &dB, int planes,
-                 int64_t a_in_plane, int64_t b_out_plane, int64_t slot_bytes, Pass *out);
-
 bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
 
 /* threads per line (NT = n / R) of the power-of-two ROW kernels, as the tables in fft_pow2_f64.hip /
  * fft_pow2_f32.hip instantiate them (default variants); launch_pow2_one re-checks at launch */
-static int pow2_rows_nt(int64_t n, int precision) {
+int pow2_rows_nt(int64_t n, int precision) {
   if (!is_pow2(n) || n < 16 || n > 4096) return 0;
   if (n <= 32) return 4;
   if (n == 64) return 8;
@@ -294,7 +188,7 @@ bool fused_pad_ok(int64_t n_axis) {
 #endif
 }
 
-bool factorize(int64_t n, Factors *f, int max_prime) {
+static bool factorize(int64_t n, Factors *f, int max_prime) {
   f->count = 0;
   auto push = [&](int r) { if (f->count < 24) f->r[f->count++] = r; };
   while (n % 4 == 0) { push(4); n /= 4; }
@@ -315,88 +209,6 @@ constexpr int GENERIC_MAX_PRIME = 61;
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// ---- scratch shared by all plans ---------------------------------------------------------------
-// One buffer per (device, host thread, stream) -- torch's default stream is handle 0 on EVERY device --, grown to the
-// largest request seen there: the passes of one
-// gfft_execute are enqueued back to back by one thread and a stream runs them in order, so every
-// plan that thread executes on that stream can share the buffer (the forward and the backward plan
-// of a 1024^3 PFFT each need a 16 GiB padded workspace; owning one each doubled that).  Other
-// threads -- whose launches could interleave with this one's on the same stream -- and other
-// streams get their own.  Growing synchronises the stream once (earlier launches may still be
-// using the old buffer).
-struct ScratchPool {
-  struct Slot { void *p = nullptr; size_t n = 0; bool pinned = false; };
-  struct Key {
-    int dev; std::thread::id th; hipStream_t st;
-    bool operator<(const Key &o) const { return std::tie(dev, th, st) < std::tie(o.dev, o.th, o.st); }
-  };
-  std::mutex m;
-  std::map<Key, Slot> bufs;
-  std::vector<void *> retired;      // buffers a captured graph may still use, replaced by larger ones
-  int get(hipStream_t s, size_t bytes, void **out) {
-    std::lock_guard<std::mutex> lock(m);
-    const auto me = std::this_thread::get_id();
-    const int dev = current_device();
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
-    if (cap != hipStreamCaptureStatusNone) {
-      // No allocation inside a capture: the graph uses the buffer this thread's warm-up execution
-      // grew (on whatever stream that ran), so replays must not overlap other executions of this
-      // thread -- the stream a graph is replayed on orders them.  The buffer's address is now baked
-      // into the graph: it is PINNED -- never freed by growth or by the last plan going away, only
-      // by an explicit gfft_scratch_release().
-      for (auto &kv : bufs)
-        if (kv.first.dev == dev && kv.first.th == me && kv.second.n >= bytes) { kv.second.pinned = true; *out = kv.second.p; return GFFT_OK; }
-      return fail(GFFT_ERR_INVALID, "stream capture: execute the plan once before capturing it (its workspace is allocated at the first execution)");
-    }
-    Slot &b = bufs[Key{dev, me, s}];
-    if (bytes > b.n) {
-      if (b.p && b.pinned) {
-        retired.push_back(b.p);      // a captured graph holds this address: keep it alive
-      } else if (b.p) {
-        HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipFree(b.p));
-      }
-      b = Slot{};
-      void *p = nullptr;
-      hipError_t e = hipMalloc(&p, bytes);
-      if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(GFFT_ERR_NOMEM, "scratch allocation failed"); }
-      HIP_TRY(e);
-      b.p = p;
-      b.n = bytes;
-    }
-    *out = b.p;
-    return GFFT_OK;
-  }
-  // everything == false: the last plan of the process went away -- buffers no graph refers to are
-  // freed; true: gfft_scratch_release(), the caller vouches that no captured graph will be replayed
-  int release(bool everything) {
-    std::lock_guard<std::mutex> lock(m);
-    // (one device-wide synchronisation per device that holds a buffer: the stream handles in the keys may have been
-    // destroyed since)
-    const int here = current_device();
-    int synced = -1;
-    for (auto it = bufs.begin(); it != bufs.end();) {
-      if (it->second.p && (everything || !it->second.pinned)) {
-        if (it->first.dev != synced) {          // (keys are ordered by device)
-          if (hipSetDevice(it->first.dev) != hipSuccess || hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-          synced = it->first.dev;
-        }
-        (void)hipFree(it->second.p);
-        it = bufs.erase(it);
-      } else {
-        ++it;
-      }
-    }
-    if (synced >= 0 && synced != here && hipSetDevice(here) != hipSuccess) (void)hipGetLastError();
-    if (everything) {
-      if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-      for (void *p : retired) (void)hipFree(p);
-      retired.clear();
-    }
-    return GFFT_OK;
-  }
-};
 ScratchPool &scratch_pool() {
   static ScratchPool p;
   return p;
@@ -404,35 +216,7 @@ ScratchPool &scratch_pool() {
 // plans alive: when the last one goes the shared workspaces go with it (a 1024^3 plan leaves 16 GiB)
 std::atomic<int> g_live_plans{0};
 
-}  // namespace
-
-int gfft::scratch_get(hipStream_t s, size_t bytes, void **out) { return scratch_pool().get(s, bytes, out); }
-
-struct gfft_plan_s {
-  int ndims = 0, kind = 0, precision = 0;
-  std::vector<int64_t> sizes_in, sizes_out;
-  std::vector<int> axes;
-  std::vector<Pass> passes;
-  size_t region_bytes[BUF_COUNT] = {0, 0, 0, 0, 0, 0, 0};   // WS / FS / AUX / RING / FS2 sizes
-  double flops = 0, bytes = 0;
-  int variant_rows = 0, variant_cols = 0, xcd_swizzle = 0;
-  int tile_order = -1;                         // plan_fused3: PassDesc::order of the stand-alone strided passes; -1 = not a schedule that takes one
-  bool fused3 = false;
-  int mixv_variant = 0;                        // option mixv_variant at plan time (fft_mixv_*.hip: measured alternatives)
-  int64_t ws_pitch = 0;                        // plan_fused3: entries between consecutive rows of the workspace
-  int ws_tile = 0;                             // ... or: columns of a tile of its tile-major layout
-  std::vector<int64_t> trunc;                  // gfft_plan_create_padded: kept entries per axis (else empty)
-  std::vector<std::vector<hipEvent_t>> prof;   // per execute: events before pass 0 and after each pass
-  std::vector<void *> device_allocs;            // small device buffers the plan owns (descriptors of fused launches)
-  std::vector<Pass> alt;                        // stand-alone forms of the fused pairs (Pass::alt_first)
-  unsigned id = 0;                              // what a voided fused launch reports (async_errors)
-  int device = 0;                               // the device the plan's tables and descriptors live on
-  std::atomic<bool> fused_off{false};           // a fused launch gave up a wait: the pairs run as stand-alone passes from now on
-  std::atomic<bool> voided{false};              // ... and nobody has been told yet (poll_async_error)
-  int async_slot = -1;                          // this plan's word of the host-visible table (async_errors; -1: none taken yet)
-  gfft_plan_s();
-  ~gfft_plan_s();
-};
+int scratch_get(hipStream_t s, size_t bytes, void **out) { return scratch_pool().get(s, bytes, out); }
 
 // ---- fused launches that gave up a wait (fft_pow2_impl.h fused_give_up) --------------------------------
 // The kernel writes the plan's id into the plan's OWN word of a small table of pinned host words (taken at the plan's first
@@ -441,25 +225,6 @@ struct gfft_plan_s {
 // the error until it is reported ONCE: by that plan's own next gfft_execute (which enqueues nothing), by
 // gfft_plan_status(plan), or by gfft_async_error() -- whichever looks first.  Other plans are not refused: the results of
 // the voided plan's last execution are invalid, everything else is untouched.
-namespace {
-struct AsyncErrors {
-  static constexpr int SLOTS = 256;
-  std::mutex m;
-  unsigned *flag = nullptr;                    // SLOTS pinned, device-visible words
-  gfft_plan_s *owner[SLOTS] = {};              // the live plan each word belongs to (a plan takes one at its first fused launch)
-  std::map<unsigned, gfft_plan_s *> live;
-  std::vector<unsigned> orphans;               // ids of voided plans destroyed before anybody looked
-  unsigned next_id = 1;
-  unsigned *word() {
-    if (!flag) {
-      void *p = nullptr;
-      if (hipHostMalloc(&p, SLOTS * sizeof(unsigned), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-      flag = static_cast<unsigned *>(p);
-      for (int i = 0; i < SLOTS; ++i) flag[i] = 0;
-    }
-    return flag;
-  }
-};
 AsyncErrors &async_errors() {
   static AsyncErrors a;
   return a;
@@ -471,7 +236,7 @@ void fused_pairs_off(gfft_plan_s *pl) {
     if (p.kind == PK_FUSED2 && p.alt_buf >= 0 && p.alt_bytes > pl->region_bytes[p.alt_buf]) pl->region_bytes[p.alt_buf] = p.alt_bytes;
 }
 // move what the kernels wrote since the last look into the plans (a.m held by the caller)
-void collect_async_errors(AsyncErrors &a) {
+static void collect_async_errors(AsyncErrors &a) {
   if (!a.flag) return;
   for (int i = 0; i < AsyncErrors::SLOTS; ++i) {
     // (a plain look first -- this runs on entry to every gfft_execute --, then ONE exchange, not load-then-store: a word written
@@ -486,7 +251,7 @@ void collect_async_errors(AsyncErrors &a) {
     pl->voided = true;
   }
 }
-int report_voided(unsigned id) {
+static int report_voided(unsigned id) {
   char msg[320];
   snprintf(msg, sizeof msg, "a fused launch of plan #%u waited longer than %d ms for another workgroup and gave up (device shared or stalled?): "
            "the results of that plan's last execution are INVALID; the plan runs its pass pairs as stand-alone launches from now on", id,
@@ -512,7 +277,7 @@ int poll_async_error(gfft_plan_s *only) {
   }
   return GFFT_OK;
 }
-}  // namespace
+}  // namespace gfft
 gfft_plan_s::gfft_plan_s() {
   device = current_device();
   AsyncErrors &a = async_errors();
@@ -536,11 +301,13 @@ gfft_plan_s::~gfft_plan_s() {
   for (void *q : device_allocs) (void)hipFree(q);
 }
 
-namespace {
+namespace gfft {
 
 void need(gfft_plan_s *pl, int buf, size_t bytes) {
   if (bytes > pl->region_bytes[buf]) pl->region_bytes[buf] = bytes;
 }
+
+namespace {
 
 // Row pitches of the scratch arrays (workspace, four-step intermediate, hand-off slots), in entries of esz bytes.
 // Rule 1: +256 B when the pitch would be a multiple of 2 KiB (rows a power of two apart alias the memory channels).
@@ -609,10 +376,6 @@ bool fused2_arch_ok() {
 // Whether a kernel pair exists for (precision, kind, n_a, n_b) on `planes` planes of slot_bytes each, and its ring: everything
 // that can be known without the descriptors.  make_fused2 starts from it, and plan_fused3 asks it BEFORE it lays the workspace
 // out for a pair.  pair == nullptr: no pair.
-struct PairChoice {
-  const FusedPair *pair = nullptr;
-  int ring = 0, lag = 0;
-};
 PairChoice fused2_pair(int precision, int kind, int n_a, int n_b, int64_t slot_bytes, int planes) {
   // The hand-off protocol leans on gfx94x / gfx950 specifics: raw-buffer cache policy sc0 | sc1 = system scope (written
   // through / never served from a stale L2 line), stores counted by vmcnt -- so that s_waitcnt(0) means "write-through
@@ -631,6 +394,8 @@ PairChoice fused2_pair(int precision, int kind, int n_a, int n_b, int64_t slot_b
   return c;
 }
 
+// Turn two consecutive passes A -> B into one fused launch when a kernel pair exists: dA / dB are the passes
+// cut down to one plane, the plane strides say where plane p starts on A's input and B's output side.
 bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const PassDesc &dA, const PassDesc &dB, int planes,
                  int64_t a_in_plane, int64_t b_out_plane, int64_t slot_bytes, Pass *out) {
   const PairChoice c = fused2_pair(pl->precision, kind, dA.n, dB.n, slot_bytes, planes);
@@ -686,16 +451,6 @@ bool make_fused2(gfft_plan_s *pl, int kind, const Pass &a, const Pass &b, const 
   *out = f;
   return true;
 }
-
-// A batch of 1-D lines: array [outer][nin -> nout][inner] (row-major), logical length n.
-struct Line {
-  int64_t outer, inner, n, nin, nout;
-  int mode;        // PassMode
-  bool inverse;
-  int src, dst;
-};
-
-int plan_line(gfft_plan_s *pl, const Line &L, bool top);
 
 PassDesc natural_desc(const Line &L) {
   PassDesc d{};
@@ -1057,7 +812,6 @@ int plan_embedded(gfft_plan_s *pl, const Line &L, bool bluestein) {
 // (cos/sin sums written as real parts of complex exponentials).  The complex transform runs on
 // whatever plan_line picks for N, so every length works; the cost is that of a length-N complex
 // transform per n real samples -- these kinds are a convenience of the API, not its hot path.
-struct R2RTables { void *pre, *post; };
 std::map<std::tuple<int, int64_t, int, int64_t>, R2RTables> g_r2r_cache;   // (kind, n, precision + device, test-hook signature)
 
 int64_t r2r_logical_n(int kind, int64_t n) {
@@ -1118,6 +872,8 @@ int get_r2r_tables(int kind, int64_t n, int prec, R2RTables *out) {
   *out = it->second;
   return GFFT_OK;
 }
+
+}  // namespace
 
 // one real-to-real axis: [outer][n][inner] real -> same shape; src/dst in {BUF_IN, BUF_OUT}
 int plan_r2r_line(gfft_plan_s *pl, int64_t outer, int64_t n, int64_t inner, int kind, int src, int dst) {
@@ -1191,7 +947,7 @@ int plan_r2r_line(gfft_plan_s *pl, int64_t outer, int64_t n, int64_t inner, int 
   return GFFT_OK;
 }
 
-int64_t max_prime_factor(int64_t n) {
+static int64_t max_prime_factor(int64_t n) {
   int64_t m = 1;
   for (int64_t p = 2; p * p <= n; ++p)
     while (n % p == 0) { m = p; n /= p; }
@@ -1330,10 +1086,7 @@ int plan_fused3(gfft_plan_s *pl) {
   const int64_t nc = tr ? pl->trunc[2] : nc_full;      // complex entries per stored row
   const int64_t t0 = tr ? pl->trunc[0] : n0, t1 = tr ? pl->trunc[1] : n1;
   auto keep = [&](Pass &p, int64_t kept, int64_t of) {   // libfft.py:263-311 as the pass's store / load adapter
-    if (kept == of) return;
-    p.d.tr_dir = inverse ? 2 : 1;
-    p.d.tr_n = p.d.tr_N = (int)kept;
-    p.d.tr_even = (kept % 2 == 0) ? 1 : 0;
+    if (kept != of) set_truncation(p.d, inverse ? 2 : 1, kept);
   };
   const int64_t esz = 2 * prec;
   const int64_t seg = 128 / esz;      // (R4: rows in whole 256-byte pieces instead measured +1 % on the real fp64 schedule: more padding columns, nothing gained)
@@ -1686,21 +1439,16 @@ hipError_t run_pass(const gfft_plan_s *pl, const Pass &p, const PassDesc &d0, co
   return launch_generic(d, p.f, pl->precision, in, out, s);
 }
 
-}  // namespace
-
-namespace gfft {
 int pow2_grid_cap() { return opts().grid_cap > 0 ? opts().grid_cap : 4096; }
-}  // namespace gfft
 
 // Batched 2-D complex transform plane by plane: the passes of gfft_plan_create_guru2 (see there), pushed onto pl->passes
 // -- one fused launch where a pair exists, else (unless fused_only) the two stand-alone passes [first: IN -> OUT, second:
 // in place on OUT].
-static int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, const gfft_iodim *planes, bool inverse, int cols_first,
-                        int in_blocks, int64_t in_block_stride, int out_blocks, int64_t out_block_stride, bool fused_only, bool *fused_out) {
+int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, const gfft_iodim *planes, bool inverse, int cols_first,
+                 int in_blocks, int64_t in_block_stride, int out_blocks, int64_t out_block_stride, bool fused_only, bool *fused_out) {
   const int precision = pl->precision;
   const int64_t esz = 2 * (int64_t)precision;
   const int64_t n1 = cols->n, np = planes->n;
-  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
   // one side of the array pair as the two passes see it: the strided pass steps es along the axis and jumps between
   // blocks; the row pass places row r = (block m, row i of the block) by its batch strides
   struct Side { int nb; int64_t per, es, bstride, plane; };
@@ -1724,12 +1472,12 @@ static int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, con
   };
   auto cols_in = [&](Pass &p, const Side &s) {
     p.d.in_os = s.plane;  p.d.in_es = s.es;
-    if (s.nb > 1) { p.d.in_lgp = lg2(s.nb);  p.d.in_jump = s.bstride - s.per * s.es; }
+    if (s.nb > 1) { p.d.in_lgp = ilog2_ceil(s.nb);  p.d.in_jump = s.bstride - s.per * s.es; }
     p.blocks[0] = s.nb;  p.bstride[0] = s.nb > 1 ? s.bstride : 0;
   };
   auto cols_out = [&](Pass &p, const Side &s) {
     p.d.out_os = s.plane;  p.d.out_es = s.es;
-    if (s.nb > 1) { p.d.out_lgp = lg2(s.nb);  p.d.out_jump = s.bstride - s.per * s.es; }
+    if (s.nb > 1) { p.d.out_lgp = ilog2_ceil(s.nb);  p.d.out_jump = s.bstride - s.per * s.es; }
     p.blocks[1] = s.nb;  p.bstride[1] = s.nb > 1 ? s.bstride : 0;
   };
   // the stand-alone forms: the first pass carries the data across (IN -> OUT), the second runs in place on OUT
@@ -1787,11 +1535,10 @@ static int build_pair2d(gfft_plan_s *pl, const gfft_iodim *cols, int64_t n2, con
 // [strided -> packed-real c2r rows], the strided pass addressing the blocks of the half-spectrum side.  `cx` is the
 // half-spectrum side (strides in complex entries), `re` the real side (strides in reals, even: the rows are read / written
 // as complex pairs); nb / bstride: the blocks of the strided axis on the half-spectrum side.
-static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np, int64_t re_es, int64_t re_plane, int64_t cx_es,
-                             int64_t cx_plane, int nb, int64_t bstride, bool inverse) {
+int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np, int64_t re_es, int64_t re_plane, int64_t cx_es,
+                      int64_t cx_plane, int nb, int64_t bstride, bool inverse) {
   const int prec = pl->precision;
   const int64_t esz = 2 * (int64_t)prec, m = n2 / 2, H = m + 1, per = n1 / nb;
-  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
   // the hand-off slot (and the workspace of the stand-alone backward form): rows of H entries rounded up to whole 128-byte
   // lines, pitched off multiples of 2 KiB and off 129 x 2^k entries (pitch_off_129)
   const int64_t seg = 128 / esz, Pu = (H + seg - 1) / seg * seg;
@@ -1820,7 +1567,7 @@ static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np
   pc.d.inner = H;
   pc.d.in_is = pc.d.out_is = 1;
   pc.d.scale = 1.0;
-  const int lgp = nb > 1 ? lg2(nb) : 0;
+  const int lgp = nb > 1 ? ilog2_ceil(nb) : 0;
   const int64_t jump = nb > 1 ? bstride - per * cx_es : 0;
   if (!inverse) {
     // IN (real) -> OUT: row r of plane o = (block r / per, row r % per of the block) placed by the block stride
@@ -1884,1117 +1631,4 @@ static int build_pair2d_real(gfft_plan_s *pl, int64_t n1, int64_t n2, int64_t np
   return GFFT_OK;
 }
 
-extern "C" {
-
-const char *gfft_strerror(int status) {
-  switch (status) {
-    case GFFT_OK: return "success";
-    case GFFT_ERR_INVALID: return "invalid argument";
-    case GFFT_ERR_UNSUPPORTED: return "unsupported transform";
-    case GFFT_ERR_NO_DEVICE: return "no HIP device";
-    case GFFT_ERR_HIP: return "HIP runtime error";
-    case GFFT_ERR_NOMEM: return "out of memory";
-    case GFFT_ERR_VOIDED: return "asynchronous launch failure";
-  }
-  return "unknown gfft status";
-}
-
-const char *gfft_last_error(void) { return g_last_error.c_str(); }
-
-int gfft_version(void) { return 100; }
-
-int gfft_device_count(int *count) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) {
-    (void)hipGetLastError();
-    if (count) *count = 0;
-    return fail(GFFT_ERR_NO_DEVICE, "no HIP device available");
-  }
-  if (count) *count = n;
-  return GFFT_OK;
-}
-
-int gfft_device_name(int device, char *buf, size_t len) {
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  snprintf(buf, len, "%s (%s, %d CUs)", prop.name, prop.gcnArchName, prop.multiProcessorCount);
-  return GFFT_OK;
-}
-
-int gfft_set_option(const char *key, int value) {
-  if (!key) return fail(GFFT_ERR_INVALID, "null option name");
-  if (!strcmp(key, "grid_cap")) opts().grid_cap = value;
-  else if (!strcmp(key, "variant_rows")) opts().variant_rows = value;
-  else if (!strcmp(key, "variant_cols")) opts().variant_cols = value;
-  else if (!strcmp(key, "force_generic")) opts().force_generic = value;
-  else if (!strcmp(key, "copy_nt")) gfft::g_copy_nt = value;
-  else if (!strcmp(key, "fused3")) opts().fused3 = value;
-  else if (!strcmp(key, "plane2d")) opts().plane2d = value;
-  else if (!strcmp(key, "fuse2")) opts().fuse2 = value;
-  else if (!strcmp(key, "fuse2_ring")) opts().fuse2_ring = value;
-  else if (!strcmp(key, "fuse2_lag")) opts().fuse2_lag = value;
-  else if (!strcmp(key, "fuse2_kinds")) opts().fuse2_kinds = value;
-  else if (!strcmp(key, "fuse2_wait_ms")) opts().fuse2_wait_ms = value;
-  else if (!strcmp(key, "fuse2_f32")) opts().fuse2_f32 = value;
-  else if (!strcmp(key, "fuse2_n512")) gfft::g_fuse2_n512 = value;
-  else if (!strcmp(key, "c2r_2048")) gfft::g_c2r_2048 = value;
-  else if (!strcmp(key, "fuse2_mixv")) gfft::g_fuse2_mixv = value;
-  else if (!strcmp(key, "fuse2_mixed")) gfft::g_fuse2_mixed = value;
-  else if (!strcmp(key, "fuse2_f32_n512")) gfft::g_fuse2_f32_n512 = value;
-  else if (!strcmp(key, "debug_flat")) opts().debug_flat = value;
-  else if (!strcmp(key, "flat_out")) opts().flat_out = value;
-  else if (!strcmp(key, "wtile")) opts().wtile = value;
-  else if (!strcmp(key, "mixv")) opts().mixv = value;
-  else if (!strcmp(key, "mixv_variant")) opts().mixv_variant = value;
-  else if (!strcmp(key, "debug_tile_lg")) opts().debug_tile_lg = value;
-  else if (!strcmp(key, "debug_tile_side")) opts().debug_tile_side = value;
-  else if (!strcmp(key, "debug_tile_stride")) opts().debug_tile_stride = value;
-  else if (!strcmp(key, "profile")) opts().profile = value;
-  else if (!strcmp(key, "debug_tw_index")) opts().debug_tw_index = value;
-  else if (!strcmp(key, "debug_tw_exp")) opts().debug_tw_exp = value;
-  else if (!strcmp(key, "debug_tw_len")) opts().debug_tw_len = value;
-  else if (!strcmp(key, "debug_r2r_index")) opts().debug_r2r_index = value;
-  else if (!strcmp(key, "debug_r2r_exp")) opts().debug_r2r_exp = value;
-  else if (!strcmp(key, "debug_r2r_post")) opts().debug_r2r_post = value;
-  else if (!strcmp(key, "xcd_swizzle")) opts().xcd_swizzle = value;
-  else if (!strcmp(key, "tile_order")) opts().tile_order = value;
-  else if (!strcmp(key, "fused3_min_mib")) opts().fused3_min_bytes = (int64_t)value << 20;
-  else return fail(GFFT_ERR_INVALID, std::string("unknown option ") + key);
-  return GFFT_OK;
-}
-
-int gfft_plan_create(gfft_plan *plan, int ndims, const int64_t *sizes_in, const int64_t *sizes_out,
-                     int naxes, const int *axes, int kind, int precision) {
-  if (!plan || !sizes_in || !sizes_out || !axes) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (ndims < 1 || ndims > 16 || naxes < 1 || naxes > ndims) return fail(GFFT_ERR_INVALID, "bad ndims/naxes");
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  if (kind != GFFT_C2C_FORWARD && kind != GFFT_C2C_BACKWARD && kind != GFFT_R2C && kind != GFFT_C2R)
-    return fail(GFFT_ERR_UNSUPPORTED, "only c2c / r2c / c2r kinds are implemented (r2r kinds are out of scope)");
-  std::vector<int> ax(axes, axes + naxes);
-  std::vector<char> seen(ndims, 0);
-  for (int &a : ax) {
-    if (a < 0) a += ndims;
-    if (a < 0 || a >= ndims || seen[a]) return fail(GFFT_ERR_INVALID, "bad or repeated axis");
-    seen[a] = 1;
-  }
-  const int last = ax.back();
-  for (int i = 0; i < ndims; ++i) {
-    if (sizes_in[i] < 1 || sizes_out[i] < 1) return fail(GFFT_ERR_INVALID, "sizes must be >= 1");
-    if (i == last && kind == GFFT_R2C) {
-      if (sizes_out[i] != sizes_in[i] / 2 + 1) return fail(GFFT_ERR_INVALID, "r2c: sizes_out[axis] must be n/2+1");
-    } else if (i == last && kind == GFFT_C2R) {
-      if (sizes_in[i] != sizes_out[i] / 2 + 1) return fail(GFFT_ERR_INVALID, "c2r: sizes_in[axis] must be n/2+1");
-    } else if (sizes_in[i] != sizes_out[i]) {
-      return fail(GFFT_ERR_INVALID, "sizes_in and sizes_out may differ only along the halved axis");
-    }
-  }
-  int rc = check_device();
-  if (rc) return rc;
-
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = ndims;
-  pl->kind = kind;
-  pl->precision = precision;
-  pl->sizes_in.assign(sizes_in, sizes_in + ndims);
-  pl->sizes_out.assign(sizes_out, sizes_out + ndims);
-  pl->axes = ax;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-
-  rc = GFFT_OK;
-  auto line = [&](int axis, int mode, bool inverse, const std::vector<int64_t> &sin_,
-                  const std::vector<int64_t> &sout_, int src, int dst) {
-    Line L;
-    L.outer = L.inner = 1;
-    for (int i = 0; i < axis; ++i) L.outer *= sin_[i];
-    for (int i = axis + 1; i < ndims; ++i) L.inner *= sin_[i];
-    L.nin = sin_[axis];
-    L.nout = sout_[axis];
-    L.n = (mode == MODE_C2R) ? sout_[axis] : sin_[axis];
-    L.mode = mode;
-    L.inverse = inverse;
-    L.src = src;
-    L.dst = dst;
-    return plan_line(pl, L, true);
-  };
-  if (fused3_applicable(pl)) {
-    rc = plan_fused3(pl);
-  } else if (kind == GFFT_C2C_FORWARD || kind == GFFT_C2C_BACKWARD) {
-    const bool inv = kind == GFFT_C2C_BACKWARD;
-    for (int i = naxes - 1; i >= 0 && !rc; --i)
-      rc = line(ax[i], MODE_C2C, inv, pl->sizes_in, pl->sizes_in, i == naxes - 1 ? BUF_IN : BUF_OUT, BUF_OUT);
-    // Batched 2-D transforms over the last two axes of a 3-D array -- the leading stage of a slab-decomposed
-    // PFFT with collapse=True, or fftn(axes=(1, 2)) --: plane by plane in one fused launch, [strided along axis 1 ->
-    // rows along axis 2] in both directions (build_pair2d: strided reads, whole rows written -- round 6; against the
-    // [rows -> strided] order of rounds 4-5: level in complex128, 9 % ahead in complex64, profiles/r06_stage_probe_slab.txt)
-    if (!rc && ndims == 3 && naxes == 2 && ax[0] == 1 && ax[1] == 2 && pl->passes.size() == 2) {
-      const Pass &pr = pl->passes[0], &pc = pl->passes[1];
-      const int64_t n0 = sizes_in[0], n1 = sizes_in[1], n2 = sizes_in[2];
-      if (pr.kind == PK_FFT && pc.kind == PK_FFT && pr.regk && pc.regk && !pr.cols && pc.cols && !pr.d.tw_hi && !pc.d.tw_hi &&
-          is_pow2(n1) && is_pow2(n2) && n0 < ((int64_t)1 << 30)) {
-        const std::vector<Pass> two = pl->passes;
-        pl->passes.clear();
-        const gfft_iodim c{n1, n2, n2}, p{n0, n1 * n2, n1 * n2};
-        bool fused = false;
-        if (build_pair2d(pl, &c, n2, &p, inv, 1, 1, 0, 1, 0, true, &fused) != GFFT_OK || !fused) pl->passes = two;
-      }
-    }
-    // Planes of 32 x 32 / 64 x 64 points -- config C1's 64^3, small images --: rows and columns of a plane in ONE launch with the
-    // plane held in LDS (fft_plane2d.hip): such arrays live in the caches and a pass costs its dependent memory round trip, not
-    // its bytes (64^3 complex128: three passes of ~5 us each, tools/c1_probe.py); this removes one of them.
-    // (a 2-D array is one plane)
-    const int p0 = ndims - 2;                                // the two in-plane axes: p0, p0 + 1
-    if (!rc && (ndims == 3 || ndims == 2) && naxes >= 2 && ax[naxes - 2] == p0 && ax[naxes - 1] == p0 + 1 &&
-        (naxes == 2 || (ndims == 3 && naxes == 3 && ax[0] == 0)) &&
-        sizes_in[p0] == sizes_in[p0 + 1] && plane2d_supported((int)sizes_in[p0], precision) && pl->passes.size() == (size_t)naxes && opts().plane2d) {
-      const Pass &pr = pl->passes[0], &pc = pl->passes[1];
-      const int64_t nplanes = ndims == 3 ? sizes_in[0] : 1;
-      if (pr.kind == PK_FFT && pc.kind == PK_FFT && pr.regk && pc.regk && !pr.cols && pc.cols && nplanes < ((int64_t)1 << 30)) {
-        const int64_t n = sizes_in[p0], P = plane2d_pitch((int)n), esz = 2 * (int64_t)precision;
-        Pass f = pr;
-        f.kind = PK_PLANE2D;
-        f.d = pr.d;                                          // rows of ONE plane: natural rows -> the plane in LDS, rows P entries apart
-        f.d.batch = n;  f.d.mid = 1;  f.d.inner = 1;  f.d.in_os = n;  f.d.in_is = 0;  f.d.out_os = P;  f.d.out_is = 0;
-        f.d2 = pc.d;                                         // columns of one plane: LDS -> natural rows
-        f.d2.batch = n;  f.d2.mid = 1;  f.d2.inner = n;  f.d2.in_os = 0;  f.d2.out_os = 0;  f.d2.in_es = P;  f.d2.in_is = 1;
-        f.fused.planes = (int)nplanes;
-        f.fused.a_in_plane = n * n * esz;
-        f.fused.b_out_plane = n * n * esz;
-        f.src = BUF_IN;  f.dst = BUF_OUT;
-        f.bytes2 = 4.0 * (double)nplanes * (double)n * (double)n * (double)esz;
-        pl->passes.erase(pl->passes.begin(), pl->passes.begin() + 2);
-        pl->passes.insert(pl->passes.begin(), f);
-      }
-    }
-  } else if (kind == GFFT_R2C) {
-    rc = line(last, MODE_R2C, false, pl->sizes_in, pl->sizes_out, BUF_IN, BUF_OUT);
-    for (int i = naxes - 2; i >= 0 && !rc; --i)
-      rc = line(ax[i], MODE_C2C, false, pl->sizes_out, pl->sizes_out, BUF_OUT, BUF_OUT);
-  } else {
-    // C2R: the complex passes run into / inside the WS region, so the caller's input is never
-    // written (FFTW's multi-dimensional c2r destroys it), then the real pass
-    for (int i = 0; i <= naxes - 2 && !rc; ++i)
-      rc = line(ax[i], MODE_C2C, true, pl->sizes_in, pl->sizes_in, i == 0 ? BUF_IN : BUF_WS, BUF_WS);
-    if (!rc) rc = line(last, MODE_C2R, true, pl->sizes_in, pl->sizes_out, naxes > 1 ? BUF_WS : BUF_IN, BUF_OUT);
-    if (naxes > 1) {
-      size_t bytes = 2 * (size_t)precision;
-      for (int i = 0; i < ndims; ++i) bytes *= (size_t)sizes_in[i];
-      need(pl, BUF_WS, bytes);
-    }
-  }
-  if (rc) {
-    delete pl;
-    return rc;
-  }
-  // the scale factor rides on the last pass
-  pl->passes.back().carries_scale = true;
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-int gfft_plan_create_padded(gfft_plan *plan, const int64_t *padded, const int64_t *kept, int kind, int precision) {
-  if (!plan || !padded || !kept) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  if (kind != GFFT_C2C_FORWARD && kind != GFFT_C2C_BACKWARD && kind != GFFT_R2C && kind != GFFT_C2R)
-    return fail(GFFT_ERR_INVALID, "kind must be c2c forward / backward, r2c or c2r");
-  const bool real = kind == GFFT_R2C || kind == GFFT_C2R;
-  const bool inverse = kind == GFFT_C2C_BACKWARD || kind == GFFT_C2R;
-  for (int i = 0; i < 3; ++i) {
-    const int64_t of = (real && i == 2) ? padded[i] / 2 + 1 : padded[i];
-    if (padded[i] < 1 || kept[i] < 1 || kept[i] > of) return fail(GFFT_ERR_INVALID, "kept entries must lie in 1 .. transformed entries");
-  }
-  int rc = check_device();
-  if (rc) return rc;
-  // the all-axes schedule needs one register-kernel pass per axis (packed-real rows on a real axis)
-  if (!opts().fused3) return fail(GFFT_ERR_UNSUPPORTED, "fused 3-D plans are switched off");
-  for (int i = 0; i < 3; ++i) {
-    const bool real_axis = i == 2 && real;
-    const bool one_pass = regk_ok(padded[i], precision) ||
-                          (real_axis ? (padded[i] % 2 == 0 && real_half_mixv_ok(padded[i] / 2)) : regk_c2c_ok(padded[i], precision, MODE_C2C));
-    if (!one_pass || (kept[i] < (real_axis ? padded[i] / 2 + 1 : padded[i]) && !fused_pad_ok(real_axis ? padded[i] / 2 : padded[i])))
-      return fail(GFFT_ERR_UNSUPPORTED, "padded length without a single-pass kernel");
-  }
-  if (real && !(padded[2] % 2 == 0 &&
-                (real_half_supported((int)(padded[2] / 2)) || real_half_mix_supported((int)(padded[2] / 2)) || real_half_mixv_ok(padded[2] / 2))))
-    return fail(GFFT_ERR_UNSUPPORTED, "real axis without a packed-real row kernel");
-  const int64_t bytes = padded[0] * padded[1] * padded[2] * (real ? 1 : 2) * precision;
-  if (bytes < opts().fused3_min_bytes) return fail(GFFT_ERR_UNSUPPORTED, "below the size where the workspace schedule pays");
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = 3;
-  pl->kind = kind;
-  pl->precision = precision;
-  std::vector<int64_t> phys(padded, padded + 3), spec(kept, kept + 3);
-  pl->sizes_in = inverse ? spec : phys;
-  pl->sizes_out = inverse ? phys : spec;
-  pl->axes = {0, 1, 2};
-  pl->trunc = spec;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-  rc = plan_fused3(pl);
-  if (rc) {
-    delete pl;
-    return rc;
-  }
-  pl->passes.back().carries_scale = true;
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-int gfft_plan_create_r2r(gfft_plan *plan, int ndims, const int64_t *sizes, int naxes, const int *axes,
-                         const int *kinds, int precision) {
-  if (!plan || !sizes || !axes || !kinds) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (ndims < 1 || ndims > 16 || naxes < 1 || naxes > ndims) return fail(GFFT_ERR_INVALID, "bad ndims/naxes");
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  std::vector<int> ax(axes, axes + naxes);
-  std::vector<char> seen(ndims, 0);
-  for (int i = 0; i < naxes; ++i) {
-    int &a = ax[i];
-    if (a < 0) a += ndims;
-    if (a < 0 || a >= ndims || seen[a]) return fail(GFFT_ERR_INVALID, "bad or repeated axis");
-    seen[a] = 1;
-    if (kinds[i] < GFFT_REDFT00 || kinds[i] > GFFT_RODFT11)
-      return fail(GFFT_ERR_UNSUPPORTED, "r2r kind must be one of REDFT00..RODFT11 (halfcomplex / DHT kinds are not implemented)");
-  }
-  for (int i = 0; i < ndims; ++i)
-    if (sizes[i] < 1) return fail(GFFT_ERR_INVALID, "sizes must be >= 1");
-  int rc = check_device();
-  if (rc) return rc;
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = ndims;
-  pl->kind = GFFT_R2R;
-  pl->precision = precision;
-  pl->sizes_in.assign(sizes, sizes + ndims);
-  pl->sizes_out = pl->sizes_in;
-  pl->axes = ax;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-  for (int i = naxes - 1; i >= 0 && !rc; --i) {
-    int64_t outer = 1, inner = 1;
-    for (int k = 0; k < ax[i]; ++k) outer *= sizes[k];
-    for (int k = ax[i] + 1; k < ndims; ++k) inner *= sizes[k];
-    rc = plan_r2r_line(pl, outer, sizes[ax[i]], inner, kinds[i], i == naxes - 1 ? BUF_IN : BUF_OUT, BUF_OUT);
-  }
-  if (rc) {
-    delete pl;
-    return rc;
-  }
-  pl->passes.back().carries_scale = true;
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void *stream) {
-  if (!pl || !d_in || !d_out) return fail(GFFT_ERR_INVALID, "null argument");
-  {
-    // a fused launch of an earlier execution of THIS plan gave up a wait: report it now, once, and enqueue nothing (the
-    // plan has been switched to stand-alone passes; calling again runs it that way).  Another plan's pending event stays
-    // with that plan (gfft_plan_status / gfft_async_error / its own next execute) and does not refuse this call.
-    int rc = poll_async_error(pl);
-    if (rc) return rc;
-  }
-  if (current_device() != pl->device) return fail(GFFT_ERR_INVALID, "the plan was made on another device than the calling thread's current one");
-  if ((pl->kind == GFFT_R2C || pl->kind == GFFT_C2R) && d_in == d_out)
-    return fail(GFFT_ERR_INVALID, "in-place real transforms are not supported");
-  if (!pl->fused_off && pl->async_slot < 0) {
-    bool any = false;
-    for (const Pass &q : pl->passes) any = any || q.kind == PK_FUSED2;
-    if (any) {
-      // this plan's own word of the host-visible table: two live plans never share one (ids 64 apart used to), so a
-      // voided launch is always attributed; with every word taken the pairs run as their stand-alone passes instead
-      AsyncErrors &ae = async_errors();
-      std::lock_guard<std::mutex> lock(ae.m);
-      if (ae.word())
-        for (int i = 0; i < AsyncErrors::SLOTS && pl->async_slot < 0; ++i)
-          if (!ae.owner[i]) { ae.owner[i] = pl; pl->async_slot = i; }
-      if (pl->async_slot < 0) fused_pairs_off(pl);
-    }
-  }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // scratch regions: carved from the stream's shared buffer (scratch_pool)
-  size_t off[BUF_COUNT] = {0, 0, 0, 0, 0, 0, 0}, total = 0;
-  for (int b = BUF_WS; b < BUF_COUNT; ++b) {
-    off[b] = total;
-    total += align256(pl->region_bytes[b]);
-  }
-  void *scratch = nullptr;
-  if (total) {
-    int rc = scratch_pool().get(s, total, &scratch);
-    if (rc) return rc;
-  }
-  void *bufs[BUF_COUNT] = {const_cast<void *>(d_in), d_out, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int b = BUF_WS; b < BUF_COUNT; ++b)
-    if (pl->region_bytes[b]) bufs[b] = static_cast<char *>(scratch) + off[b];
-
-  std::vector<hipEvent_t> *ev = nullptr;
-  auto mark = [&]() -> hipError_t {
-    if (!ev) return hipSuccess;
-    hipEvent_t e;
-    hipError_t rc = hipEventCreate(&e);
-    if (rc != hipSuccess) return rc;
-    rc = hipEventRecord(e, s);
-    ev->push_back(e);
-    return rc;
-  };
-  if (opts().profile) {
-    pl->prof.emplace_back();
-    ev = &pl->prof.back();
-    HIP_TRY(mark());
-  }
-  for (const Pass &p : pl->passes) {
-    PassDesc d = p.d;
-    if (p.kind == PK_PLANE2D) {
-      PassDesc d2 = p.d2;
-      d2.scale = p.carries_scale ? scale : 1.0;
-      HIP_TRY(launch_plane2d(d, d2, pl->precision, p.fused.planes, p.fused.a_in_plane, p.fused.b_out_plane, bufs[p.src], bufs[p.dst], s));
-      HIP_TRY(mark());
-      continue;
-    }
-    if (p.kind == PK_FUSED2 && pl->fused_off) {
-      // the pair as its two stand-alone passes (a fused launch of this plan gave up a wait, poll_async_error)
-      for (int k = 0; k < 2; ++k) {
-        const Pass &q = pl->alt[p.alt_first + k];
-        PassDesc dq = q.d;
-        const bool sc = k == 1 && p.carries_scale;
-        if (sc) dq.scale = scale;
-        HIP_TRY(run_pass(pl, q, dq, bufs[q.src], bufs[q.dst], sc ? scale : 1.0, s));
-      }
-      HIP_TRY(mark());
-      continue;
-    }
-    if (p.kind == PK_FUSED2) {
-      PassDesc d2 = p.d2;
-      if (p.carries_scale) d2.scale = scale;
-      FusedDesc f = p.fused;
-      char *ring = static_cast<char *>(bufs[BUF_RING]);
-      f.ctr = reinterpret_cast<unsigned *>(ring + (size_t)f.ring * (size_t)f.slot_bytes);
-      {
-        AsyncErrors &ae = async_errors();
-        f.host_flag = (ae.flag && pl->async_slot >= 0) ? ae.flag + pl->async_slot : nullptr;
-        const int ms = opts().fuse2_wait_ms;
-        f.wait_ticks = ms <= 0 ? 0u : (ms > 40000 ? 4000000000u : (unsigned)ms * 100000u);      // 100 MHz ticks
-      }
-      static const int debug = getenv("GFFT_FUSE2_DEBUG") ? atoi(getenv("GFFT_FUSE2_DEBUG")) : 0;
-      if (debug) { f.wait_ticks = 100000u; f.host_flag = nullptr; f.debug = (unsigned)debug; }      // (1 ms; counters printed below)
-      HIP_TRY(p.pair->launch(d, d2, p.dev_descs, f, bufs[p.src], ring, bufs[p.dst], s));
-      if (debug) {      // developer aid: the launch's counters (tickets drawn, waits given up, tiles per plane)
-        HIP_TRY(hipStreamSynchronize(s));
-        std::vector<unsigned> h(16 + 2 * (size_t)f.planes);
-        HIP_TRY(hipMemcpy(h.data(), f.ctr, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        unsigned long long sa = 0, sb = 0;
-        for (int i = 0; i < f.planes; ++i) { sa += h[16 + i]; sb += h[16 + f.planes + i]; }
-        fprintf(stderr, "[gfft fuse2] kind %d planes %d tiles %d+%d ring %d lag %d: tickets %u, waits given up %u, A tiles %llu, B tiles %llu\n",
-                p.fused_kind, f.planes, f.tiles_a, f.tiles_b, f.ring, f.lag, h[0], h[1], sa, sb);
-#ifdef GFFT_FUSE2_TRACE
-        if (const char *path = getenv("GFFT_FUSE2_TRACE_FILE")) {
-          std::vector<unsigned long long> tr((size_t)1024 * 96 * 16);
-          const size_t off = ((16 + 2 * (size_t)f.planes + 63) & ~(size_t)63) * sizeof(unsigned);
-          HIP_TRY(hipMemcpy(tr.data(), reinterpret_cast<char *>(f.ctr) + off, tr.size() * sizeof(tr[0]), hipMemcpyDeviceToHost));
-          if (FILE *fp = fopen(path, "wb")) { fwrite(tr.data(), sizeof(tr[0]), tr.size(), fp); fclose(fp); }
-        }
-#endif
-      }
-      HIP_TRY(mark());
-      continue;
-    }
-    if (p.carries_scale) d.scale = scale;
-    HIP_TRY(run_pass(pl, p, d, bufs[p.src], bufs[p.dst], p.carries_scale ? scale : 1.0, s));
-    HIP_TRY(mark());
-  }
-  return GFFT_OK;
-}
-
-/* Accumulated per-pass kernel time since the last call (needs option "profile" = 1 while
- * executing): ms[i] = total milliseconds of pass i, *executes = number of executes summed.
- * Synchronises on the recorded events and frees them. */
-int gfft_plan_profile(gfft_plan pl, float *ms, int max_passes, int *executes) {
-  if (!pl || !ms) return fail(GFFT_ERR_INVALID, "null argument");
-  for (int i = 0; i < max_passes; ++i) ms[i] = 0.f;
-  int n = 0;
-  for (auto &ev : pl->prof) {
-    if (ev.empty()) continue;
-    HIP_TRY(hipEventSynchronize(ev.back()));
-    for (size_t i = 0; i + 1 < ev.size(); ++i) {
-      float t = 0.f;
-      HIP_TRY(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-      if ((int)i < max_passes) ms[i] += t;
-    }
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    ++n;
-  }
-  pl->prof.clear();
-  if (executes) *executes = n;
-  return GFFT_OK;
-}
-
-/* text name of the kernel family behind pass i ("pow2-rows", "pow2-cols", "generic") */
-int gfft_plan_pass_info(gfft_plan pl, int i, char *buf, size_t len, double *bytes) {
-  if (!pl || i < 0 || i >= (int)pl->passes.size()) return fail(GFFT_ERR_INVALID, "bad pass index");
-  const Pass &p = pl->passes[i];
-  static const char *kinds[] = {"", "embed", "mul-B", "extract"};
-  if (p.kind == PK_FUSED2) {
-    // two axis passes in one launch: the algorithmic bytes of both (one read + one write of the array each)
-    snprintf(buf, len, "%s n=%dx%d", kFusedKinds[p.fused_kind].pass_name, p.d.n, p.d2.n);
-    if (bytes) *bytes = p.bytes2 > 1 ? p.bytes2 : (double)p.fused.planes * 2.0 * pl->precision *
-                        ((double)p.d.batch * 2.0 * p.d.n + (double)p.d2.batch * 2.0 * p.d2.n);
-    return GFFT_OK;
-  }
-  if (p.kind == PK_PLANE2D) {
-    snprintf(buf, len, "planes in LDS rows+cols n=%dx%d", p.d.n, p.d2.n);
-    if (bytes) *bytes = p.bytes2;
-    return GFFT_OK;
-  }
-  if (p.kind != PK_FFT) {
-    snprintf(buf, len, "%s n=%lld", kinds[p.kind], (long long)p.pt.n);
-    if (bytes) *bytes = 0;
-    return GFFT_OK;
-  }
-  const bool percol = !p.regk && (p.d.n == 3 || p.d.n == 5 || p.d.n == 7 || p.d.n == 11 || p.d.n == 13) &&
-                      p.d.mode == MODE_C2C && !p.d.tw_hi && p.d.in_is == 1 && p.d.out_is == 1 && p.d.inner >= 64;
-  snprintf(buf, len, "%s n=%d", p.regk ? (p.cols ? "pow2-cols" : "pow2-rows") : (percol ? "percol" : "generic"), p.d.n);
-  if (bytes && (p.d.mode == MODE_R2C_H || p.d.mode == MODE_C2R_H)) {
-    // n complex = 2n reals on one side, n + 1 complex on the other
-    *bytes = (double)p.d.batch * (2.0 * p.d.n * pl->precision + (p.d.n + 1.0) * 2.0 * pl->precision);
-    snprintf(buf, len, "real-rows n=%d", 2 * p.d.n);
-    return GFFT_OK;
-  }
-  if (bytes) {
-    const double esz = 2.0 * pl->precision;
-    const double nc = p.d.mode == MODE_C2C ? p.d.n : p.d.n / 2 + 1;
-    const double ein = p.d.mode == MODE_R2C ? p.d.n * (double)pl->precision : nc * esz;
-    const double eout = p.d.mode == MODE_C2R ? p.d.n * (double)pl->precision : nc * esz;
-    *bytes = (double)p.d.batch * (ein + eout);
-    if (p.data_inner) *bytes *= (double)p.data_inner / (double)p.d.inner;
-    if (p.d.mode == MODE_R2R) *bytes = (double)p.d.batch * 2.0 * p.d.r2r_n * (double)pl->precision;
-  }
-  return GFFT_OK;
-}
-
-/* Fuse the 3/2-rule truncation (forward kinds) or zero-padding (backward kinds) of
- * libfft.py:263-311 into a single-axis plan: the truncated array (n_keep entries along the axis:
- * N for a complex axis, N/2+1 for the real half-axis) becomes the plan's output (input).
- * Returns GFFT_ERR_UNSUPPORTED, leaving the plan unchanged, when the plan is not one
- * register-kernel pass (the caller then uses gfft_truncate / gfft_pad). */
-int gfft_plan_set_truncation(gfft_plan pl, int64_t n_keep) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (pl->passes.size() != 1 || pl->axes.size() != 1 || pl->fused3)
-    return fail(GFFT_ERR_UNSUPPORTED, "truncation fuses into single-pass plans only");
-  Pass &p = pl->passes[0];
-  if (p.d.mode == MODE_R2C_H || p.d.mode == MODE_C2R_H) {
-    // packed-real rows: the truncating store / zero-padding load act on the half spectrum
-    // (entries 0 .. n_keep-1 of the p.d.n + 1; strides are in complex entries, inner == 1)
-    const int64_t full_h = (int64_t)p.d.n + 1;
-    if (n_keep < 1 || n_keep > full_h) return fail(GFFT_ERR_INVALID, "bad truncated length");
-    if (n_keep == full_h) return GFFT_OK;        // nothing to cut: the plain plan is the answer
-    if (!fused_pad_ok(p.d.n)) return fail(GFFT_ERR_UNSUPPORTED, "no fused truncation kernels for this length in this build");
-    const bool fwd_h = p.d.mode == MODE_R2C_H;
-    const double lines_h = (double)p.d.batch, esz_h = 2.0 * pl->precision;
-    if (fwd_h) { p.d.tr_dir = 1; p.d.out_os = n_keep; } else { p.d.tr_dir = 2; p.d.in_os = n_keep; }
-    pl->bytes += lines_h * ((double)n_keep - (double)full_h) * esz_h;
-    p.d.tr_n = p.d.tr_N = (int)n_keep;
-    p.d.tr_even = (n_keep % 2 == 0) ? 1 : 0;
-    return GFFT_OK;
-  }
-  if (p.kind != PK_FFT || !p.regk || p.d.mid != 1 || p.d.tw_hi || !fused_pad_ok(p.d.n))
-    return fail(GFFT_ERR_UNSUPPORTED, "truncation fuses into register-kernel passes only");
-  const int axis = pl->axes[0];
-  const bool fwd = pl->kind == GFFT_C2C_FORWARD || pl->kind == GFFT_R2C;
-  const bool real = pl->kind == GFFT_R2C || pl->kind == GFFT_C2R;
-  const int64_t full = real ? p.d.n / 2 + 1 : p.d.n;
-  if (n_keep < 1 || n_keep > full) return fail(GFFT_ERR_INVALID, "bad truncated length");
-  int64_t inner = 1;
-  for (int i = axis + 1; i < pl->ndims; ++i) inner *= pl->sizes_in[i];
-  const double esz = 2.0 * pl->precision;
-  const double lines = (double)p.d.batch;
-  if (fwd) {
-    p.d.tr_dir = 1;
-    p.d.out_os = n_keep * inner;
-    pl->bytes -= lines * (double)full * esz;
-  } else {
-    p.d.tr_dir = 2;
-    p.d.in_os = n_keep * inner;
-    pl->bytes -= lines * (double)full * esz;
-  }
-  pl->bytes += lines * (double)n_keep * esz;
-  p.d.tr_n = (int)n_keep;
-  p.d.tr_N = (int)n_keep;
-  p.d.tr_even = (n_keep % 2 == 0) ? 1 : 0;
-  return GFFT_OK;
-}
-
-/* Packed-layout adapters (see include/gfft.h).  side 0: the plan reads its input from an
- * all-to-all receive buffer; side 1: it writes its output as an all-to-all send buffer.  Both are
- * the layout gfft_pack produces for `nblocks` equal blocks of the transformed axis:
- * [block][outer][n/nblocks][inner].  nblocks = 1 restores the natural layout. */
-int gfft_plan_set_split(gfft_plan pl, int side, int nblocks) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (side != 0 && side != 1) return fail(GFFT_ERR_INVALID, "side must be 0 (input) or 1 (output)");
-  if (pl->passes.size() != 1 || pl->axes.size() != 1 || pl->fused3)
-    return fail(GFFT_ERR_UNSUPPORTED, "split layouts fuse into single-pass plans only");
-  Pass &p = pl->passes[0];
-  // (3 x 5 x 2^k lengths: their stages keep different numbers of values per thread, and a block boundary would have to
-  // fall between the same thread slots on the load AND the store geometry -- natural layouts only, fft_mixv_*.hip)
-  if (p.regk && mixv_supported(p.d.n)) return fail(GFFT_ERR_UNSUPPORTED, "split layouts: not for 3 x 5 x 2^k lengths");
-  if ((p.d.mode == MODE_R2C_H && side == 1) || (p.d.mode == MODE_C2R_H && side == 0)) {
-    // packed-real rows: the half-spectrum side as an all-to-all buffer of UNEVEN blocks (the
-    // n/2 + 1 entries never divide evenly; pencil.py:5-9 deals the remainder to the first ranks)
-    if (p.d.mid != 1 || p.d.inner != 1) return fail(GFFT_ERR_UNSUPPORTED, "split layout: packed-real rows only");
-    // (with a fused truncation / zero padding the blocks are those of the KEPT entries)
-    const int nh = p.d.tr_dir ? p.d.tr_n : p.d.n + 1;
-    if (nblocks < 1 || nblocks > 8 || nblocks > nh) return fail(GFFT_ERR_UNSUPPORTED, "split layout: at most 8 blocks");
-    if (nblocks == 1) {
-      p.d.ub_p = 0;
-      return GFFT_OK;
-    }
-    const int q = nh / nblocks, r = nh % nblocks;
-    p.d.ub_p = nblocks;
-    for (int b = 0; b <= nblocks; ++b) p.d.ub_start[b] = b * q + (b < r ? b : r);
-    for (int b = nblocks + 1; b < 9; ++b) p.d.ub_start[b] = nh;
-    p.d.ub_minw = q;
-    p.d.ub_rows = p.d.batch;
-    return GFFT_OK;
-  }
-  if (p.kind != PK_FFT || !p.regk || p.d.mid != 1 || p.d.tw_hi || p.d.mode != MODE_C2C)
-    return fail(GFFT_ERR_UNSUPPORTED, "split layouts fuse into complex register-kernel passes only");
-  const int64_t n = p.d.n, inner = p.d.inner, outer = p.d.batch / p.d.inner;
-  int lg = 0;
-  while ((1 << lg) < nblocks) ++lg;
-  if (nblocks < 1 || (1 << lg) != nblocks) return fail(GFFT_ERR_UNSUPPORTED, "block count must be a power of two");
-  if (p.d.tr_dir && side == (p.d.tr_dir == 1 ? 1 : 0)) {
-    // the TRUNCATED side of a fused 3/2-rule truncation / zero padding: equal blocks of the kept
-    // entries, addressed per entry (PassDesc::tr_jump) -- no tie to the kernel's thread layout
-    const int64_t keep = p.d.tr_N;
-    if (nblocks > 8 || keep % nblocks) return fail(GFFT_ERR_UNSUPPORTED, "block count does not divide the kept length");
-    const int64_t per = keep / nblocks;
-    if (nblocks > 1 && !is_pow2(per)) return fail(GFFT_ERR_UNSUPPORTED, "kept entries per block must be a power of two");
-    int lgper = 0;
-    while (((int64_t)1 << lgper) < per) ++lgper;
-    if (nblocks > 1 && (double)(outer - 1) * per * inner * (nblocks - 1) >= 2147483648.0)
-      return fail(GFFT_ERR_UNSUPPORTED, "blocked truncated side beyond 2^31 elements");      // (32-bit block offsets in the kernels)
-    p.d.tr_lgper = nblocks > 1 ? lgper : 0;
-    p.d.tr_jump = nblocks > 1 ? (outer - 1) * per * inner : 0;
-    (side == 0 ? p.d.in_os : p.d.out_os) = per * inner;
-    return GFFT_OK;
-  }
-  // whole thread slots per block: R = 4 (n = 16), 8 or 16 (other powers of two), 12 / 20 (3^b 2^k / 5^c 2^k)
-  const int max_blocks = is_pow2(n) ? (n >= 32 ? 8 : 4) : 4;
-  if (nblocks > max_blocks || n % nblocks) return fail(GFFT_ERR_UNSUPPORTED, "block count not supported for this length");
-  const int64_t nb = n / nblocks;
-  const int64_t os = nb * inner, jump = nblocks > 1 ? (outer - 1) * nb * inner : 0;
-  // (what gfft_plan_create_guru would have recorded for the same layout: gfft_plan_set_tiles re-derives the block
-  // jump from these)
-  p.blocks[side] = nblocks;
-  p.bstride[side] = nblocks > 1 ? outer * nb * inner : 0;
-  if (side == 0) {
-    p.d.in_os = os;
-    p.d.in_jump = jump;
-    p.d.in_lgp = lg;
-  } else {
-    p.d.out_os = os;
-    p.d.out_jump = jump;
-    p.d.out_lgp = lg;
-  }
-  return GFFT_OK;
-}
-
-int gfft_plan_create_guru(gfft_plan *plan, int precision, int kind, const gfft_iodim *dim, int howmany_rank,
-                          const gfft_iodim *howmany, int in_blocks, int64_t in_block_stride, int out_blocks,
-                          int64_t out_block_stride) {
-  return gfft_plan_create_guru_padded(plan, precision, kind, dim, 0, howmany_rank, howmany, in_blocks, in_block_stride,
-                                      out_blocks, out_block_stride);
-}
-
-int gfft_plan_create_guru_padded(gfft_plan *plan, int precision, int kind, const gfft_iodim *dim, int64_t n_keep,
-                                 int howmany_rank, const gfft_iodim *howmany, int in_blocks, int64_t in_block_stride,
-                                 int out_blocks, int64_t out_block_stride) {
-  if (!plan || !dim || (howmany_rank > 0 && !howmany)) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  if (kind != GFFT_C2C_FORWARD && kind != GFFT_C2C_BACKWARD) return fail(GFFT_ERR_UNSUPPORTED, "guru plans are complex-to-complex");
-  if (howmany_rank < 0 || howmany_rank > 3) return fail(GFFT_ERR_UNSUPPORTED, "at most three batch dims");
-  if (dim->n < 1) return fail(GFFT_ERR_INVALID, "bad transform length");
-  int rc = check_device();
-  if (rc) return rc;
-  if (!regk_ok(dim->n, precision)) return fail(GFFT_ERR_UNSUPPORTED, "no single-pass register kernel for this length");
-  // batch dims -> (outer, mid, inner): the last listed dim is the one adjacent columns run along
-  gfft_iodim o{1, 0, 0}, m{1, 0, 0}, i{1, 0, 0};
-  if (howmany_rank == 1) i = howmany[0];
-  if (howmany_rank == 2) { o = howmany[0]; i = howmany[1]; }
-  if (howmany_rank == 3) { o = howmany[0]; m = howmany[1]; i = howmany[2]; }
-  if (o.n < 1 || m.n < 1 || i.n < 1) return fail(GFFT_ERR_INVALID, "bad batch length");
-  const double batch = (double)o.n * (double)m.n * (double)i.n;
-  if (batch >= 2147483648.0) return fail(GFFT_ERR_UNSUPPORTED, "batch exceeds 2^31");
-  const int64_t n = dim->n;
-  if (n_keep < 0 || n_keep > n) return fail(GFFT_ERR_INVALID, "bad kept length");
-  const bool trunc = n_keep > 0 && n_keep < n;
-  if (trunc && !fused_pad_ok(n)) return fail(GFFT_ERR_UNSUPPORTED, "no fused truncation kernels for this length in this build");
-  const int tr_side = kind == GFFT_C2C_FORWARD ? 1 : 0;           // the side that holds the kept entries
-  auto blocks_ok = [&](int nb, int side) {
-    if (nb < 1 || (nb & (nb - 1))) return false;
-    if (trunc && side == tr_side)                                // equal power-of-two blocks of the kept entries
-      return nb <= 8 && n_keep % nb == 0 && (nb == 1 || is_pow2(n_keep / nb));
-    const int max_blocks = is_pow2(n) ? (n >= 32 ? 8 : 4) : 4;    // whole thread slots per block (see gfft_plan_set_split)
-    return nb <= max_blocks && n % nb == 0;
-  };
-  if (!blocks_ok(in_blocks, 0) || !blocks_ok(out_blocks, 1)) return fail(GFFT_ERR_UNSUPPORTED, "block count not supported for this length");
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = 0;
-  pl->kind = kind;
-  pl->precision = precision;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-  Pass p;
-  p.regk = true;
-  p.cols = !(dim->is == 1 && dim->os == 1);
-  p.logical_first = true;
-  p.carries_scale = true;
-  PassDesc &d = p.d;
-  const bool inverse = kind == GFFT_C2C_BACKWARD;
-  d.n = (int)n;
-  d.mode = MODE_C2C;
-  d.conj_in = d.conj_out = inverse ? 1 : 0;
-  d.batch = o.n * m.n * i.n;
-  d.mid = m.n;
-  d.inner = i.n;
-  d.in_os = o.is; d.in_ms = m.is; d.in_is = i.is; d.in_es = dim->is;
-  d.out_os = o.os; d.out_ms = m.os; d.out_is = i.os; d.out_es = dim->os;
-  d.scale = 1.0;
-  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-  if (in_blocks > 1 && !(trunc && tr_side == 0)) { d.in_lgp = lg2(in_blocks); d.in_jump = in_block_stride - (n / in_blocks) * dim->is; }
-  if (out_blocks > 1 && !(trunc && tr_side == 1)) { d.out_lgp = lg2(out_blocks); d.out_jump = out_block_stride - (n / out_blocks) * dim->os; }
-  if (trunc) {
-    // fused 3/2-rule truncation (forward: store side) / zero padding (backward: load side), as
-    // gfft_plan_set_truncation sets it on natural plans; blocks of the kept entries by PassDesc::tr_jump
-    d.tr_dir = tr_side == 1 ? 1 : 2;
-    d.tr_n = d.tr_N = (int)n_keep;
-    d.tr_even = (n_keep % 2 == 0) ? 1 : 0;
-    const int nb = tr_side == 1 ? out_blocks : in_blocks;
-    if (nb > 1) {
-      const int64_t per = n_keep / nb;
-      d.tr_lgper = lg2((int)per);
-      d.tr_jump = (tr_side == 1 ? out_block_stride - per * dim->os : in_block_stride - per * dim->is);
-      if (std::fabs((double)d.tr_jump) * (nb - 1) >= 2147483648.0) {        // (32-bit block offsets in the kernels)
-        delete pl;
-        return fail(GFFT_ERR_UNSUPPORTED, "blocked truncated side beyond 2^31 elements");
-      }
-    }
-  }
-  p.blocks[0] = in_blocks;   p.bstride[0] = in_block_stride;
-  p.blocks[1] = out_blocks;  p.bstride[1] = out_block_stride;
-  rc = get_twiddles(n, precision, &d.tw);
-  if (rc) { delete pl; return rc; }
-  pl->passes.push_back(p);
-  if (n > 1) pl->flops = 5.0 * (double)n * std::log2((double)n) * batch;
-  pl->bytes = batch * (double)(n + (trunc ? n_keep : n)) * 2.0 * precision;
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-
-
-/* The two local stages of a slab-decomposed transform as one plan (see include/gfft.h). */
-int gfft_plan_create_guru2(gfft_plan *plan, int precision, int kind, const gfft_iodim *cols, const gfft_iodim *rows,
-                           const gfft_iodim *planes, int cols_first, int in_blocks, int64_t in_block_stride,
-                           int out_blocks, int64_t out_block_stride) {
-  if (!plan || !cols || !rows || !planes) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  if (kind != GFFT_C2C_FORWARD && kind != GFFT_C2C_BACKWARD) return fail(GFFT_ERR_UNSUPPORTED, "guru plans are complex-to-complex");
-  const int64_t n1 = cols->n, n2 = rows->n, np = planes->n;
-  if (n1 < 1 || n2 < 1 || np < 1) return fail(GFFT_ERR_INVALID, "bad length");
-  if (rows->is != 1 || rows->os != 1) return fail(GFFT_ERR_UNSUPPORTED, "the row axis must be contiguous on both sides");
-  if (in_blocks < 1 || out_blocks < 1) return fail(GFFT_ERR_INVALID, "bad block count");
-  if (in_blocks > 1 && out_blocks > 1) return fail(GFFT_ERR_UNSUPPORTED, "blocks on one side only");
-  int rc = check_device();
-  if (rc) return rc;
-  if (!regk_ok(n1, precision) || !regk_ok(n2, precision) || mixv_supported((int)n1))
-    return fail(GFFT_ERR_UNSUPPORTED, "no single-pass register kernel for one of the lengths");
-  for (int nb_ : {in_blocks, out_blocks}) {
-    const int max_blocks = is_pow2(n1) ? (n1 >= 32 ? 8 : 4) : 4;           // whole thread slots per block (gfft_plan_set_split)
-    if ((nb_ & (nb_ - 1)) || nb_ > max_blocks || n1 % nb_) return fail(GFFT_ERR_UNSUPPORTED, "block count not supported for this length");
-  }
-  if ((double)np * (double)n1 >= 2147483648.0 || (double)np * (double)n2 >= 2147483648.0) return fail(GFFT_ERR_UNSUPPORTED, "batch exceeds 2^31");
-  const int64_t esz = 2 * (int64_t)precision;
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = 0;
-  pl->kind = kind;
-  pl->precision = precision;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-  bool fused = false;
-  rc = build_pair2d(pl, cols, n2, planes, kind == GFFT_C2C_BACKWARD, cols_first, in_blocks, in_block_stride, out_blocks, out_block_stride, false, &fused);
-  if (rc) { delete pl; return rc; }
-  pl->passes.back().carries_scale = true;
-  const double elems = (double)np * (double)n1 * (double)n2;
-  pl->flops = 5.0 * elems * std::log2((double)n1 * (double)n2);
-  pl->bytes = 4.0 * elems * (double)esz;
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-/* The two local stages of a REAL slab-decomposed transform as one plan (see include/gfft.h). */
-int gfft_plan_create_guru2_real(gfft_plan *plan, int precision, int kind, const gfft_iodim *cols, const gfft_iodim *rows,
-                                const gfft_iodim *planes, int in_blocks, int64_t in_block_stride, int out_blocks,
-                                int64_t out_block_stride) {
-  if (!plan || !cols || !rows || !planes) return fail(GFFT_ERR_INVALID, "null argument");
-  *plan = nullptr;
-  if (precision != GFFT_F32 && precision != GFFT_F64) return fail(GFFT_ERR_INVALID, "precision must be 4 or 8");
-  if (kind != GFFT_R2C && kind != GFFT_C2R) return fail(GFFT_ERR_UNSUPPORTED, "guru2_real plans are r2c / c2r (complex pairs: gfft_plan_create_guru2)");
-  const bool inverse = kind == GFFT_C2R;
-  const int64_t n1 = cols->n, n2 = rows->n, np = planes->n;
-  if (n1 < 1 || n2 < 1 || np < 1) return fail(GFFT_ERR_INVALID, "bad length");
-  if (rows->is != 1 || rows->os != 1) return fail(GFFT_ERR_UNSUPPORTED, "the row axis must be contiguous on both sides");
-  if (cols->is < 1 || cols->os < 1 || planes->is < 1 || planes->os < 1) return fail(GFFT_ERR_INVALID, "strides must be positive");
-  if (in_blocks < 1 || out_blocks < 1) return fail(GFFT_ERR_INVALID, "bad block count");
-  if ((inverse ? out_blocks : in_blocks) > 1) return fail(GFFT_ERR_INVALID, "blocks on the half-spectrum side only (R2C: output, C2R: input)");
-  // the two sides in their own elements: reals on the real side, complex entries on the half-spectrum side
-  const int64_t H = n2 / 2 + 1;
-  const int64_t re_es = inverse ? cols->os : cols->is, re_plane = inverse ? planes->os : planes->is;
-  const int64_t cx_es = inverse ? cols->is : cols->os, cx_plane = inverse ? planes->is : planes->os;
-  const int nb = inverse ? in_blocks : out_blocks;
-  const int64_t bstride = inverse ? in_block_stride : out_block_stride;
-  if (re_es < n2 || cx_es < H) return fail(GFFT_ERR_INVALID, "rows of a plane overlap (row stride below the row's length)");
-  if (nb > 1 && n1 % nb == 0 && bstride < (n1 / nb) * cx_es) return fail(GFFT_ERR_INVALID, "block stride smaller than the block's extent");
-  int rc = check_device();
-  if (rc) return rc;
-  if (n2 % 2 || n2 / 2 > 4096 || !real_half_supported((int)(n2 / 2)) || !regk_ok(n1, precision) || mixv_supported((int)n1))
-    return fail(GFFT_ERR_UNSUPPORTED, "no single-pass register kernel for one of the lengths");
-  const int max_blocks = is_pow2(n1) ? (n1 >= 32 ? 8 : 4) : 4;            // whole thread slots per block (gfft_plan_set_split)
-  if ((nb & (nb - 1)) || nb > max_blocks || n1 % nb) return fail(GFFT_ERR_UNSUPPORTED, "block count not supported for this length");
-  if (re_es % 2 || re_plane % 2) return fail(GFFT_ERR_UNSUPPORTED, "real-side strides must be even (rows are read as complex pairs)");
-  if ((double)np * (double)n1 >= 2147483648.0 || (double)np * (double)H >= 2147483648.0) return fail(GFFT_ERR_UNSUPPORTED, "batch exceeds 2^31");
-  gfft_plan_s *pl = new gfft_plan_s;
-  pl->ndims = 0;
-  pl->kind = kind;
-  pl->precision = precision;
-  pl->variant_rows = opts().variant_rows;
-  pl->variant_cols = opts().variant_cols;
-  pl->mixv_variant = opts().mixv_variant;
-  pl->xcd_swizzle = opts().xcd_swizzle;
-  rc = build_pair2d_real(pl, n1, n2, np, re_es, re_plane, cx_es, cx_plane, nb, bstride, inverse);
-  if (rc) { delete pl; return rc; }
-  *plan = pl;
-  ++g_live_plans;
-  return GFFT_OK;
-}
-
-/* Tile-major layouts of exchange buffers (see include/gfft.h). */
-int gfft_plan_set_tiles(gfft_plan pl, int side, int tile, int64_t tile_stride) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (side != 0 && side != 1) return fail(GFFT_ERR_INVALID, "side must be 0 (input) or 1 (output)");
-  if (pl->passes.size() != 1 || pl->fused3) return fail(GFFT_ERR_UNSUPPORTED, "tile-major layouts: single-pass plans only");
-  Pass &p = pl->passes[0];
-  if (p.kind != PK_FFT || !p.regk || p.d.mode != MODE_C2C || p.d.tw_hi || p.d.tr_dir || mixv_supported(p.d.n))
-    return fail(GFFT_ERR_UNSUPPORTED, "tile-major layouts: plain complex register-kernel passes only");
-  int lg = 0;
-  while ((1 << lg) < tile) ++lg;
-  if (tile < 0 || (tile > 0 && ((1 << lg) != tile || tile < 2 || tile_stride < tile)))
-    return fail(GFFT_ERR_INVALID, "tile must be a power of two >= 2 (0 switches the layout off)");
-  PassDesc &d = p.d;
-  if (p.cols) {
-    // the adjacent columns (innermost batch dim) are tile-major
-    if (side == 0) { d.in_ilg = tile ? lg : 0; d.in_iS = tile ? tile_stride : 0; }
-    else { d.out_ilg = tile ? lg : 0; d.out_iS = tile ? tile_stride : 0; }
-    return GFFT_OK;
-  }
-  // ROWS: the transformed axis itself is tile-major; thread slots advance by NT entries, which must be
-  // whole tiles, and blocks must be whole tiles too
-  const int64_t n = d.n;
-  const int nb = p.blocks[side];
-  if (tile) {
-    const int nt = pow2_rows_nt(n, pl->precision);
-    if (!nt || nt % tile || (n / nb) % tile)
-      return fail(GFFT_ERR_UNSUPPORTED, "tile-major rows: the line's thread layout does not advance by whole tiles");
-  }
-  const int64_t es = 1;
-  const int64_t per = n / nb;
-  const int64_t span = tile ? (per / tile) * tile_stride : per * es;     // what one block advances the address by
-  const int64_t jump = nb > 1 ? p.bstride[side] - span : 0;
-  if (side == 0) { d.in_tlg = tile ? lg : 0; d.in_tS = tile ? tile_stride : 0; d.in_jump = jump; }
-  else { d.out_tlg = tile ? lg : 0; d.out_tS = tile ? tile_stride : 0; d.out_jump = jump; }
-  return GFFT_OK;
-}
-
-int gfft_plan_set_flat(gfft_plan pl, int64_t body_width, int64_t tail_offset, int64_t tail_row_stride) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (pl->passes.size() != 1 || pl->fused3) return fail(GFFT_ERR_UNSUPPORTED, "flat tiles: single-pass plans only");
-  Pass &p = pl->passes[0];
-  if (p.kind != PK_FFT || !p.regk || !p.cols || p.d.mode != MODE_C2C || p.d.tw_hi || p.d.tr_dir)
-    return fail(GFFT_ERR_UNSUPPORTED, "flat tiles: plain complex strided register-kernel passes only");
-  if (body_width < 0 || body_width > p.d.inner) return fail(GFFT_ERR_INVALID, "body width must lie in 0 .. columns per row");
-  p.d.flat = 1;
-  p.d.fl_bw = (body_width > 0 && body_width < p.d.inner) ? body_width : 0;
-  p.d.fl_tail = tail_offset;
-  p.d.fl_tail_ms = tail_row_stride;
-  return GFFT_OK;
-}
-
-int gfft_plan_set_split_slabs(gfft_plan pl, int side, int nblocks, int64_t rows_per_slab, int tile) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (pl->passes.size() != 1 || pl->axes.size() != 1 || pl->fused3)
-    return fail(GFFT_ERR_UNSUPPORTED, "split layouts fuse into single-pass plans only");
-  Pass &p = pl->passes[0];
-  if (!((p.d.mode == MODE_R2C_H && side == 1) || (p.d.mode == MODE_C2R_H && side == 0)))
-    return fail(GFFT_ERR_UNSUPPORTED, "slab-wise split: the half-spectrum side of packed-real rows only");
-  // Every failure below leaves the plan as it was; a repeated call starts from the natural row strides again (the
-  // slab form multiplies them), and one block switches the slab form off altogether.
-  const PassDesc saved = p.d;
-  auto bail = [&](int code, const char *msg) { p.d = saved; return fail(code, msg); };
-  if (p.d.ub_n1 > 0) {
-    p.d.inner = 1;
-    p.d.in_os = p.d.in_is;   p.d.in_is = 1;
-    p.d.out_os = p.d.out_is; p.d.out_is = 1;
-    p.d.ub_n1 = 0;
-    p.d.ub_tlg = 0;
-  }
-  if (p.d.tr_dir || p.d.mid != 1 || p.d.inner != 1) return bail(GFFT_ERR_UNSUPPORTED, "slab-wise split: plain packed-real rows only");
-  int lg = 0;
-  while ((1 << lg) < tile) ++lg;
-  if (tile < 2 || (1 << lg) != tile) return bail(GFFT_ERR_INVALID, "tile must be a power of two >= 2");
-  if (rows_per_slab < 1 || p.d.batch % rows_per_slab) return bail(GFFT_ERR_INVALID, "rows per slab must divide the number of rows");
-  // (the kernels address this layout with 32-bit element offsets)
-  if ((double)p.d.batch * ((double)p.d.n + 1.0) >= 2147483648.0) return bail(GFFT_ERR_UNSUPPORTED, "slab-wise split: buffer beyond 2^31 entries");
-  int rc = gfft_plan_set_split(pl, side, nblocks);
-  if (rc) { p.d = saved; return rc; }
-  if (nblocks == 1) return GFFT_OK;
-  PassDesc &d = p.d;
-  // rows of the batch as (slab, row in slab): the kernel's (o, i) indices
-  d.inner = rows_per_slab;
-  d.in_is = d.in_os;   d.in_os *= rows_per_slab;
-  d.out_is = d.out_os; d.out_os *= rows_per_slab;
-  d.ub_n1 = rows_per_slab;
-  d.ub_tlg = lg;
-  for (int b = 0; b < 8; ++b) d.ub_base[b] = b < nblocks ? d.ub_rows * (int64_t)d.ub_start[b] : 0;
-  return GFFT_OK;
-}
-
-/* free the shared scratch buffers (they are otherwise kept for the life of the process) */
-int gfft_scratch_release(void) { return scratch_pool().release(true); }
-
-/* Did a fused launch of ANY plan give up a wait since the last look?  GFFT_OK, or GFFT_ERR_VOIDED once per event with the plan
- * named in gfft_last_error().  Does not synchronise: call it after the stream (or device) has been synchronised to learn
- * whether the results that synchronisation waited for are valid (include/gfft.h). */
-int gfft_async_error(void) { return poll_async_error(nullptr); }
-int gfft_plan_status(gfft_plan pl) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  return poll_async_error(pl);
-}
-
-int gfft_plan_destroy(gfft_plan pl) {
-  if (!pl) return GFFT_OK;
-  delete pl;
-  if (--g_live_plans == 0) (void)scratch_pool().release(false);
-  return GFFT_OK;
-}
-
-int gfft_plan_describe(gfft_plan pl, char *buf, size_t len) {
-  if (!pl || !buf || !len) return fail(GFFT_ERR_INVALID, "null argument");
-  std::string s;
-  char line[256];
-  const char *kn = pl->kind == GFFT_C2C_FORWARD ? "c2c-forward" : pl->kind == GFFT_C2C_BACKWARD ? "c2c-backward"
-                   : pl->kind == GFFT_R2C ? "r2c" : "c2r";
-  char sched[96] = "";
-  if (pl->fused3 && pl->ws_tile) snprintf(sched, sizeof sched, " [3-D schedule: tile-major workspace, tiles of %d columns]", pl->ws_tile);
-  else if (pl->fused3) snprintf(sched, sizeof sched, " [3-D schedule: padded-pitch workspace, rows %lld entries apart]", (long long)pl->ws_pitch);
-  snprintf(line, sizeof line, "gfft plan: %s %s, %d dims, %zu passes%s\n", kn, pl->precision == 8 ? "f64" : "f32",
-           pl->ndims, pl->passes.size(), sched);
-  s += line;
-  static const char *bufn[] = {"IN", "OUT", "WS", "FS", "AUX", "RING", "FS2"};
-  for (const Pass &p : pl->passes) {
-    if (p.kind == PK_FUSED2) {
-      const char *fk = kFusedKinds[p.fused_kind].describe_name;
-      if (pl->fused_off)
-        snprintf(line, sizeof line, "  pair (%s) n=%d then n=%d as two stand-alone passes (a fused launch gave up a wait)%s  %s -> %s\n",
-                 fk, p.d.n, p.d2.n, p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
-      else
-      snprintf(line, sizeof line, "  fused pair (%s) n=%d then n=%d: %d planes, %d + %d tiles per plane, ring of %d slots x %lld KiB, one persistent launch%s  %s -> %s\n",
-               fk, p.d.n, p.d2.n, p.fused.planes, p.fused.tiles_a, p.fused.tiles_b, p.fused.ring,
-               (long long)(p.fused.slot_bytes >> 10), p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
-      s += line;
-      continue;
-    }
-    if (p.kind == PK_PLANE2D) {
-      snprintf(line, sizeof line, "  planes on chip: rows n=%d then columns n=%d of %d planes held in LDS, one launch%s  %s -> %s\n", p.d.n, p.d2.n,
-               p.fused.planes, p.carries_scale ? " [scale]" : "", bufn[p.src], bufn[p.dst]);
-      s += line;
-      continue;
-    }
-    if (p.kind != PK_FFT) {
-      static const char *kinds[] = {"", "embed (chirp/zero-pad into AUX)", "multiply by B = FFT(chirp)", "extract (chirp, scale)"};
-      snprintf(line, sizeof line, "  %s n=%lld Lw=%lld  %s -> %s\n", kinds[p.kind], (long long)p.pt.n,
-               (long long)p.pt.Lw, bufn[p.src], bufn[p.dst]);
-      s += line;
-      continue;
-    }
-    snprintf(line, sizeof line, "  n=%d batch=%lld (mid=%lld inner=%lld) es_in=%lld es_out=%lld kernel=%s%s%s  %s -> %s\n",
-             p.d.n, (long long)p.d.batch, (long long)p.d.mid, (long long)p.d.inner, (long long)p.d.in_es,
-             (long long)p.d.out_es,
-             (p.d.mode == MODE_R2C_H || p.d.mode == MODE_C2R_H) ? "regs-rows packed-real (n = complex length)"
-             : p.regk ? (p.cols ? "regs-cols" : "regs-rows") : "generic",
-             p.d.tw_hi ? " [four-step 1/2, fused twiddle]" : "", p.carries_scale ? " [scale]" : "",
-             bufn[p.src], bufn[p.dst]);
-    s += line;
-  }
-  snprintf(buf, len, "%s", s.c_str());
-  return GFFT_OK;
-}
-
-int gfft_plan_cost(gfft_plan pl, double *flops, double *bytes, int *launches) {
-  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
-  if (flops) *flops = pl->flops;
-  if (bytes) *bytes = pl->bytes;
-  if (launches) *launches = (int)pl->passes.size();
-  return GFFT_OK;
-}
-
-static int collapse(int ndims, const int64_t *shape, int axis, int64_t *outer, int64_t *naxis, int64_t *inner) {
-  if (!shape || ndims < 1 || axis < 0 || axis >= ndims) return fail(GFFT_ERR_INVALID, "bad shape/axis");
-  *outer = *inner = 1;
-  for (int i = 0; i < axis; ++i) *outer *= shape[i];
-  for (int i = axis + 1; i < ndims; ++i) *inner *= shape[i];
-  *naxis = shape[axis];
-  return GFFT_OK;
-}
-
-int gfft_pack(const void *d_array, void *d_packed, int ndims, const int64_t *shape, int axis, int nparts,
-              int itemsize, void *stream) {
-  int64_t o, n, i;
-  int rc = collapse(ndims, shape, axis, &o, &n, &i);
-  if (rc) return rc;
-  if (nparts < 1 || n < nparts) return fail(GFFT_ERR_INVALID, "axis shorter than the number of parts");
-  if ((rc = check_device())) return rc;
-  HIP_TRY(launch_pack(d_array, d_packed, o, n, i, nparts, itemsize, false, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_unpack(const void *d_packed, void *d_array, int ndims, const int64_t *shape, int axis, int nparts,
-                int itemsize, void *stream) {
-  int64_t o, n, i;
-  int rc = collapse(ndims, shape, axis, &o, &n, &i);
-  if (rc) return rc;
-  if (nparts < 1 || n < nparts) return fail(GFFT_ERR_INVALID, "axis shorter than the number of parts");
-  if ((rc = check_device())) return rc;
-  HIP_TRY(launch_pack(d_packed, d_array, o, n, i, nparts, itemsize, true, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_truncate(const void *d_padded, void *d_trunc, int ndims, const int64_t *shape_padded, int axis,
-                  int64_t n_trunc, int is_real, int precision, double scale, void *stream) {
-  int64_t o, n, i;
-  int rc = collapse(ndims, shape_padded, axis, &o, &n, &i);
-  if (rc) return rc;
-  if (n_trunc < 1 || n_trunc > n) return fail(GFFT_ERR_INVALID, "bad truncated length");
-  if ((rc = check_device())) return rc;
-  HIP_TRY(launch_trunc(d_padded, d_trunc, o, n, n_trunc, i, is_real, precision, scale, false, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_pad(const void *d_trunc, void *d_padded, int ndims, const int64_t *shape_padded, int axis,
-             int64_t n_trunc, int is_real, int precision, void *stream) {
-  int64_t o, n, i;
-  int rc = collapse(ndims, shape_padded, axis, &o, &n, &i);
-  if (rc) return rc;
-  if (n_trunc < 1 || n_trunc > n) return fail(GFFT_ERR_INVALID, "bad truncated length");
-  if ((rc = check_device())) return rc;
-  HIP_TRY(launch_trunc(d_trunc, d_padded, o, n, n_trunc, i, is_real, precision, 1.0, true, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(launch_scale(d_data, count, precision, scale, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-int gfft_malloc(void **d_ptr, size_t bytes) {
-  int rc = check_device();
-  if (rc) return rc;
-  hipError_t e = hipMalloc(d_ptr, bytes);
-  if (e == hipErrorOutOfMemory) return fail(GFFT_ERR_NOMEM, "hipMalloc: out of memory");
-  HIP_TRY(e);
-  return GFFT_OK;
-}
-int gfft_free(void *d_ptr) { HIP_TRY(hipFree(d_ptr)); return GFFT_OK; }
-int gfft_memcpy_h2d(void *d, const void *h, size_t n, void *s) { HIP_TRY(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, (hipStream_t)s)); return GFFT_OK; }
-int gfft_memcpy_d2h(void *h, const void *d, size_t n, void *s) { HIP_TRY(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, (hipStream_t)s)); return GFFT_OK; }
-int gfft_memcpy_d2d(void *d, const void *s_, size_t n, void *s) { HIP_TRY(hipMemcpyAsync(d, s_, n, hipMemcpyDeviceToDevice, (hipStream_t)s)); return GFFT_OK; }
-int gfft_stream_synchronize(void *s) { HIP_TRY(hipStreamSynchronize((hipStream_t)s)); return GFFT_OK; }
-
-int gfft_event_create(void **event) {
-  int rc = check_device();
-  if (rc) return rc;
-  hipEvent_t e;
-  HIP_TRY(hipEventCreate(&e));
-  *event = e;
-  return GFFT_OK;
-}
-int gfft_event_record(void *event, void *stream) { HIP_TRY(hipEventRecord((hipEvent_t)event, (hipStream_t)stream)); return GFFT_OK; }
-int gfft_event_elapsed_ms(void *start, void *stop, float *ms) {
-  HIP_TRY(hipEventSynchronize((hipEvent_t)stop));
-  HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
-  return GFFT_OK;
-}
-int gfft_event_destroy(void *event) { HIP_TRY(hipEventDestroy((hipEvent_t)event)); return GFFT_OK; }
-
-/* developer probe: run ONE power-of-two pass with explicit batch geometry and strides
- * (element units), bypassing the planner.  geom = {n, outer, mid, inner, in_os, in_ms, in_is,
- * in_es, out_os, out_ms, out_is, out_es}.  Not part of the drop-in boundary. */
-int gfft_debug_pass(const int64_t *geom, int precision, int cols, int variant, int inverse,
-                    const void *d_in, void *d_out, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  PassDesc d{};
-  d.n = (int)geom[0];
-  d.mode = MODE_C2C;
-  d.conj_in = d.conj_out = inverse;
-  d.mid = geom[2];
-  d.inner = geom[3];
-  d.batch = geom[1] * geom[2] * geom[3];
-  d.in_os = geom[4]; d.in_ms = geom[5]; d.in_is = geom[6]; d.in_es = geom[7];
-  d.out_os = geom[8]; d.out_ms = geom[9]; d.out_is = geom[10]; d.out_es = geom[11];
-  d.scale = 1.0;
-  d.flat = opts().debug_flat;
-  d.swizzle = opts().xcd_swizzle > 0 ? 1 : 0;
-  if (!cols && (opts().debug_tile_side & 1)) { d.in_tlg = opts().debug_tile_lg; d.in_tS = opts().debug_tile_stride; }
-  if (!cols && (opts().debug_tile_side & 2)) { d.out_tlg = opts().debug_tile_lg; d.out_tS = opts().debug_tile_stride; }
-  rc = get_twiddles(d.n, precision, &d.tw);
-  if (rc) return rc;
-  hipError_t e = precision == 8 ? launch_pow2_f64(d, cols != 0, variant, d_in, d_out, (hipStream_t)stream)
-                                : launch_pow2_f32(d, cols != 0, variant, d_in, d_out, (hipStream_t)stream);
-  HIP_TRY(e);
-  return GFFT_OK;
-}
-
-int gfft_probe_copy(const void *d_src, void *d_dst, size_t bytes, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(launch_copy(d_src, d_dst, bytes, (hipStream_t)stream));
-  return GFFT_OK;
-}
-int gfft_probe_tile_copy(const void *d_src, void *d_dst, int64_t outer, int64_t n, int64_t inner, int tcols, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
-  HIP_TRY(launch_tile_copy(d_src, d_dst, outer, n, inner, tcols, (hipStream_t)stream));
-  return GFFT_OK;
-}
-
-}  // extern "C"
+}  // namespace gfft

@@ -234,7 +234,7 @@ def test_single_rank_3d_schedule_vs_oracle(shape, dt):
 # C3 (512^3 complex128 on 2 ranks, slab) and C4 (1024^3 complex128 on 8 ranks: pencil grid (4,2,1), and the slab
 # grid (8,1,1)) fit one 288 GB device with every rank a thread and tests/fake_rccl as the wire.  What this catches
 # before the first real multi-GPU run: 32-bit offsets, pitches and chunk plans at the real sizes of every stage
-# (csrc/plan.cpp refuses a side beyond 2^31 elements: none of the stages here may hit that).  The reference runs its
+# (csrc/api.cpp refuses a side beyond 2^31 elements: none of the stages here may hit that).  The reference runs its
 # distributed tests the same way at 2 and 4 ranks, tests/runtests.sh:21-36, tests/test_mpifft.py:144-177.
 def _line_partial(x, start, k0, k1, n0, n1):
     """sum over the LOCAL (i0, i1) of x[i0, i1, :] e^{-2 pi i (k0 I0 / n0 + k1 I1 / n1)}, I = global indices: this

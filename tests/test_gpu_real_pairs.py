@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 from tests import cases
 from oracle import pfft_oracle as O
 
-KINDS_DEFAULT = 2046              # every pair kind but bit 1 (plan.cpp Options::fuse2_kinds)
+KINDS_DEFAULT = 2046              # every pair kind but bit 1 (plan_internal.h Options::fuse2_kinds)
 REAL_SLAB_BITS = 512 | 1024       # FUSED_R2C_PLANES_B, FUSED_COLS_C2R_B
 
 

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""What the planner decides, as text: for a fixed list of requests -- the shapes of the fused pairs and their neighbours, once under
+"""What the planner decides, as text: for a fixed list of requests -- the shapes of the fused pairs and their neighbours, and a few
+small requests through every other plan creator (guru, padded, r2r, one line per family of lengths) --, once under
 the defaults and once under each planning option that switches a pair -- gfft_plan_describe, every pass's name and bytes
 (gfft_plan_pass_info) and gfft_plan_cost; under an option, only the requests that come out other than under the defaults are
 printed.  Plans are created and destroyed, nothing is allocated or executed: seconds on a GPU.
-Two builds whose outputs are identical plan identically: what a refactor of plan.cpp / the pair tables has to show.
+Two builds whose outputs are identical plan identically: what a refactor of plan.cpp / api.cpp / the pair tables has to show.
 --brief: one line per request instead -- its passes under the defaults, a digest (sha256, 12 digits) of the full text above, and
 the digest under every option that changes it: the form that is kept under profiles/.
 usage: plan_fingerprint.py [--brief] > out.txt   (GFFT_AB_LIB=<file next to libgfft.so>: under that build of the library)"""
@@ -76,6 +77,27 @@ def requests():
                 yield ('guru2_real c2r f%d %dx%d blocks %d' % (8 * prec, n1, n2, blocks),
                        lambda n1=n1, n2=n2, H=H, blocks=blocks, E=E, bs=bs:
                        eng.plan_create_guru2_real(prec, C2R, (n1, H, n2), (n2, 1, 1), (planes, E, n1 * n2), blocks, bs, 1, 0))
+        # every other creator, small: strided batched lines (64 lines, blocks laid out as gfft_pack does), one of them truncating
+        for n, keep in ((16, 0), (48, 0), (48, 32), (64, 0), (1024, 0)):
+            for inb, outb in ((1, 1), (4, 1), (1, 4)):
+                yield ('guru %+d f%d n=%d keep=%d blocks %d -> %d' % (FWD, 8 * prec, n, keep, inb, outb),
+                       lambda n=n, keep=keep, inb=inb, outb=outb:
+                       eng.plan_create_guru(prec, FWD, (n, 1, 1), [(64, n // inb, (keep or n) // outb)], inb, 64 * (n // inb),
+                                            outb, 64 * ((keep or n) // outb), keep))
+        # ... the padded (3/2-rule) 3-D transform above the size where the workspace schedule starts, complex and real
+        for kind in (FWD, BWD):
+            yield 'padded c2c %+d f%d 192^3 keep 128^3' % (kind, 8 * prec), lambda kind=kind: eng.plan_create_padded((192,) * 3, (128,) * 3, kind, prec)
+        for kind in (R2C, C2R):
+            yield 'padded %s f%d 384^3 keep (256, 256, 129)' % ('r2c' if kind == R2C else 'c2r', 8 * prec), \
+                lambda kind=kind: eng.plan_create_padded((384,) * 3, (256, 256, 129), kind, prec)
+        # ... the eight real-to-real kinds (REDFT00 = 3 ... RODFT11 = 10) on a one-pass logical length and off it
+        for n in (16, 17):
+            for kind in range(3, 11):
+                yield 'r2r kind %d f%d (8, %d)' % (kind, 8 * prec, n), lambda n=n, kind=kind: eng.plan_create_r2r((8, n), (1,), (kind,), prec)
+        # ... and one line length per family of plan_line: 2^k, 3 x 2^k, 7-smooth in one pass, small primes (generic), four-step
+        # (2^20 and 3 x 2^18), a prime (Bluestein)
+        for n in (1024, 768, 896, 1001, 1 << 20, 3 << 18, 1009):
+            yield 'c2c %+d f%d (4, %d) axes (1,)' % (FWD, 8 * prec, n), lambda n=n: eng.plan_create((4, n), (4, n), (1,), FWD, prec)
 
 
 brief = '--brief' in sys.argv[1:]
