@@ -31,9 +31,10 @@ def rounding_tol(dt, nelem, factor=2.0):
     (north_star: 1e-10 round trip / 2e-10 forward in fp64; 1e-4 / 2e-4 in fp32) are 10^3 ... 10^5 times looser: a kernel
     that lost three digits would pass them.  The reference's own serial tests ask for the same level
     (/root/reference/tests/test_libfft.py:17, abstol f = 5e-5, d = 1e-14 on O(1) data).
-    Three transform families are held to it, each with an impulse family of its own beside the random-data comparisons: complex
-    (`impulse_errors`), real r2c / c2r (`real_impulse_errors`) and real-to-real DCT / DST (`r2r_impulse_errors`; there `nelem`
-    counts the LOGICAL points N = 2 (n -+ 1) or 2 n of the complex transform a kind runs on, tests/test_gpu_r2r.py)."""
+    Four families are held to it, each with an impulse family of its own beside the random-data comparisons: complex
+    (`impulse_errors`), real r2c / c2r (`real_impulse_errors`), real-to-real DCT / DST (`r2r_impulse_errors`; there `nelem`
+    counts the LOGICAL points N = 2 (n -+ 1) or 2 n of the complex transform a kind runs on, tests/test_gpu_r2r.py) and the
+    3/2-rule truncating store / zero-padding load (`trunc_impulse_errors`; `nelem` is the PADDED length of the line)."""
     return factor * EPS[dt] * max(1.0, float(np.log2(max(2.0, float(nelem)))))
 
 
@@ -496,6 +497,201 @@ def r2r_path(describe, N, mapping):
     assert len(passes) == 1 and ' n=%d ' % N in passes[0], text
     assert ('kernel=regs-rows' if mapping == 'rows' else 'kernel=regs-cols') in passes[0], text
     return 'adapter'
+
+
+# ---- the 3/2-rule family: truncating store (forward) / zero-padding load (backward), libfft.py:263-311 of the model ----
+# padded (transformed) length n -> kept length (complex entries N of a complex axis; REAL points of a real axis, of which
+# m = kept // 2 + 1 half-spectrum entries are stored), by the path plan.cpp fused_pad_ok gives the plan in the shipped build
+TRUNC_LENGTHS = {'fused pow2': [(64, 32), (64, 43), (1024, 512), (1024, 683), (4096, 2731)],
+                 'fused 3^b 2^k': [(48, 32), (48, 31), (96, 64), (768, 512), (1536, 1024), (3072, 2048)],
+                 'fused unequal-width': [(240, 160), (240, 161), (672, 448), (960, 640), (3600, 2400)],
+                 'stand-alone': [(40, 27), (80, 63), (1000, 667), (112, 75), (1792, 1195), (18, 12), (27, 18), (343, 229), (8192, 5461),
+                                 (521, 347)]}
+TRUNC_CASES = [(n, kept, family) for family, pairs in TRUNC_LENGTHS.items() for n, kept in pairs]
+TRUNC_MAPPINGS = R2R_MAPPINGS
+
+
+def trunc_entries(n, kept, real):
+    """(entries stored along the axis, entries of the full spectrum): N of n for a complex axis, m = kept // 2 + 1 of
+    n // 2 + 1 for a real one.  The two agree when nothing is cut (kept == n): the exact answers below are then those of the
+    plain transform -- no fold, no halving --, which is what the probe sets beside the padded plans."""
+    return (kept // 2 + 1, n // 2 + 1) if real else (kept, n)
+
+
+def _cis(m, n, sign):
+    """exp(sign 2 pi i m / n) in long double, the integer array m reduced modulo n first."""
+    ld = np.longdouble
+    th = (ld(8) * np.arctan(ld(1))) * (np.asarray(m, dtype=np.int64) % n).astype(ld) / ld(n)
+    return np.cos(th) + (1j * sign) * np.sin(th)
+
+
+def _kappa(keep):
+    k = np.arange(keep, dtype=np.int64)
+    return np.where(k <= keep // 2, k, k - keep)
+
+
+def trunc_exact_forward(n, keep, j, real):
+    """The `keep` entries a truncating forward transform of padded length n stores for the unit impulse at j, unnormalised.
+      complex   T[k] = exp(-2 pi i j kap(k) / n), kap(k) = k for k <= h = keep // 2, else k - keep; for an even keep the upper
+                band's first entry n - h folds onto h: T[h] = 2 cos(2 pi j h / n)
+      real      T[k] = exp(-2 pi i j k / n), k < keep = m; for an even m, T[m - 1] = 2 Re(...), imaginary part exactly 0
+    (the parity rule is on the TRUNCATED array's length, libfft.py:267 -- for a real axis that is m, not the real length).
+    Long double, integer phase products reduced modulo n first; returned as complex128.  tests/test_trunc_exact_host.py
+    holds these against the float64 oracle."""
+    j = int(j)
+    full = n // 2 + 1 if real else n
+    assert 0 <= j < n and 1 <= keep <= full, (n, keep, j)
+    cut = keep < full
+    if real:
+        T = _cis(j * np.arange(keep, dtype=np.int64), n, -1)
+        if cut and keep % 2 == 0:
+            T[keep - 1] = 2 * T[keep - 1].real
+    else:
+        T = _cis(j * _kappa(keep), n, -1)
+        if cut and keep % 2 == 0:
+            T[keep // 2] = 2 * T[keep // 2].real
+    return np.asarray(T, dtype=np.complex128)
+
+
+def trunc_exact_backward(n, keep, kb, a, real):
+    """The n points a zero-padding backward transform gives for ONE stored bin kb of amplitude a, unnormalised.
+      complex   x[j] = a exp(+2 pi i j kap(kb) / n); for an even keep and kb == h, x[j] = a cos(2 pi j h / n) (both copies halved)
+      real      kb = 0: Re(a);  even m and kb = m - 1: Re(a) cos(2 pi j kb / n) -- a = i gives zeros --;  otherwise
+                2 Re(a exp(+2 pi i j kb / n))
+    With nothing cut (keep is the full length) the plain backward transform: Re(a) (-1)^j at the Nyquist bin of an even n."""
+    kb = int(kb)
+    full = n // 2 + 1 if real else n
+    assert 0 <= kb < keep <= full, (n, keep, kb)
+    cut = keep < full
+    j = np.arange(n, dtype=np.int64)
+    a = complex(a)
+    if real:
+        w = _cis(j * kb, n, +1)
+        if kb == 0:
+            x = np.full(n, a.real, dtype=np.longdouble)
+        elif (cut and keep % 2 == 0 and kb == keep - 1) or (not cut and 2 * kb == n):
+            x = a.real * w.real
+        else:
+            x = 2 * (a.real * w.real - a.imag * w.imag)
+        return np.asarray(x, dtype=np.float64)
+    w = _cis(j * int(_kappa(keep)[kb]), n, +1)
+    if cut and keep % 2 == 0 and kb == keep // 2:
+        w = w.real + 0j
+    return np.asarray(np.clongdouble(a) * w, dtype=np.complex128)
+
+
+def trunc_bins(keep, real):
+    """The bins of the backward lines, (kb, a) per line: complex 0, 1, 2, h - 1, h, h + 1 (first of the upper band), N - 2,
+    N - 1 with a = 1 and again with a = i, then N // 3 + 1 for every further line; real 0, 1, 2, 3, m // 2, m - 3, m - 2, m - 1
+    with a = 1 and with a = i, cyclically."""
+    if real:
+        bins = [0, 1, 2, 3, keep // 2, keep - 3, keep - 2, keep - 1]
+    else:
+        h = keep // 2
+        bins = [0, 1, 2, h - 1, h, h + 1, keep - 2, keep - 1]
+    assert all(0 <= k < keep for k in bins), (keep, real, bins)
+    return [(k, 1.0) for k in bins] + [(k, 1j) for k in bins]
+
+
+def trunc_impulse_lines(n, kept, real, lines):
+    """The family as (lines, length) arrays, one line per row: x (impulses, n) and its exact truncated transform wf (keep);
+    spec (one bin per line, keep) and its exact padded backward transform wb (n); the peaks (pf, pb) errors are taken
+    relative to -- 2 where a fold or a 2 Re occurs in the answer, else 1."""
+    keep, full = trunc_entries(n, kept, real)
+    pos = r2r_positions(n)
+    spikes = trunc_bins(keep, real)
+    x = np.zeros((lines, n), dtype='d' if real else 'D')
+    wf = np.empty((lines, keep), dtype='D')
+    spec = np.zeros((lines, keep), dtype='D')
+    wb = np.empty((lines, n), dtype='d' if real else 'D')
+    ef, eb = {}, {}
+    for b in range(lines):
+        j = pos[b % len(pos)]
+        kb, a = spikes[b % len(spikes)] if (real or b < len(spikes)) else (keep // 3 + 1, 1.0)
+        if j not in ef:
+            ef[j] = trunc_exact_forward(n, keep, j, real)
+        if (kb, a) not in eb:
+            eb[kb, a] = trunc_exact_backward(n, keep, kb, a, real)
+        x[b, j] = 1
+        wf[b] = ef[j]
+        spec[b, kb] = a
+        wb[b] = eb[kb, a]
+    pf = 2.0 if keep < full and keep % 2 == 0 else 1.0
+    pb = 2.0 if real else 1.0
+    return x, wf, spec, wb, pf, pb
+
+
+def trunc_impulse_case(n, kept, dt, mapping):
+    """The impulse family of ONE padded plan in the mapping's layout ('rows' (19, n), 'cols' (n, 19), 'middle' (3, n, 7), as
+    `r2r_impulse_case`: no batch a multiple of a kernel tile): (shape, axis, x, wf, spec, wb, pf, pb) -- x of `shape`, wf / spec
+    with `keep` entries along `axis`, wb of `shape`."""
+    real = dt in 'df'
+    shape, axis = {'rows': ((19, n), 1), 'cols': ((n, 19), 0), 'middle': ((3, n, 7), 1)}[mapping]
+    lead = shape[:axis] + shape[axis + 1:]
+    x, wf, spec, wb, pf, pb = trunc_impulse_lines(n, kept, real, int(np.prod(lead)))
+    x, wf, spec, wb = (np.ascontiguousarray(np.moveaxis(v.reshape(lead + (v.shape[-1],)), -1, axis)) for v in (x, wf, spec, wb))
+    assert x.shape == wb.shape == shape and wf.shape == spec.shape
+    return shape, axis, x, wf, spec, wb, pf, pb
+
+
+def trunc_impulse_errors(n, kept, dt, mapping, describe=None):
+    """Adapter integrity of ONE padded serial plan, FFT(shape, axis, dt, padding=n / kept), unnormalised and out of place into
+    arrays that start as NaN (an entry left unwritten shows): forward the unit impulses of `r2r_positions(n)`, backward one
+    stored bin per line (`trunc_bins`), every line against its exact answer (`trunc_exact_forward` / `trunc_exact_backward`).
+    A wrong band edge, a dropped fold or halving, parity taken from the wrong length show at full size in the one or two
+    entries they touch.  kept == n runs the unpadded plan on the same inputs.
+    Returns (forward error, backward error), each max |got - exact| over all lines relative to the exact answer's peak
+    (`trunc_impulse_lines`); `describe`, a list, receives `fft._fused_trunc` and gfft_plan_describe of the two plans."""
+    from mpi4py_fft_amd import FFT, asdevice
+    cdt = dt.upper()
+    shape, axis, x, wf, spec, wb, pf, pb = trunc_impulse_case(n, kept, dt, mapping)
+    fft = FFT(shape, axis, dtype=dt, padding=n / kept) if kept != n else FFT(shape, axis, dtype=dt)
+    assert tuple(fft.forward.output_array.shape) == wf.shape, (n, kept, dt, fft.forward.output_array.shape, wf.shape)
+    if describe is not None:
+        describe.append(bool(fft._fused_trunc))
+        describe.extend(p._eng.plan_describe(p._plan) for p in (fft.fwd, fft.bck))
+    out = asdevice(np.full(wf.shape, np.nan, dtype=cdt))
+    fft.forward(asdevice(x.astype(dt)), normalize=False, dst=out)
+    got = np.asarray(out).astype('D')
+    back = asdevice(np.full(shape, np.nan, dtype=dt))
+    fft.backward(asdevice(spec.astype(cdt)), normalize=False, dst=back)
+    gotb = np.asarray(back).astype(wb.dtype)
+    fft.destroy()
+    ef, eb = np.abs(got - wf).max() / pf, np.abs(gotb - wb).max() / pb
+    return (float('inf') if np.isnan(ef) else float(ef)), (float('inf') if np.isnan(eb) else float(eb))
+
+
+def trunc_path(describe, n, mapping):
+    """'fused' or 'stand-alone' for what `trunc_impulse_errors` left in `describe`: a fused plan pair is ONE register-kernel
+    pass each, of length n -- or n / 2, the packed-real form of contiguous real rows."""
+    fused, texts = describe[0], describe[1:]
+    if not fused:
+        return 'stand-alone'
+    for text in texts:
+        passes = [ln for ln in text.splitlines() if 'kernel=' in ln]
+        assert len(passes) == 1 and 'kernel=regs-' in passes[0], text
+        assert ' n=%d ' % (n // 2 if 'packed-real' in passes[0] else n) in passes[0], text
+        assert ('regs-rows' if mapping == 'rows' else 'regs-cols') in passes[0], text
+    return 'fused'
+
+
+def trunc_expected_path(n, family, dt, mapping):
+    """What plan.cpp fused_pad_ok and plan_line give the shipped build, as a set of accepted paths.  The table's exceptions:
+      * 5^c 2^k lengths (40, 80, 1000, and the packed-real rows of twice such a length) carry the adapters only in a
+        `make VARIANTS=1` library: either path;
+      * a REAL transform along a strided axis of an unequal-width length has no register kernel (generic kernel + separate
+        truncation);
+      * contiguous real rows of 8192 points run packed on the 4096-point kernel, which carries the adapters: fused."""
+    real = dt in 'df'
+    if family == 'fused unequal-width':
+        return {'stand-alone'} if real and mapping != 'rows' else {'fused'}
+    if family != 'stand-alone':
+        return {'fused'}
+    if n in (40, 80, 1000):
+        return {'fused', 'stand-alone'}
+    if n == 8192 and real and mapping == 'rows':
+        return {'fused'}
+    return {'stand-alone'}
 
 
 def dirty_spectrum(shape, dt, seed):

@@ -16,6 +16,21 @@ def _tol(dt):
     return 2e-10 if dt in 'dD' else 2e-4
 
 
+def _padded_at_rounding_level(shp, axis, dt, padding, A, B, Bref, A1, what):
+    """A padded serial plan against the FLOAT64 oracle whatever `dt` (numpy keeps complex64 / float32 transforms in single
+    precision: the oracle of the test's own precision is no high-precision reference), on the input widened AFTER it was
+    rounded to `dt`; n is the padded length of the line.  B = forward(A); A1 = backward(Bref), Bref the spectrum the plan was
+    given (widened as it is: the reference starts from the same numbers)."""
+    from tests import cases
+    n = shp[axis]
+    wide = 'D' if dt in 'DF' else 'd'
+    ref64 = O.OFFT(shp, axis, wide, padding=padding)
+    cases.assert_close(B, ref64.forward(A.astype(wide)), dt, n, (what, 'forward'))
+    want = ref64.backward(Bref.astype('D'))
+    err = float(np.abs(A1 - want).max())
+    assert err <= 2 * cases.rounding_tol(dt, n) * np.abs(want).max(), (what, 'backward, ROUNDING-LEVEL guard', err / np.abs(want).max())
+
+
 def _check(shape, axes, dt, seed=0):
     from mpi4py_fft_amd import FFT, asdevice
     fft = FFT(shape, axes, dtype=dt)
@@ -210,6 +225,7 @@ def test_padding_truncation(dt):
                 assert np.abs(B - Bref).max() <= tol * np.abs(Bref).max(), (shp, axis, padding)
                 A1 = np.asarray(fft.backward(asdevice(B))).copy()
                 assert np.abs(A1 - ref.backward(Bref)).max() <= 10 * tol * np.abs(A).max()
+                _padded_at_rounding_level(shp, axis, dt, padding, A, B, B, A1, (shp, axis, padding, dt))
                 B2 = np.asarray(fft.forward(asdevice(A1)))
                 assert np.abs(B2 - B).max() <= 10 * tol * np.abs(B).max()
                 fft.destroy()
@@ -433,6 +449,7 @@ def test_fused_truncation_and_padding_on_unequal_width_lengths(dt):
         assert np.abs(B - Bref).max() <= tol * np.abs(Bref).max(), (shp, axis, padding, dt)
         A1 = np.asarray(fft.backward(asdevice(Bref))).copy()
         assert np.abs(A1 - ref.backward(Bref)).max() <= 10 * tol * np.abs(A).max(), (shp, axis, padding, dt)
+        _padded_at_rounding_level(shp, axis, dt, padding, A, B, Bref, A1, (shp, axis, padding, dt))
         fft.destroy()
 
 
@@ -459,6 +476,7 @@ def test_fused_truncation_and_padding(dt):
         assert np.abs(B - Bref).max() <= tol * np.abs(Bref).max(), (shp, axis, padding, dt)
         A1 = np.asarray(fft.backward(asdevice(Bref))).copy()
         assert np.abs(A1 - ref.backward(Bref)).max() <= 10 * tol * np.abs(A).max(), (shp, axis, padding, dt)
+        _padded_at_rounding_level(shp, axis, dt, padding, A, B, Bref, A1, (shp, axis, padding, dt))
         B2 = np.asarray(fft.forward(asdevice(A1)))
         assert np.abs(B2 - B).max() <= 10 * tol * np.abs(B).max()
         fft.destroy()
@@ -466,8 +484,9 @@ def test_fused_truncation_and_padding(dt):
 
 def test_padded_pfft_uses_fused_truncation():
     from mpi4py_fft_amd import PFFT, newDistArray, comm
+    from tests import cases
     shape = (32, 64, 128)
-    for dt in 'dD':
+    for dt in 'dDfF':
         fft = PFFT(comm.COMM_SELF, shape, dtype=dt, padding=[1.5, 1.5, 1.5])
         assert all(x._fused_trunc for x in fft.xfftn)
         ref = O.OPFFT(1, shape, dtype=dt, padding=[1.5, 1.5, 1.5])
@@ -476,9 +495,16 @@ def test_padded_pfft_uses_fused_truncation():
         u[...] = G
         uh = np.asarray(fft.forward(u)).copy()
         want = ref.forward([G])[0]
-        assert np.abs(uh - want).max() <= 2e-10 * np.abs(want).max()
-        back = np.asarray(fft.backward())
-        assert np.abs(back - ref.backward([want])[0]).max() <= 1e-10 * max(1, np.abs(G).max())
+        assert np.abs(uh - want).max() <= _tol(dt) * np.abs(want).max()
+        back = np.asarray(fft.backward()).copy()
+        assert np.abs(back - ref.backward([want])[0]).max() <= (1e-10 if dt in 'dD' else 1e-4) * max(1, np.abs(G).max())
+        # ... and at rounding level, both directions against the FLOAT64 oracle on the numbers the plan was given
+        wide = 'D' if dt in 'DF' else 'd'
+        ref64 = O.OPFFT(1, shape, dtype=wide, padding=[1.5, 1.5, 1.5])
+        cases.assert_close(uh, ref64.forward([G.astype(wide)])[0], dt, G.size, (dt, 'forward'))
+        want64 = ref64.backward([uh.astype('D')])[0]
+        err = float(np.abs(back - want64).max())
+        assert err <= 2 * cases.rounding_tol(dt, G.size) * np.abs(want64).max(), (dt, 'backward, ROUNDING-LEVEL guard', err / np.abs(want64).max())
         fft.destroy()
 
 
