@@ -54,6 +54,14 @@ derivatives pooled over the three directions, three `SpectralOps.histogram` call
 many give the same tables.  `solve(w, verbose=True, gradients=True, pdfs=True, dealias='2/3')` prints the shares of the four
 (R, Q) quadrants.
 
+`particles=(P, order, seed)` follows P tracers through the flow: positions uniform in the box, replicated on all ranks, advanced
+by the same RK4 as the velocity -- every right-hand side interpolates the stage's velocity at the stage's positions with
+`SpectralOps.interpolate`, for order 2 straight from the U the step already holds in physical space, for order 4 from B-spline
+coefficients (`scale_axes(U_hat, bspline_vectors(4))` and three more backward transforms); the positions ride through
+`spectral.rk_stage` beside the velocity's stages and are not wrapped (the interpolation is periodic).  After 10 steps at 64^3
+with dealias='2/3' the coordinates of 1000 cubic tracers (seed 7) add up to PARTICLE_CHECK below (measured on one MI355X; the
+reference has no particles).
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -71,12 +79,13 @@ DEALIASED_ENERGY = 0.124953117516743          # solve(dealias='2/3'), M = 6, 10 
 SCALAR_VARIANCE = 0.126225641497587           # 'scalar_variance' of solve(scalar=(nu, (1, 0, 0))), M = 6, 10 steps
 IF_ENERGY = 0.124953117516741                 # solve(integrator='ifrk4'), M = 6, 10 steps
 GRADIENT_SKEWNESS = -0.064835990474654        # 'gradients'.skewness of solve(gradients=True, dealias='2/3'), M = 6, 10 steps
+PARTICLE_CHECK = 15755.713888103239            # sum of 'particles' of solve(particles=(1000, 4, 7), dealias='2/3'), M = 6, 10 steps
 PDF_BINS, PDF_R, PDF_Q, PDF_SIGMAS = 128, 4.0, 6.0, 6.0     # solve(pdfs=True): bins per axis; the (R, Q) plane in <Q_w>^(3/2), <Q_w>; the derivative range
 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
           transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
-          scalar=None, integrator='rk4', gradients=False, pdfs=False):
+          scalar=None, integrator='rk4', gradients=False, pdfs=False, particles=None):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -112,7 +121,15 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     `SpectralOps.histogram` calls added), the int64 tables themselves ('rq_counts', 'longitudinal_counts'), their ranges
     ('rq_range', 'longitudinal_range') and 'quadrants', the shares of the in-range points in the four quarters of the table: (lower
     half of the R range, upper half of the Q range), (upper, upper), (lower, lower), (upper, lower).  The halves meet at 0 to
-    within the rounding of the bin rule: a point with R or Q exactly 0 may count on either side."""
+    within the rounding of the bin rule: a point with R or Q exactly 0 may count on either side.
+    particles=(P, order, seed): P tracers, uniform in the box from np.random.default_rng(seed), the same on all ranks, in a
+    double [P][3] tensor, advanced with the velocity: every right-hand side interpolates its stage's velocity at its stage's
+    positions -- on the fused path by `SpectralOps.interpolate` (order 2 from U itself, order 4 from the coefficients that
+    `SpectralOps.scale_axes` with `bspline_vectors(4)` and three backward transforms give; on one rank with reduce=False, so the
+    step stays capturable), on the fused=False path by torch index expressions over the same weights (the A/B baseline) -- and
+    the positions take the stages of `spectral.rk_stage` (dt= included) beside the velocity's.  Positions are not wrapped.
+    A dict passed as `stats` receives 'particles' (numpy [P][3]) and 'particle_velocity' (the last interpolated velocities).
+    The velocity, and so the returned energy, is unchanged."""
     from mpi4py_fft_amd import PFFT, _lib, newDistArray, spectral
     assert not pdfs or (gradients and fused), 'pdfs needs gradients=True and the fused path'
     N = [2 ** M] * 3
@@ -145,6 +162,18 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         Theta = newDistArray(FFT, False)                      # the scalar, physical space
         T_hat, T_hat0, T_hat1, dT = (newDistArray(FFT) for _ in range(4))
         th, tht, tht0, tht1, dth = (a.tensor for a in (Theta, T_hat, T_hat0, T_hat1, dT))
+    if particles is not None:
+        n_part, p_order, p_seed = int(particles[0]), int(particles[1]), particles[2]
+        assert p_order in (2, 4), 'particles = (P, order, seed) with order 2 or 4'
+        xp_start = np.random.default_rng(p_seed).uniform(0.0, 1.0, (n_part, 3)) * L
+        Xp = torch.tensor(xp_start, dtype=torch.float64, device=dev)          # (a copy, also where the device is the host)
+        Xp0, Xp1, dXp = (torch.zeros_like(Xp) for _ in range(3))          # the stage's start, the accumulator, the velocity at Xp
+        one_rank = world.Get_size() == 1
+        if p_order == 4:
+            Coef = newDistArray(FFT, False, rank=1)               # B-spline coefficients of U
+            C_hat = newDistArray(FFT, rank=1)
+            # the prefilter per axis: 1 / ((2 + cos(2 pi n / N)) / 3) over this rank's spectral block
+            bvec = [1.0 / ((2.0 + np.cos(2 * np.pi * ki[si] / float(n))) / 3.0) for ki, si, n in zip(k, s, N)]
     assert dealias in (None, '2/3'), dealias
     assert integrator in ('rk4', 'ifrk4') and (fused or integrator == 'rk4'), 'ifrk4 needs the fused path'
     ifrk = integrator == 'ifrk4'
@@ -163,6 +192,8 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             UT_hat = newDistArray(FFT, rank=1)
 
         force = [None]                                        # project's force= of the current step
+        if particles is not None and p_order == 4:
+            bspl = ops.bspline_vectors(4)
 
         def compute_rhs_fused(nu=0.0 if ifrk else nu):
             for j in range(3):
@@ -180,6 +211,17 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                 for j in range(3):
                     FFT.forward(UT[j], UT_hat[j])
                 ops.scalar_rhs(dT, UT_hat, T_hat, 0.0 if ifrk else kappa, G, U_hat, dealias=mask)
+            if particles is not None:                         # the stage's velocity at the stage's positions
+                field = U
+                if p_order == 4:
+                    ops.scale_axes(U_hat, bspl, out=C_hat)
+                    for j in range(3):
+                        FFT.backward(C_hat[j], Coef[j])
+                    field = Coef
+                if one_rank:
+                    ops.interpolate(field, Xp, order=p_order, out=dXp, reduce=False)          # enqueued, like everything else
+                else:
+                    dXp.copy_(torch.as_tensor(ops.interpolate(field, Xp, order=p_order)))    # each rank its points; added on the host
 
     def fwd(x, out):      # physical (torch expression) -> spectral slice `out`
         out.copy_(FFT.forward(x).tensor)
@@ -211,6 +253,41 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                 dth.sub_(G[0] * uh[0] + G[1] * uh[1] + G[2] * uh[2])
             if dealias:
                 dth.masked_fill_(~keep, 0)
+        if particles is not None:
+            field = u
+            if p_order == 4:
+                pre = torch.as_tensor(bvec[0][:, None, None] * bvec[1][None, :, None] * bvec[2][None, None, :], device=dev)
+                field = torch.stack([FFT.backward(uh[j] * pre).tensor.clone() for j in range(3)])
+            part = interp_torch(field)
+            if world.Get_size() > 1:
+                part = torch.as_tensor(sum(world.allgather_obj(part.cpu().numpy())), device=dev)
+            dXp.copy_(part)
+
+    def interp_torch(field):
+        """this rank's share of the interpolant of field [3] + local shape at Xp as torch index expressions: per axis the
+        base cell, the weights and the wrapped indices, then order^3 gathers per component"""
+        start = [sl.start or 0 for sl in FFT.local_slice(False)]
+        n = field.shape[1:]
+        w, idx, ok = [], [], []
+        for a in range(3):
+            sa = Xp[:, a] * (N[a] / L[a])
+            ia = torch.floor(sa)
+            t = sa - ia
+            r = 1.0 - t
+            w.append([r, t] if p_order == 2 else
+                     [r * r * r / 6.0, (3.0 * t * t * t - 6.0 * t * t + 4.0) / 6.0, (3.0 * r * r * r - 6.0 * r * r + 4.0) / 6.0, t * t * t / 6.0])
+            b = ia.long() - (1 if p_order == 4 else 0)
+            l = [(b + j) % N[a] - start[a] for j in range(p_order)]
+            ok.append([(lj >= 0) & (lj < n[a]) for lj in l])
+            idx.append([lj.clamp(0, n[a] - 1) for lj in l])
+        out = torch.zeros_like(dXp)
+        for j0 in range(p_order):
+            for j1 in range(p_order):
+                for j2 in range(p_order):
+                    inside = ok[0][j0] & ok[1][j1] & ok[2][j2]
+                    vals = field[:, idx[0][j0], idx[1][j1], idx[2][j2]].T.to(torch.float64)
+                    out += torch.where(inside[:, None], (w[0][j0] * w[1][j1] * w[2][j2])[:, None] * vals, torch.zeros_like(vals))
+        return out
 
     u[0] = torch.sin(X[0]) * torch.cos(X[1]) * torch.cos(X[2])
     u[1] = -torch.cos(X[0]) * torch.sin(X[1]) * torch.cos(X[2])
@@ -265,6 +342,9 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         if scalar is not None:
             tht0.copy_(tht)
             tht1.copy_(tht)
+        if particles is not None:
+            Xp0.copy_(Xp)
+            Xp1.copy_(Xp)
         for rk in range(4):
             if ifrk:
                 compute_rhs_fused()
@@ -294,7 +374,18 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                     if rk < 3:
                         torch.add(tht0, dth, alpha=b[rk] * dt, out=tht)
                     tht1.add_(dth, alpha=a[rk] * dt)
+            if particles is not None and fused:               # dXp is this stage's velocity at Xp: the stage the velocity took
+                if adaptive and device_dt:
+                    spectral.rk_stage(Xp if rk < 3 else None, Xp0, Xp1, dXp, b[rk] if rk < 3 else 0.0, a[rk], dt=dt_dev)
+                else:
+                    spectral.rk_stage(Xp if rk < 3 else None, Xp0, Xp1, dXp, b[rk] * h if rk < 3 else 0.0, a[rk] * h)
+            elif particles is not None:
+                if rk < 3:
+                    torch.add(Xp0, dXp, alpha=b[rk] * dt, out=Xp)
+                Xp1.add_(dXp, alpha=a[rk] * dt)
         uh.copy_(uh1)
+        if particles is not None:
+            Xp.copy_(Xp1)
         if scalar is not None:
             tht.copy_(tht1)
         for i in range(3):
@@ -311,6 +402,7 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         keep = uh.clone()
         keep_t = tht.clone() if scalar is not None else None
         keep_u = u.clone() if adaptive else None     # the adaptive step READS U: the warm-up must not leave its own there
+        keep_x = Xp.clone() if particles is not None else None
         side = torch.cuda.Stream()
         with torch.cuda.stream(side):
             step()                               # warm-up on the capture stream: scratch, tables
@@ -319,12 +411,16 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
         uh.copy_(keep)
         if scalar is not None:
             tht.copy_(keep_t)
+        if particles is not None:
+            Xp.copy_(keep_x)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             step()
         uh.copy_(keep)
         if scalar is not None:
             tht.copy_(keep_t)
+        if particles is not None:
+            Xp.copy_(keep_x)
         if adaptive:
             u.copy_(keep_u)
             dt_dev.zero_()
@@ -360,6 +456,10 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             sflux = [sum(world.allgather_obj(float((u[c] * th).sum().item()))) / npts for c in range(3)]
         if stats is not None:
             stats.update(scalar_variance=variance, scalar_flux=sflux)
+    if particles is not None:
+        xp_h, vp_h = Xp.cpu().numpy(), dXp.cpu().numpy()
+        if stats is not None:
+            stats.update(particles=xp_h, particle_velocity=vp_h)
     elapsed = time.time() - t0
     if verbose and world.Get_rank() == 0:
         print('%d^3, %d steps, %s pointwise path: %.3f s (%.2f ms per RK4 step), energy = %.12f'
@@ -373,6 +473,10 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                   % (band + (f_eps, 'device' if device_gain else 'host', last_gain[0], last_gain[1], 2 * last_gain[0] * last_gain[1])))
     if scalar is not None and verbose and world.Get_rank() == 0:
         print('  scalar (kappa = %g, G = %s): variance %.15f, flux <u theta> = (%.6e, %.6e, %.6e)' % ((kappa, G, variance) + tuple(sflux)))
+    if particles is not None and verbose and world.Get_rank() == 0:
+        print('  %d tracers, order %d: sum of coordinates %.12f, mean |v| %.6f, largest displacement %.6f'
+              % (n_part, p_order, xp_h.sum(), np.sqrt((vp_h * vp_h).sum(axis=1)).mean() if n_part else 0.0,
+                 np.abs(xp_h - xp_start).max() if n_part else 0.0))
     if gradients:
         npts = N[0] * N[1] * N[2]
         if fused:
@@ -524,6 +628,16 @@ if __name__ == '__main__':
     assert abs(gf.skewness - gb.skewness) <= 1e-10 * abs(gf.skewness) and abs(gf.dissipation - gb.dissipation) <= 1e-10 * gf.dissipation, (gf, gb)
     assert abs(gf.skewness - GRADIENT_SKEWNESS) <= 1e-9 * abs(GRADIENT_SKEWNESS) and abs(gf.betchov - 1) <= 1e-9, (gf, GRADIENT_SKEWNESS)
     assert abs(gf.strain - gf.enstrophy) <= 1e-12 * gf.strain and gf.div_rms <= 1e-12, gf
+    sp, sq = {}, {}
+    ep = solve(w, verbose=True, particles=(1000, 4, 7), dealias='2/3', stats=sp)      # tracers: cubic B-splines
+    solve(w, verbose=True, particles=(1000, 2, 7), dealias='2/3', stats=sq)           # ... and trilinear
+    assert abs(ep - DEALIASED_ENERGY) <= 1e-9, ep                                     # tracers are passive
+    assert abs(sp['particles'].sum() - PARTICLE_CHECK) <= 1e-9 * PARTICLE_CHECK, (sp['particles'].sum(), PARTICLE_CHECK)
+    assert np.abs(sp['particles'] - sq['particles']).max() <= 1e-3, np.abs(sp['particles'] - sq['particles']).max()
+    if w.Get_size() == 1:
+        sg = {}
+        solve(w, verbose=True, particles=(1000, 4, 7), dealias='2/3', stats=sg, graph=True)
+        assert np.array_equal(sg['particles'], sp['particles'])
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)

@@ -603,6 +603,60 @@ int gfft_ps_gradient_pdf(const void *d_A /* [3][3][count] real */, int64_t count
                          int qy, double ylo, double yhi, int nby,
                          int64_t *d_out, int precision, void *stream);
 
+/* ---- the fields where no grid point is: B-spline interpolation at particle positions ----------
+ *   gfft_ps_scale_axes   the separable spectral multiplier: out[c][i0][i1][i2] = f_hat[c][i0][i1][i2] * g with
+ *                    g = (v0[i0] * v1[i1]) * v2[i2], the vectors real, of the field's precision, over the block's axes.  g is
+ *                    formed in the field's precision; the real and the imaginary part are each ONE multiply by g.  A NULL
+ *                    vector means that axis contributes no factor -- no multiply by 1 is issued for it (v0 NULL: g = v1 * v2;
+ *                    all NULL: a copy).  Every result is a defined sequence of single multiplies with nothing to contract,
+ *                    so it equals a host restatement in the same precision bit for bit, NaN, inf and the sign of a zero
+ *                    included.  d_out == d_f_hat (in place) is allowed; any other overlap is not.  1 <= ncomp <= 4.
+ *                    The prefilter of cubic B-spline interpolation is one such g (per axis 1 / ((2 + cos(2 pi n / N)) / 3),
+ *                    n the integer wavenumber); any separable filter (Gaussian, box) is three vectors through the same call.
+ *                    GFFT_ERR_INVALID (before a device is touched) for a null field, ncomp < 1, a negative size, precision;
+ *                    GFFT_ERR_UNSUPPORTED for ncomp > 4 and an axis longer than 2^30.  Only enqueues.
+ *   gfft_ps_interp   d_out[p][c] = the order-2 (trilinear) or order-4 (cubic B-spline) interpolant of the coefficient field
+ *                    c at position x[p], restricted to the stencil points THIS block owns.  d_c = [ncomp][n[0]][n[1]][n[2]]
+ *                    real, the block start[a] .. start[a] + n[a] of a periodic grid of N[a] cells per axis; inv_dx[a] = N[a] /
+ *                    L[a] (host); d_x = double [np][3] whatever the field's precision; d_out = double [np][ncomp], OVERWRITTEN.
+ *                    THE DEFINITION, per particle p and axis a, in double:
+ *                      s = x[p][a] * inv_dx[a]                  (one multiply)
+ *                      !(fabs(s) < 2^51) on ANY axis            -> every entry of out[p][:] is NaN and nothing is loaded
+ *                                                                  (NaN, +-inf, and anything too large to have a fraction)
+ *                      i = floor(s),  t = s - i                 (one rounded subtraction; t may come out as exactly 1.0 for a
+ *                                                                  tiny negative s: the weights are continuous there)
+ *                      order 2:  base b = i,      weights  1 - t,  t
+ *                      order 4:  base b = i - 1,  with r = 1 - t the weights
+ *                                r^3 / 6,  (3 t^3 - 6 t^2 + 4) / 6,  (3 r^3 - 6 r^2 + 4) / 6,  t^3 / 6
+ *                      for stencil offset j = 0 .. order - 1:   g = (b + j) mod N[a] as a non-negative int64, l = g - start[a];
+ *                                                                the point contributes iff 0 <= l < n[a] on all three axes
+ *                      out[p][c] = sum over the contributing points of ((w0 * w1) * w2) * (double)c[c][l0][l1][l2]
+ *                    taken in ONE fixed order (a row of the stencil along the last axis in a lane, the rows by a fixed
+ *                    butterfly), so the result repeats bit for bit from call to call; a particle with no contributing
+ *                    point gets +0.0.  How the weight polynomials are evaluated and whether a product is contracted into
+ *                    the sum is not part of the definition: a result lies within (order^3 + 64) 2^-53 sum |w0 w1 w2 c| of the
+ *                    exact sum.  Summed over the blocks of a grid the results are the full interpolant; with start = 0,
+ *                    n = N it is the whole periodic interpolant.  Positions are NOT required to lie in the box: they
+ *                    wrap.  N[a] < order is legal: the stencil wraps onto itself, which periodicity makes correct.  For order
+ *                    4, c must hold B-spline coefficients: the backward transform of gfft_ps_scale_axes with the prefilter
+ *                    above; fed samples instead it smooths.  Every index that reaches a load has gone through the integer
+ *                    wrap and the block test -- or is the constant 0, element 0 of a component, read in place of a point
+ *                    outside the block and dropped --, and the 2^51 guard comes before the conversion to an integer: no
+ *                    position, finite or not, addresses outside the block.  A NaN in c reaches exactly the particles whose stencil
+ *                    holds it (a point of weight 0 included).  np = 0 launches nothing.  order^2 lanes serve a particle;
+ *                    no atomics, no scratch.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, ncomp < 1,
+ *                    np < 0, an order other than 2 or 4, n or N < 1, start < 0, start + n > N, an inv_dx that is not
+ *                    finite and > 0, precision; GFFT_ERR_UNSUPPORTED for ncomp > 4 (and a grid axis beyond 2^40).  Only enqueues. */
+int gfft_ps_scale_axes(void *d_out, const void *d_f_hat /* [ncomp][n0][n1][n2] complex */, int ncomp,
+                       const void *d_v0, const void *d_v1, const void *d_v2 /* real [n0], [n1], [n2]; NULL: no factor */,
+                       int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
+int gfft_ps_interp(const void *d_c /* [ncomp][n[0]][n[1]][n[2]] real: this rank's block of the coefficients */,
+                   int ncomp, const int64_t n[3], const int64_t start[3], const int64_t N[3],
+                   const double inv_dx[3] /* host: N_i / L_i */,
+                   const double *d_x /* [np][3] positions, double whatever the field's precision */,
+                   int64_t np, int order /* 2 (trilinear) or 4 (cubic B-spline) */,
+                   double *d_out /* [np][ncomp], overwritten */, int precision, void *stream);
+
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:
  *   gfft_comm_create / gfft_comm_split  <- MPI_Cart_create + MPI_Cart_sub   mpi4py_fft/pencil.py:64-93

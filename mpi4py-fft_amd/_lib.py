@@ -108,6 +108,8 @@ def _declare(lib):
                                         c.c_int, vp]),
         'gfft_ps_gradient_pdf': (c.c_int, [vp, c.c_int64, c.c_int, c.c_double, c.c_double, c.c_int, c.c_int, c.c_double,
                                            c.c_double, c.c_int, vp, c.c_int, vp]),
+        'gfft_ps_scale_axes': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_int, vp]),
+        'gfft_ps_interp': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, c.POINTER(c.c_double), vp, c.c_int64, c.c_int, vp, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -584,6 +586,28 @@ class HipEngine:
         self.require_device(tout)
         check(lib().gfft_ps_gradient_pdf(ta.data_ptr(), int(count), int(qx), float(xr[0]), float(xr[1]), int(nbx), int(qy),
                                          float(yr[0]), float(yr[1]), int(nby), tout.data_ptr(), precision, current_stream()))
+
+    def ps_scale_axes(self, tf, tout, ncomp, v, shape, precision):
+        """gfft_ps_scale_axes: tout[c] = tf[c] * (v[0][i0] * v[1][i1]) * v[2][i2] on complex [ncomp] + shape; v = three real
+        device vectors of the field's precision or None (no factor from that axis); tout is tf or overlaps nothing."""
+        self.require_device(tf)
+        self.require_device(tout)
+        for vi in v:
+            if vi is not None:
+                self.require_device(vi)
+        check(lib().gfft_ps_scale_axes(tout.data_ptr(), tf.data_ptr(), int(ncomp), *[None if vi is None else vi.data_ptr() for vi in v],
+                                       shape[0], shape[1], shape[2], precision, current_stream()))
+
+    def ps_interp(self, tc, ncomp, n, start, N, inv_dx, tx, npart, order, tout, precision):
+        """gfft_ps_interp: tc = real [ncomp] + n, the block start .. start + n of a periodic grid N; inv_dx = three host floats;
+        tx = double [npart][3]; tout = double [npart][ncomp] on the device, overwritten with this block's share of the
+        order-2 or order-4 interpolant."""
+        self.require_device(tc)
+        self.require_device(tx)
+        self.require_device(tout)
+        dx = (ctypes.c_double * 3)(*[float(d) for d in inv_dx])
+        check(lib().gfft_ps_interp(tc.data_ptr(), int(ncomp), _i64(n), _i64(start), _i64(N), dx, tx.data_ptr(), int(npart), int(order),
+                                   tout.data_ptr(), precision, current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

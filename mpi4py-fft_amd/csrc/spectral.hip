@@ -10,7 +10,9 @@
 //     binned by |k| (ps_shell_kernel: E(k), co-spectra, helicity), physical-space statistics (ps_stats_kernel) and the
 //     statistics of the velocity-gradient tensor (ps_gradient_stats_kernel, behind the pointwise ps_gradient_kernel: i K_j f_hat);
 //   * histograms over the same geometry: integer counts in a workgroup's LDS table (ps_histogram_kernel: the components of a
-//     real field; ps_gradient_pdf_kernel: one or two of the gradient invariants per point), summed to int64 by pd_sum_kernel.
+//     real field; ps_gradient_pdf_kernel: one or two of the gradient invariants per point), summed to int64 by pd_sum_kernel;
+//   * a field where no grid point is: ps_scale_axes_kernel (pointwise: a separable spectral multiplier, the B-spline prefilter)
+//     and ps_interp_kernel (a gather: order^2 lanes per particle, trilinear or cubic B-spline, periodic, block by block).
 #include "../../include/gfft.h"
 #include "gfft_internal.h"
 
@@ -1173,6 +1175,162 @@ pd_sum_kernel(const uint32_t *__restrict__ slabs, int nwg, int nrow, int rowlen,
   }
 }
 
+// ---- the fields where no grid point is: a separable spectral multiplier and the B-spline gather ----------------------------
+// out[c][e] = f[c][e] * g with g = (v0[i0] * v1[i1]) * v2[i2] formed in the field's precision; a null vector contributes no
+// factor (no multiply by 1), all three null: a copy.  Each part of each value is ONE multiply by g, and g at most two: a
+// defined sequence of single multiplies with nothing to contract, so any host restates it bit for bit.  The B-spline
+// prefilter of gfft_ps_interp is one such g (SpectralOps.bspline_vectors); a Gaussian or a box filter is another.
+// NC loads and NC stores per mode in the mould of ps_gradient_kernel (a lane's mode its flat index, the three cached vector
+// lookups of ps_curl_kernel, grid-stride); V modes per lane: 16 bytes per load and store -- one mode in fp64, two in fp32
+// where n2 is even (a pair then shares its row) and both bases are 16-byte aligned, else one.  A lane reads all its values
+// before it stores any, and no other lane touches them: out may BE f (in place); any other overlap is the caller's error.
+// (Registers, hipcc -O3, gfx950: ps_scale_axes_kernel<double, 1, NC = 1 ... 4> 21, 26, 42, 40 VGPRs; <float, 2, NC> 23, 24, 29, 34;
+// <float, 1, NC> 21, 21, 26, 27 -- 8 waves per SIMD, no scratch.)
+constexpr int SA_MAX_COMP = 4;
+
+template <typename real, int V, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_scale_axes_kernel(cx<real> *out, const cx<real> *f, const real *__restrict__ v0, const real *__restrict__ v1,
+                     const real *__restrict__ v2, int64_t n1, int64_t n2, int64_t count) {
+  using vec = st_load<real, 2 * V>;
+  const int64_t nvec = count / V;                        // (count is a multiple of V)
+  for (int64_t i = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * PS_THREADS) {
+    const int64_t e = i * V;
+    const int64_t row = e / n2, i2 = e - row * n2;
+    const int64_t i0 = row / n1;
+    bool has = false;
+    real g01 = 0;
+    if (v0) { g01 = v0[i0]; has = true; }
+    if (v1) { const real b = v1[row - i0 * n1]; g01 = has ? g01 * b : b; has = true; }
+    real g[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) g[j] = v2 ? (has ? g01 * v2[i2 + j] : v2[i2 + j]) : g01;
+    const bool any = has || v2;
+    vec a[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) a[c] = *reinterpret_cast<const vec *>(f + c * count + e);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      vec o = a[c];
+      if (any) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          o.m[2 * j] = a[c].m[2 * j] * g[j];
+          o.m[2 * j + 1] = a[c].m[2 * j + 1] * g[j];
+        }
+      }
+      *reinterpret_cast<vec *>(out + c * count + e) = o;
+    }
+  }
+}
+
+// gfft_ps_interp: trilinear (ORDER 2) or cubic B-spline (ORDER 4) interpolation of NC <= 4 real fields at np positions; the
+// definition, operation by operation, is in include/gfft.h.  A GROUP of ORDER^2 lanes (4 or 16: whole groups per wave) serves
+// one particle: lane (j0, j1) of the group owns one row of the stencil and loads its ORDER last-axis values for every
+// component -- ORDER NC independent loads per lane, ORDER^2 NC lines in flight per particle --, forms its partial sum in
+// double in the order j2 = 0, 1, ..., and the group adds the partial sums by the butterfly lane ^ ORDER^2 / 2, ..., 2, 1 (both
+// partners form the same a + b): one fixed order, so the result repeats bit for bit.  Every lane of a group derives the same
+// base cell and fraction from the same position (redundant arithmetic instead of a broadcast).  Groups stride over the
+// particles; lane 0 of a group stores its NC results.  No atomics, no LDS, nothing between workgroups.
+//
+// What keeps every load inside the block, whatever the position holds:
+//   1. s = x * inv_dx passes !(fabs(s) < 2^51) -> the particle's results are NaN and the group loads NOTHING.  This comes
+//      BEFORE the conversion to an integer: NaN, +-inf and anything without a fraction never reach it.
+//   2. otherwise floor(s) is an integer of magnitude <= 2^51, exact in int64, and b + j cannot overflow;
+//   3. ip_wrap brings it to g in [0, N) by the integer remainder, made non-negative; ip_next steps g + 1 with the wrap, which
+//      is (b + j) mod N for every j (also where N < ORDER: the stencil wraps onto itself);
+//   4. l = g - start is tested 0 <= l < n on all three axes, per element, and ONLY a point that passed is added.  The index of
+//      a load is SELECTED between two values: the sum of three tested l's, inside [0, n0 n1 n2) of its component, and the
+//      constant 0 -- element 0 of the component, which exists because every n >= 1 (the entry point refuses less) -- for a
+//      point outside the block, whose value is then dropped.  The select instead of a branch keeps the ORDER NC loads of a
+//      lane independent and in flight together: with a branch around each load the compiler waited for one load before it
+//      issued the next (a wait per load in the assembly), and the random-order gather ran at the latency of ORDER loads in turn.
+// A particle none of whose points lies in the block gets +0.0 (the sum of nothing).
+// (Registers, hipcc -O3, gfx950: ps_interp_kernel<double, NC = 1 ... 4, ORDER 4> 38, 48, 54, 64 VGPRs and <float, NC, 4> 36, 38, 42,
+// 50; <double, NC, ORDER 2> 36, 36, 35, 44 and <float, NC, 2> 36, 36, 38, 44: every instantiation 8 waves per SIMD, none spills or
+// uses scratch.)
+constexpr int IP_MAX_COMP = 4;
+struct ip_dims { int64_t n[3], start[3], N[3]; double inv_dx[3]; };          // by value in the launch
+
+__device__ __forceinline__ int64_t ip_wrap(int64_t b, int64_t N) {
+  if (b >= 0 && b < N) return b;                         // a particle inside the box: no division
+  const int64_t r = b % N;
+  return r < 0 ? r + N : r;
+}
+
+__device__ __forceinline__ int64_t ip_next(int64_t g, int64_t N) { return g + 1 == N ? 0 : g + 1; }
+
+// weight j of the stencil at fraction t in [0, 1] (j is a lane's own index: selected, never indexed)
+template <int ORDER>
+__device__ __forceinline__ double ip_weight(int j, double t) {
+  const double r = 1.0 - t;
+  if (ORDER == 2) return j == 0 ? r : t;
+  const double sixth = 1.0 / 6.0;
+  const double wa = ((r * r) * r) * sixth, wd = ((t * t) * t) * sixth;
+  const double wb = ((t * t) * (3.0 * t - 6.0) + 4.0) * sixth, wc = ((r * r) * (3.0 * r - 6.0) + 4.0) * sixth;
+  return j == 0 ? wa : j == 1 ? wb : j == 2 ? wc : wd;
+}
+
+template <typename real, int NC, int ORDER>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_interp_kernel(const real *__restrict__ c, ip_dims d, const double *__restrict__ x, int64_t np, double *__restrict__ out) {
+  constexpr int G = ORDER * ORDER;                       // lanes per particle
+  const int lane = threadIdx.x % G, j0 = lane / ORDER, j1 = lane % ORDER;
+  const int64_t cnt = d.n[0] * d.n[1] * d.n[2];
+  const int64_t stride = (int64_t)gridDim.x * (PS_THREADS / G);
+  for (int64_t p = (int64_t)blockIdx.x * (PS_THREADS / G) + threadIdx.x / G; p < np; p += stride) {
+    const double s0 = x[3 * p] * d.inv_dx[0], s1 = x[3 * p + 1] * d.inv_dx[1], s2 = x[3 * p + 2] * d.inv_dx[2];
+    const double lim = 2251799813685248.0;               // 2^51
+    const bool good = fabs(s0) < lim && fabs(s1) < lim && fabs(s2) < lim;          // (false for a NaN)
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    if (good) {                                          // (the same on every lane of the group)
+      const double f0 = floor(s0), f1 = floor(s1), f2 = floor(s2);
+      const double w01 = ip_weight<ORDER>(j0, s0 - f0) * ip_weight<ORDER>(j1, s1 - f1);
+      const double t2 = s2 - f2;
+      const int64_t shift = ORDER == 4 ? 1 : 0;
+      int64_t g0 = ip_wrap((int64_t)f0 - shift, d.N[0]), g1 = ip_wrap((int64_t)f1 - shift, d.N[1]);
+      int64_t g2 = ip_wrap((int64_t)f2 - shift, d.N[2]);
+#pragma unroll
+      for (int j = 1; j < ORDER; ++j) {
+        if (j <= j0) g0 = ip_next(g0, d.N[0]);
+        if (j <= j1) g1 = ip_next(g1, d.N[1]);
+      }
+      const int64_t l0 = g0 - d.start[0], l1 = g1 - d.start[1];
+      const bool row_in = l0 >= 0 && l0 < d.n[0] && l1 >= 0 && l1 < d.n[1];
+      const int64_t base = row_in ? (l0 * d.n[1] + l1) * d.n[2] : 0;
+      bool in[ORDER];
+      real v[NC][ORDER];
+#pragma unroll
+      for (int j = 0; j < ORDER; ++j) {
+        const int64_t l2 = g2 - d.start[2];
+        in[j] = row_in && l2 >= 0 && l2 < d.n[2];
+        const int64_t at = in[j] ? base + l2 : 0;        // tested, or element 0 of the component (n >= 1: it exists); see 4.
+#pragma unroll
+        for (int k = 0; k < NC; ++k) v[k][j] = c[k * cnt + at];
+        g2 = ip_next(g2, d.N[2]);
+      }
+#pragma unroll
+      for (int j = 0; j < ORDER; ++j) {
+        const double w = w01 * ip_weight<ORDER>(j, t2);
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+          if (in[j]) acc[k] += w * (double)v[k][j];
+      }
+    }
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) acc[k] += __shfl_xor(acc[k], off);
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) out[p * NC + k] = good ? acc[k] : (double)NAN;
+    }
+  }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // f(real()) with the element type of `precision`: a launcher names its kernel and arguments once
 template <typename F>
@@ -1418,6 +1576,37 @@ hipError_t launch_ps_gradient(const void *f, void *out, int ncomp, const void *k
   const int64_t lanes = ncomp == 1 ? (count + 1) / 2 : count;          // a single field: two modes per lane and step
   return by_precision(
       precision, [&](auto r) { return ps_pointwise(gr_kernel<decltype(r)>(ncomp), lanes, s, f, out, k0, k1, k2, n1, n2, count); });
+}
+
+template <typename real, int V>
+auto sa_kernel(int nc) {
+  return nc == 1 ? ps_scale_axes_kernel<real, V, 1> : nc == 2 ? ps_scale_axes_kernel<real, V, 2>
+       : nc == 3 ? ps_scale_axes_kernel<real, V, 3> : ps_scale_axes_kernel<real, V, 4>;
+}
+
+// 1 <= ncomp <= SA_MAX_COMP; out == f or no overlap
+hipError_t launch_ps_scale_axes(void *out, const void *f, int ncomp, const void *v0, const void *v1, const void *v2, int64_t n0,
+                                int64_t n1, int64_t n2, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  const bool pair = precision == GFFT_F32 && n2 % 2 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)f % 16 == 0;
+  if (pair) return ps_pointwise(sa_kernel<float, 2>(ncomp), count / 2, s, out, f, v0, v1, v2, n1, n2, count);
+  return by_precision(
+      precision, [&](auto r) { return ps_pointwise(sa_kernel<decltype(r), 1>(ncomp), count, s, out, f, v0, v1, v2, n1, n2, count); });
+}
+
+template <typename real, int ORDER>
+auto ip_kernel(int nc) {
+  return nc == 1 ? ps_interp_kernel<real, 1, ORDER> : nc == 2 ? ps_interp_kernel<real, 2, ORDER>
+       : nc == 3 ? ps_interp_kernel<real, 3, ORDER> : ps_interp_kernel<real, 4, ORDER>;
+}
+
+// 1 <= ncomp <= IP_MAX_COMP, order 2 or 4, d checked by the caller; ORDER^2 lanes per particle, so np * ORDER^2 lanes
+hipError_t launch_ps_interp(const void *c, int ncomp, const ip_dims &d, const double *x, int64_t np, int order, double *out,
+                            int precision, hipStream_t s) {
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    return ps_pointwise(order == 4 ? ip_kernel<real, 4>(ncomp) : ip_kernel<real, 2>(ncomp), np * order * order, s, c, d, x, np, out);
+  });
 }
 
 // the geometry of launch_ps_stats over the one base A; `slabs` = ST_SCRATCH_BYTES of stream-ordered scratch
@@ -1828,6 +2017,45 @@ int gfft_ps_gradient_pdf(const void *d_A, int64_t count, int qx, double xlo, dou
   rc = scratch_get((hipStream_t)stream, pd_scratch_bytes(ncounters, ntails), &slabs);
   if (rc) return rc;
   HIP_TRY(launch_ps_gradient_pdf(d_A, count, ax, ay, d_out, static_cast<uint32_t *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_scale_axes(void *d_out, const void *d_f_hat, int ncomp, const void *d_v0, const void *d_v1, const void *d_v2,
+                       int64_t n0, int64_t n1, int64_t n2, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum; a null vector is legal: that axis contributes no factor)
+  if (!d_out || !d_f_hat || ncomp < 1 || n0 < 0 || n1 < 0 || n2 < 0 || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_scale_axes: bad argument");
+  static_assert(SA_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > SA_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scale_axes: more than 4 components");
+  if (n0 > ((int64_t)1 << 30) || n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scale_axes: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_scale_axes(d_out, d_f_hat, ncomp, d_v0, d_v1, d_v2, n0, n1, n2, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_interp(const void *d_c, int ncomp, const int64_t n[3], const int64_t start[3], const int64_t N[3],
+                   const double inv_dx[3], const double *d_x, int64_t np, int order, double *d_out, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_c || !n || !start || !N || !inv_dx || !d_x || !d_out || ncomp < 1 || np < 0 ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_interp: bad argument");
+  if (order != 2 && order != 4) return fail(GFFT_ERR_INVALID, "gfft_ps_interp: order must be 2 or 4");
+  ip_dims d;
+  for (int a = 0; a < 3; ++a) {
+    if (n[a] < 1 || N[a] < 1 || start[a] < 0 || start[a] > N[a] || n[a] > N[a] - start[a])
+      return fail(GFFT_ERR_INVALID, "gfft_ps_interp: a block needs n >= 1, N >= 1 and 0 <= start, start + n <= N");
+    if (!std::isfinite(inv_dx[a]) || !(inv_dx[a] > 0)) return fail(GFFT_ERR_INVALID, "gfft_ps_interp: inv_dx must be finite and > 0");
+    d.n[a] = n[a], d.start[a] = start[a], d.N[a] = N[a], d.inv_dx[a] = inv_dx[a];
+  }
+  static_assert(IP_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > IP_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_interp: more than 4 components");
+  // an axis of 2^40 cells and a block of 2^60 values: the flat index of a load and b + j stay far inside int64
+  if (N[0] > ((int64_t)1 << 40) || N[1] > ((int64_t)1 << 40) || N[2] > ((int64_t)1 << 40) ||
+      (double)n[0] * (double)n[1] * (double)n[2] > 0x1p60)
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_interp: block too large");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_interp(d_c, ncomp, d, d_x, np, order, d_out, precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -91,6 +91,17 @@ and the distributions those moments compress -- integer counts from one read, ex
                                 without fused multiply-adds so that the counts equal a numpy restatement exactly
     pdf(counts, range), joint_pdf(counts, ranges, bins)   bin centres, the density and the shares outside the range
 
+and the fields where no grid point is -- tracer particles, probes, a line or a plane that is not a grid plane: B-spline
+interpolation (van Hinsberg et al. 2012), whose coefficients cost a spectral code one pointwise pass:
+
+    scale_axes(f_hat, v, out)   f_hat * (v0[i0] * v1[i1]) * v2[i2]: any separable spectral multiplier as three per-axis vectors (the
+                                sparse form again), in place or not; every part one multiply, bit for bit a numpy restatement
+    bspline_vectors(order)      the three vectors of the order-4 prefilter 1 / ((2 + cos(2 pi n / N)) / 3); order 2 needs none
+    interpolate(c, x, order)    the order-2 (trilinear) or order-4 (cubic) interpolant of m <= 4 real fields at double positions
+                                [P][3], periodic, positions anywhere: order^2 lanes gather a particle's stencil and add it in a
+                                fixed order (bit for bit repeatable); each rank adds the stencil points it owns and `reduce=`
+                                adds the ranks -- no halo, no particle migration; a position that is not finite gives NaN
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -206,6 +217,89 @@ class SpectralOps:
         self._gshape = tuple(int(n) for n in fft.global_shape(True))
         self._slice = tuple(fft.local_slice(True))
         self._real = np.dtype(fft.dtype(False)).kind == 'f'
+        # what interpolate needs: where this rank's physical block starts in the periodic grid N
+        self.pstart = tuple(int(sl.start or 0) for sl in fft.local_slice(False))
+
+    def scale_axes(self, f_hat, v, out=None):
+        """out = f_hat * g with g = (v[0][i0] * v[1][i1]) * v[2][i2]: a separable spectral multiplier in one pass.  f_hat is the
+        spectral shape or [m] + spectral shape, m <= 4, complex, contiguous, of the transform's precision; v is a triple of real
+        device vectors of that precision over this rank's spectral axes, or None for an axis that contributes no factor (no
+        multiply by 1 is issued); out defaults to f_hat itself (in place) and otherwise has its shape and overlaps nothing.
+        g is formed in the field's precision and each part of each value is one multiply by it: bit for bit a numpy
+        restatement.  `bspline_vectors(4)` is the prefilter of `interpolate`; any separable filter -- Gaussian, box -- is
+        three vectors through the same call.  Returns out.  Nothing synchronises or allocates."""
+        t, ncomp, precision = self._field(f_hat)
+        assert ncomp <= 4, 'at most 4 components per call'
+        assert len(v) == 3, 'v = three per-axis vectors (or None)'
+        rdt = torch.float64 if precision == 8 else torch.float32
+        for vi, n in zip(v, self.shape):
+            assert vi is None or (isinstance(vi, torch.Tensor) and vi.dtype == rdt and tuple(vi.shape) == (n,) and
+                                  vi.is_contiguous()), 'a vector is a real tensor of the field\'s precision over its local axis'
+        if out is None:
+            out = f_hat
+        to, no, po = self._field(out)
+        assert (no, po) == (ncomp, precision) and to.dim() == t.dim(), 'out and f_hat differ in shape or precision'
+        _lib.engine().ps_scale_axes(t, to, ncomp, tuple(v), self.shape, precision)
+        return out
+
+    def bspline_vectors(self, order=4):
+        """The prefilter of B-spline interpolation of `order` as three vectors for `scale_axes`, over this rank's spectral block,
+        in the transform's precision, computed on the host in double: for order 4 entry n (global integer wavenumber) of axis
+        i is 1 / ((2 + cos(2 pi n / N_i)) / 3) -- the reciprocal of the cubic B-spline's Fourier symbol, which lies in [1/3, 1]
+        and is never zero; 1 at n = 0, 3 at the Nyquist index of an even axis.  order 2: (None, None, None) -- linear
+        interpolation needs no prefilter.  Allocates three small device vectors: build them once."""
+        assert order in (2, 4), 'order = 2 or 4'
+        if order == 2:
+            return (None, None, None)
+        n = [np.fft.fftfreq(N, 1. / N) for N in self._N]
+        if self._real:
+            n[-1] = np.fft.rfftfreq(self._N[-1], 1. / self._N[-1])
+        rdt = np.float64 if self.K[0].dtype == torch.float64 else np.float32
+        dev = self.K[0].device
+        return tuple(torch.as_tensor((1.0 / ((2.0 + np.cos(2 * np.pi * ni[sl].astype(int) / float(N))) / 3.0)).astype(rdt), device=dev)
+                     for ni, N, sl in zip(n, self._N, self._slice))
+
+    def interpolate(self, c, x, order=4, out=None, reduce=True):
+        """The order-2 (trilinear) or order-4 (cubic B-spline) interpolant of real fields at particle positions: double [P][m],
+        or [P] for a scalar field.  c is a contiguous real tensor or DistArray of shape fft.shape(False) or [m] + that shape,
+        m <= 4, in the transform's precision; x is a contiguous double device tensor [P][3], THE SAME ON EVERY RANK (particles
+        are replicated), in the units of L; positions need not lie in the box (the grid is periodic) and a NaN, an infinity
+        or an |x| beyond 2^51 cells gives a NaN row.  For order 4, c must hold B-spline coefficients: the backward transform of
+        `scale_axes(f_hat, bspline_vectors(4))`; order 2 reads the samples themselves.  The definition, operation by
+        operation, is in include/gfft.h (gfft_ps_interp); values are converted to double first and summed in a fixed order:
+        the result repeats bit for bit.
+
+        Each rank adds the stencil points its block owns.  reduce=True adds the ranks' partial results on the host in rank
+        order, one grid axis after the other (as `stats` does), so every rank holds identical bits; this synchronises and
+        moves 8 P m bytes per rank through the host: priced for diagnostics and moderate P.  reduce=False only enqueues
+        and returns the device tensor (`out`, a contiguous double tensor of the shape above, or a new one): on one rank the
+        complete result, and with `out=` given capturable into a graph."""
+        t, ncomp, precision = self._real_field(c)
+        assert ncomp <= 4, 'at most 4 components per call'
+        assert order in (2, 4), 'order = 2 or 4'
+        assert isinstance(x, torch.Tensor) and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous(), \
+            'x is a contiguous double tensor [P][3]'
+        assert x.device == t.device, 'x and the field live on different devices'
+        P = int(x.shape[0])
+        shape = (P,) if t.dim() == 3 else (P, ncomp)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=t.device)
+        assert isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == torch.float64 and out.is_contiguous(), \
+            (tuple(out.shape), shape)
+        if min(self.pshape) == 0:                      # a rank without a block owns no stencil point
+            out.zero_()
+        else:
+            _lib.engine().ps_interp(t, ncomp, self.pshape, self.pstart, self._N, self.inv_dx, x, P, order, out, precision)
+        if not reduce:
+            return out
+        vals = out.cpu().numpy()                       # (waits for the kernel)
+        _lib.check_async()
+        for cm in self.comms:                          # one grid axis after the other: the same order on every rank
+            parts = cm.allgather_obj(vals)
+            vals = parts[0].copy()
+            for p in parts[1:]:
+                vals = vals + p
+        return vals
 
     def _same_precision(self, precision):
         # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
