@@ -70,8 +70,11 @@ const char *gfft_last_error(void);          /* detail of the last failure on thi
 int gfft_version(void);
 int gfft_device_count(int *count);          /* hipGetDeviceCount; GFFT_ERR_NO_DEVICE if none */
 int gfft_device_name(int device, char *buf, size_t len);
-/* tunables consulted when a plan is created: "grid_cap", "variant_rows", "variant_cols",
- * "force_generic", "fused3", "profile" (also readable from the environment as GFFT_<UPPERCASE NAME>);
+/* tunables consulted when a plan is created: "grid_cap" (> 0: workgroups per launch at most, for every pass kernel whose
+ * workgroups walk their tiles -- the register kernels, the generic and per-column kernels, the on-chip planes, the Bluestein
+ * point kernels; set it before the plan is made and keep it through the executes; 0: each launcher's own cap; persistent fused
+ * pairs and the pack / truncate / scale kernels do not look at it; gfft_plan_pass_launch reports the outcome), "variant_rows",
+ * "variant_cols", "force_generic", "fused3", "profile" (also readable from the environment as GFFT_<UPPERCASE NAME>);
  * "fuse2" (1: pass pairs as one persistent launch through the Infinity Cache where a pair exists and pays,
  * 0: stand-alone passes), with "fuse2_ring" / "fuse2_lag" (slots of the hand-off ring /
  * planes the producer runs ahead; 0 = auto: about 96 MiB of lead and twice that of ring -- 12 / 6 planes of 16 MiB, 24 / 12 of
@@ -717,6 +720,10 @@ int gfft_event_destroy(void *event);
  * the accumulated milliseconds of each pass (HIP events recorded on the execute stream) */
 int gfft_plan_profile(gfft_plan plan, float *ms, int max_passes, int *executes);
 int gfft_plan_pass_info(gfft_plan plan, int pass, char *buf, size_t len, double *algorithmic_bytes);
+/* TEST AID: tiles (units of work a workgroup takes one at a time) and workgroups of pass `pass`'s most recent launch;
+ * 0 / 0 before the plan's first execute.  GFFT_ERR_INVALID: null plan or out pointer, bad pass index ("bad pass index",
+ * as gfft_plan_pass_info).  GFFT_ERR_UNSUPPORTED: a persistent fused pair (its workgroups draw tickets; no cap applies). */
+int gfft_plan_pass_launch(gfft_plan plan, int pass, int64_t *tiles, int *workgroups);
 /* streaming-copy probe: dst[i] = src[i] over `bytes` (multiple of 16); the HBM ceiling quoted
  * beside roofline numbers */
 int gfft_probe_copy(const void *d_src, void *d_dst, size_t bytes, void *stream);

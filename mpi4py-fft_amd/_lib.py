@@ -123,6 +123,7 @@ def _declare(lib):
         'gfft_event_destroy': (c.c_int, [vp]),
         'gfft_plan_profile': (c.c_int, [vp, c.POINTER(c.c_float), c.c_int, ip]),
         'gfft_plan_pass_info': (c.c_int, [vp, c.c_int, c.c_char_p, c.c_size_t, c.POINTER(c.c_double)]),
+        'gfft_plan_pass_launch': (c.c_int, [vp, c.c_int, i64p, ip]),
         'gfft_probe_copy': (c.c_int, [vp, vp, c.c_size_t, vp]),
         'gfft_async_error': (c.c_int, []),
         'gfft_plan_status': (c.c_int, [vp]),
@@ -376,6 +377,16 @@ class HipEngine:
             b = ctypes.c_double()
             check(lib().gfft_plan_pass_info(h, i, buf, 64, ctypes.byref(b)))
             out.append((buf.value.decode(), b.value, float(ms[i]), n.value))
+        return out
+
+    def plan_pass_launch(self, h):
+        """TEST AID (gfft_plan_pass_launch): [(tiles, workgroups)] of every pass's most recent launch, (0, 0) before the first
+        execute; raises for a plan with a persistent fused pair."""
+        out = []
+        for i in range(self.plan_cost(h)[2]):
+            t, w = ctypes.c_int64(), ctypes.c_int()
+            check(lib().gfft_plan_pass_launch(h, i, ctypes.byref(t), ctypes.byref(w)))
+            out.append((t.value, w.value))
         return out
 
     def pack(self, tarray, tpacked, shape, axis, nparts, itemsize):

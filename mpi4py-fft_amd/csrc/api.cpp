@@ -394,7 +394,9 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
     if (p.kind == PK_PLANE2D) {
       PassDesc d2 = p.d2;
       d2.scale = p.carries_scale ? scale : 1.0;
+      last_launch() = LaunchNote{};
       HIP_TRY(launch_plane2d(d, d2, pl->precision, p.fused.planes, p.fused.a_in_plane, p.fused.b_out_plane, bufs[p.src], bufs[p.dst], s));
+      p.launched = last_launch();
       HIP_TRY(mark());
       continue;
     }
@@ -446,7 +448,9 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
       continue;
     }
     if (p.carries_scale) d.scale = scale;
+    last_launch() = LaunchNote{};
     HIP_TRY(run_pass(pl, p, d, bufs[p.src], bufs[p.dst], p.carries_scale ? scale : 1.0, s));
+    p.launched = last_launch();      // (gfft_plan_pass_launch)
     HIP_TRY(mark());
   }
   return GFFT_OK;
@@ -515,6 +519,18 @@ int gfft_plan_pass_info(gfft_plan pl, int i, char *buf, size_t len, double *byte
     if (p.data_inner) *bytes *= (double)p.data_inner / (double)p.d.inner;
     if (p.d.mode == MODE_R2R) *bytes = (double)p.d.batch * 2.0 * p.d.r2r_n * (double)pl->precision;
   }
+  return GFFT_OK;
+}
+
+/* TEST AID: the launch form of pass i's most recent launch, as its launcher noted it (gfft_internal.h note_launch) */
+int gfft_plan_pass_launch(gfft_plan pl, int i, int64_t *tiles, int *workgroups) {
+  if (!pl) return fail(GFFT_ERR_INVALID, "null plan");
+  if (!tiles || !workgroups) return fail(GFFT_ERR_INVALID, "null argument");
+  if (i < 0 || i >= (int)pl->passes.size()) return fail(GFFT_ERR_INVALID, "bad pass index");
+  const Pass &p = pl->passes[i];
+  if (p.kind == PK_FUSED2) return fail(GFFT_ERR_UNSUPPORTED, "a persistent fused pair has no launch form to report (its workgroups draw tickets)");
+  *tiles = p.launched.tiles;
+  *workgroups = p.launched.workgroups;
   return GFFT_OK;
 }
 

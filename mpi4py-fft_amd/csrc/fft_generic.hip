@@ -214,7 +214,8 @@ tiny_dft_kernel(PassDesc d, const void *__restrict__ in, void *__restrict__ out)
 template <typename real, int A>
 static hipError_t launch_tiny(const PassDesc &d, const void *in, void *out, hipStream_t s) {
   const int64_t blocks = (d.batch + TINY_THREADS - 1) / TINY_THREADS;
-  const int grid = (int)(blocks < 8192 ? blocks : 8192);
+  const int grid = capped_grid(blocks, 8192);
+  note_launch(blocks, grid);
   hipLaunchKernelGGL((tiny_dft_kernel<real, A>), dim3(grid), dim3(TINY_THREADS), 0, s, d, in, out);
   return hipGetLastError();
 }
@@ -256,7 +257,8 @@ static hipError_t launch_generic_t(const PassDesc &d, const Factors &f, const vo
     attr_set[dev] = true;
   }
   int64_t tiles = (d.batch + T - 1) / T;
-  int grid = (int)(tiles < 4096 ? tiles : 4096);
+  int grid = capped_grid(tiles, 4096);
+  note_launch(tiles, grid);
   hipLaunchKernelGGL(fft_generic_kernel<real>, dim3(grid), dim3(GEN_THREADS), lds, s, d, f, T, in, out);
   return hipGetLastError();
 }

@@ -72,8 +72,9 @@ static hipError_t launch_plane2d_one(const PassDesc &dA, const PassDesc &dB, int
     cus_of[dev] = n;
   }
   // (one plane per workgroup; more planes than 4 workgroups per CU: the workgroups walk)
-  const int cap = 4 * cus_of[dev];
-  hipLaunchKernelGGL(kern, dim3(planes < cap ? planes : cap), dim3(A::threads), lds, s, dA, dB, planes, in_plane, out_plane, dB.scale, in, out);
+  const int grid = capped_grid(planes, 4 * cus_of[dev]);
+  note_launch(planes, grid);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(A::threads), lds, s, dA, dB, planes, in_plane, out_plane, dB.scale, in, out);
   return hipGetLastError();
 }
 

@@ -1518,6 +1518,7 @@ hipError_t launch_pow2_one(const PassDesc &d, const void *in, void *out, hipStre
   } else {
     dd.order = 0;
   }
+  note_launch(ntiles, grid);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, dd, in, out);
   return hipGetLastError();
 }

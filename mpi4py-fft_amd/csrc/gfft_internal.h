@@ -244,6 +244,18 @@ bool pow2_r2r_supported(int n);
 hipError_t launch_pow2_r2r_f64(const PassDesc &d, bool cols, const void *in, void *out, hipStream_t s);
 hipError_t launch_pow2_r2r_f32(const PassDesc &d, bool cols, const void *in, void *out, hipStream_t s);
 int pow2_grid_cap();
+// Option grid_cap as it stands at launch time (0 = not set).  Every launcher whose workgroups WALK their tiles takes
+// min(its own cap, the option): the register kernels through pow2_grid_cap() / PassDesc::grid_cap, the others through capped_grid().
+int grid_cap_option();
+inline int capped_grid(int64_t tiles, int64_t own_cap) {
+  const int64_t opt = grid_cap_option(), cap = (opt > 0 && opt < own_cap) ? opt : own_cap;
+  return (int)(tiles < cap ? tiles : cap);
+}
+// TEST AID (gfft_plan_pass_launch): tiles -- the units of work a workgroup takes one at a time -- and workgroups of the calling
+// thread's most recent pass launch.  The launchers write it; gfft_execute copies it into the pass it has just run.
+struct LaunchNote { int64_t tiles = 0; int workgroups = 0; };
+LaunchNote &last_launch();
+inline void note_launch(int64_t tiles, int workgroups) { LaunchNote &n = last_launch(); n.tiles = tiles; n.workgroups = workgroups; }
 // two dependent fp64 passes fused into one persistent launch (fft_fused_f64.hip; fft_pow2_impl.h
 // fft_fused2_kernel).  kind: FUSED_ROWS_COLS = [rows, n] -> [strided, n], FUSED_COLS_ROWS the reverse,
 // FUSED_FOURSTEP = the two passes of a four-step transform of length n * n

@@ -227,13 +227,22 @@ extract_kernel(PointDesc p, const cx<real> *__restrict__ W, void *__restrict__ o
   }
 }
 
+// grid of the embedding / Bluestein point kernels: mv_grid, under option grid_cap, and noted for gfft_plan_pass_launch
+// (tiles = blocks of MV_THREADS elements)
+static inline int point_grid(int64_t total) {
+  const int64_t blocks = (total + MV_THREADS - 1) / MV_THREADS;
+  const int grid = capped_grid(blocks, MV_MAX_BLOCKS);
+  note_launch(blocks, grid);
+  return grid;
+}
+
 hipError_t launch_embed(const PointDesc &p, int precision, const void *in, void *scratch, hipStream_t s) {
   const int64_t total = p.outer * p.Lw * p.inner;
   if (total == 0) return hipSuccess;
   if (precision == 8)
-    hipLaunchKernelGGL(embed_kernel<double>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, in, (cx<double> *)scratch);
+    hipLaunchKernelGGL(embed_kernel<double>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, in, (cx<double> *)scratch);
   else
-    hipLaunchKernelGGL(embed_kernel<float>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, in, (cx<float> *)scratch);
+    hipLaunchKernelGGL(embed_kernel<float>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, in, (cx<float> *)scratch);
   return hipGetLastError();
 }
 
@@ -241,9 +250,9 @@ hipError_t launch_mulb(const PointDesc &p, int precision, void *scratch, hipStre
   const int64_t total = p.outer * p.Lw * p.inner;
   if (total == 0) return hipSuccess;
   if (precision == 8)
-    hipLaunchKernelGGL(mulb_kernel<double>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, (cx<double> *)scratch);
+    hipLaunchKernelGGL(mulb_kernel<double>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, (cx<double> *)scratch);
   else
-    hipLaunchKernelGGL(mulb_kernel<float>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, (cx<float> *)scratch);
+    hipLaunchKernelGGL(mulb_kernel<float>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, (cx<float> *)scratch);
   return hipGetLastError();
 }
 
@@ -251,9 +260,9 @@ hipError_t launch_extract(const PointDesc &p, int precision, const void *scratch
   const int64_t total = p.outer * p.nout * p.inner;
   if (total == 0) return hipSuccess;
   if (precision == 8)
-    hipLaunchKernelGGL(extract_kernel<double>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, (const cx<double> *)scratch, out, scale);
+    hipLaunchKernelGGL(extract_kernel<double>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, (const cx<double> *)scratch, out, scale);
   else
-    hipLaunchKernelGGL(extract_kernel<float>, dim3(mv_grid(total)), dim3(MV_THREADS), 0, s, p, (const cx<float> *)scratch, out, (float)scale);
+    hipLaunchKernelGGL(extract_kernel<float>, dim3(point_grid(total)), dim3(MV_THREADS), 0, s, p, (const cx<float> *)scratch, out, (float)scale);
   return hipGetLastError();
 }
 

@@ -1440,6 +1440,11 @@ hipError_t run_pass(const gfft_plan_s *pl, const Pass &p, const PassDesc &d0, co
 }
 
 int pow2_grid_cap() { return opts().grid_cap > 0 ? opts().grid_cap : 4096; }
+int grid_cap_option() { return opts().grid_cap > 0 ? opts().grid_cap : 0; }
+LaunchNote &last_launch() {
+  static thread_local LaunchNote note;
+  return note;
+}
 
 // Batched 2-D complex transform plane by plane: the passes of gfft_plan_create_guru2 (see there), pushed onto pl->passes
 // -- one fused launch where a pair exists, else (unless fused_only) the two stand-alone passes [first: IN -> OUT, second:

@@ -97,6 +97,7 @@ struct Pass {
   int alt_buf = -1;
   size_t alt_bytes = 0;
   double bytes2 = 0;                 // algorithmic bytes of pass B (gfft_plan_pass_info reports A + B)
+  mutable LaunchNote launched{};     // TEST AID (gfft_plan_pass_launch): tiles / workgroups of this pass's most recent launch
 };
 
 struct PairChoice {                 // what fused2_pair answers

@@ -694,6 +694,24 @@ def trunc_expected_path(n, family, dt, mapping):
     return {'stand-alone'}
 
 
+# ---- launch forms (tests/test_gpu_tile_walk.py): one workgroup per tile against workgroups that walk several ----
+def same_bits(a, b):
+    """The two arrays hold the same BYTES: NaN payloads and the sign of a zero count, which `==` does not see."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.reshape(-1).view(np.uint8), b.reshape(-1).view(np.uint8))
+
+
+def walk_batch(mapping, n, lines):
+    """(shape, axis) of a batch of lines of n points in one of R2R_MAPPINGS: 'rows' (lines, n), 'cols' (n, lines) and the
+    3-D 'middle' (5, n, 37) -- (outer, mid, inner) addressing, 185 lines whatever `lines` says."""
+    return {'rows': ((lines, n), 1), 'cols': ((n, lines), 0), 'middle': ((5, n, 37), 1)}[mapping]
+
+
+def plan_launches(plans):
+    """[(tiles, workgroups)] of every pass of the given fftw.FFT plans' most recent launches (gfft_plan_pass_launch), in order."""
+    return [tw for p in plans for tw in p._eng.plan_pass_launch(p._plan)]
+
+
 def dirty_spectrum(shape, dt, seed):
     """A seeded complex Gaussian half-spectrum that is NOT Hermitian-clean: the DC and Nyquist entries keep their O(1)
     imaginary parts, as a spectrum does after a nonlinear term."""

@@ -128,6 +128,10 @@ OTHERS = [
     ('gfft_truncate', (PTR, PTR, 2, SHAPE8, 1, 0, 0, 8, 1.0, None), -1, b'bad truncated length'),
     ('gfft_pad', (PTR, PTR, 2, SHAPE8, 1, 9, 0, 8, None), -1, b'bad truncated length'),
     ('gfft_pad', (PTR, PTR, 2, SHAPE8, 1, 0, 0, 8, None), -1, b'bad truncated length'),
+    # (a stand-in plan is not dereferenced before the out pointers have been looked at)
+    ('gfft_plan_pass_launch', (None, 0, ctypes.pointer(ctypes.c_int64()), ctypes.pointer(ctypes.c_int())), -1, b'null plan'),
+    ('gfft_plan_pass_launch', (PTR, 0, None, ctypes.pointer(ctypes.c_int())), -1, b'null argument'),
+    ('gfft_plan_pass_launch', (PTR, 0, ctypes.pointer(ctypes.c_int64()), None), -1, b'null argument'),
 ]
 
 # the keys gfft_set_option accepts and their defaults, from the library's source
