@@ -660,6 +660,54 @@ int gfft_ps_interp(const void *d_c /* [ncomp][n[0]][n[1]][n[2]] real: this rank'
                    int64_t np, int order /* 2 (trilinear) or 4 (cubic B-spline) */,
                    double *d_out /* [np][ncomp], overwritten */, int precision, void *stream);
 
+/* ---- particle to grid: the transpose of gfft_ps_interp, order-independent to the last bit ----------
+ *   gfft_ps_spread   d_acc[c][l0][l1][l2] += the contributions of np particles to the stencil points THIS block owns, with the
+ *                    weights of gfft_ps_interp, each contribution rounded ONCE to a 64-bit integer (fixed point, 2^scale_exp
+ *                    units per unit of q) and added by an integer atomic.  Integer addition is associative: d_acc does not
+ *                    depend on the order in which the adds arrive, on the order of the particles or on how the grid is cut
+ *                    into blocks, and a host restates it bit for bit.  d_acc = int64 [ncomp][n[0]][n[1]][n[2]], ADDED TO (the
+ *                    caller zeroes it, or gfft_ps_spread_finish does); n, start, N, inv_dx, d_x as in gfft_ps_interp;
+ *                    d_q = double [np][ncomp]; d_skipped = int64 [1], ADDED TO.
+ *                    THE DEFINITION, per particle p, in double, EVERY operation rounded on its own (no product is contracted
+ *                    into a sum or a difference):
+ *                      s_a = x[p][a] * inv_dx[a]                (one multiply per axis)
+ *                      u_c = q[p][c] * 2^scale_exp              (one multiply; the host forms 2^scale_exp with ldexp)
+ *                      !(fabs(s_a) < 2^51) on ANY axis or !(fabs(u_c) < 2^62) for ANY component
+ *                                                               -> the particle is SKIPPED: it adds nothing to any component
+ *                                                                  and *d_skipped grows by one (NaN and +-inf fail both tests).
+ *                                                                  This comes BEFORE the block test: every block of a grid
+ *                                                                  counts the same particles
+ *                      i = floor(s),  t = s - i,  r = 1 - t,  sixth = 1.0 / 6.0
+ *                      order 2:  base b = i,      weights  r,  t
+ *                      order 4:  base b = i - 1,  weights  ((r*r)*r)*sixth,  ((t*t)*(3.0*t - 6.0) + 4.0)*sixth,
+ *                                                          ((r*r)*(3.0*r - 6.0) + 4.0)*sixth,  ((t*t)*t)*sixth
+ *                      for stencil offset j = 0 .. order - 1:   g = (b + j) mod N[a] as a non-negative int64, l = g - start[a];
+ *                                                                the point receives iff 0 <= l < n[a] on all three axes
+ *                                                                (the wrap and the test of gfft_ps_interp)
+ *                      for every receiving point and component: k = llrint(((w0 * w1) * w2) * u_c), ties to even;
+ *                                                                acc[c][l0][l1][l2] += k  as a 64-bit add modulo 2^64
+ *                    N[a] < order is legal: the stencil wraps onto itself and one particle adds to one address several
+ *                    times.  The add is a no-return 64-bit integer atomic at agent scope; no floating-point atomic, no LDS,
+ *                    no scratch.  Weights are >= 0 and sum to 1, so with 2^scale_exp * max_c sum_p |q[p][c]| <= 2^62 no
+ *                    accumulator leaves int64; a point's value lies within n_l 2^-(scale_exp + 1) + 16 * 2^-53 * sum |w q| of the
+ *                    exact sum (n_l contributions: half a unit each, plus the roundings of the weights and products).
+ *                    Every index that reaches an add has gone through the 2^51 guard, the integer wrap and the block test.
+ *                    np = 0 launches nothing.  GFFT_ERR_INVALID (before a device is touched) for a null pointer, ncomp < 1,
+ *                    np < 0, an order other than 2 or 4, |scale_exp| > 1000, n or N < 1, start < 0, start + n > N, an inv_dx
+ *                    that is not finite and > 0; GFFT_ERR_UNSUPPORTED for ncomp > 4 (and a grid axis beyond 2^40).  Only enqueues.
+ *   gfft_ps_spread_finish   out[i] = (real)((double)acc[i] * factor) for i < count: one conversion, one multiply and, for
+ *                    GFFT_F32, one narrowing; THEN, if clear != 0, acc[i] = 0 (a captured step needs no memset).  With factor =
+ *                    2^-scale_exp (times a normalisation: the wrapper passes the ONE host quotient factor / 2^scale_exp) out
+ *                    is the spread field.  d_out and d_acc do not overlap.  count = 0 launches nothing.  GFFT_ERR_INVALID
+ *                    (before a device is touched) for a null pointer, count < 0, a factor that is not finite, precision.
+ *                    Only enqueues. */
+int gfft_ps_spread(int64_t *d_acc /* [ncomp][n[0]][n[1]][n[2]], ADDED to */, int ncomp,
+                   const int64_t n[3], const int64_t start[3], const int64_t N[3], const double inv_dx[3],
+                   const double *d_x /* [np][3] */, const double *d_q /* [np][ncomp] */, int64_t np,
+                   int order /* 2 or 4 */, int scale_exp, int64_t *d_skipped /* [1], ADDED to */, void *stream);
+int gfft_ps_spread_finish(void *d_out /* [count] real of `precision` */, int64_t *d_acc /* [count] */, int64_t count,
+                          double factor, int clear, int precision, void *stream);
+
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:
  *   gfft_comm_create / gfft_comm_split  <- MPI_Cart_create + MPI_Cart_sub   mpi4py_fft/pencil.py:64-93

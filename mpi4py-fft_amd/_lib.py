@@ -110,6 +110,8 @@ def _declare(lib):
                                            c.c_double, c.c_int, vp, c.c_int, vp]),
         'gfft_ps_scale_axes': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_int, vp]),
         'gfft_ps_interp': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, c.POINTER(c.c_double), vp, c.c_int64, c.c_int, vp, c.c_int, vp]),
+        'gfft_ps_spread': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, c.POINTER(c.c_double), vp, vp, c.c_int64, c.c_int, c.c_int, vp, vp]),
+        'gfft_ps_spread_finish': (c.c_int, [vp, vp, c.c_int64, c.c_double, c.c_int, c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -619,6 +621,23 @@ class HipEngine:
         dx = (ctypes.c_double * 3)(*[float(d) for d in inv_dx])
         check(lib().gfft_ps_interp(tc.data_ptr(), int(ncomp), _i64(n), _i64(start), _i64(N), dx, tx.data_ptr(), int(npart), int(order),
                                    tout.data_ptr(), precision, current_stream()))
+
+    def ps_spread(self, tacc, ncomp, n, start, N, inv_dx, tx, tq, npart, order, scale_exp, tskipped):
+        """gfft_ps_spread: tacc = int64 [ncomp] + n, ADDED to with this block's share of the particles' contributions in fixed
+        point (2^scale_exp units per unit of q); tx = double [npart][3], tq = double [npart][ncomp]; tskipped = int64 [1], grows
+        by the number of particles that are not finite or too large."""
+        for t in (tacc, tx, tq, tskipped):
+            self.require_device(t)
+        dx = (ctypes.c_double * 3)(*[float(d) for d in inv_dx])
+        check(lib().gfft_ps_spread(tacc.data_ptr(), int(ncomp), _i64(n), _i64(start), _i64(N), dx, tx.data_ptr(), tq.data_ptr(), int(npart),
+                                   int(order), int(scale_exp), tskipped.data_ptr(), current_stream()))
+
+    def ps_spread_finish(self, tout, tacc, count, factor, clear, precision):
+        """gfft_ps_spread_finish: tout[i] = (real)((double)tacc[i] * factor) over count values, then tacc[i] = 0 where clear"""
+        self.require_device(tout)
+        self.require_device(tacc)
+        check(lib().gfft_ps_spread_finish(tout.data_ptr(), tacc.data_ptr(), int(count), float(factor), int(bool(clear)), precision,
+                                          current_stream()))
 
     def copy(self, tsrc, tdst):
         self.require_device(tsrc)

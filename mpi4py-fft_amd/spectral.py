@@ -101,6 +101,10 @@ interpolation (van Hinsberg et al. 2012), whose coefficients cost a spectral cod
                                 [P][3], periodic, positions anywhere: order^2 lanes gather a particle's stencil and add it in a
                                 fixed order (bit for bit repeatable); each rank adds the stencil points it owns and `reduce=`
                                 adds the ranks -- no halo, no particle migration; a position that is not finite gives NaN
+    spread(q, x, order)         its transpose, particle to grid: factor * sum_p w(x_p) q_p on this rank's block, every
+                                contribution rounded once to 64-bit fixed point and added by an integer atomic, so the field
+                                does not depend on the order of the adds, of the particles or on the cut into ranks, and a
+                                numpy restatement gives the same bits; no rank reduction: the blocks are disjoint
 
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
@@ -219,6 +223,8 @@ class SpectralOps:
         self._real = np.dtype(fft.dtype(False)).kind == 'f'
         # what interpolate needs: where this rank's physical block starts in the periodic grid N
         self.pstart = tuple(int(sl.start or 0) for sl in fft.local_slice(False))
+        # where spread counts skipped particles for a caller who passes no counter (so that such a call allocates nothing)
+        self._spread_skipped = torch.zeros(1, dtype=torch.int64, device=self.K[0].device)
 
     def scale_axes(self, f_hat, v, out=None):
         """out = f_hat * g with g = (v[0][i0] * v[1][i1]) * v[2][i2]: a separable spectral multiplier in one pass.  f_hat is the
@@ -300,6 +306,88 @@ class SpectralOps:
             for p in parts[1:]:
                 vals = vals + p
         return vals
+
+    @staticmethod
+    def spread_scale_exp(q):
+        """The default `scale_exp` of `spread`: with S = max_c sum_p |q[p][c]| over the finite entries (one torch reduction; it
+        synchronises), floor(log2(2^62 / S)) clamped to +-1000, and 0 for S = 0 -- the largest power of two at which no
+        accumulator can leave int64, whatever the positions are."""
+        a = q.abs()
+        a = torch.where(torch.isfinite(a), a, torch.zeros_like(a))
+        S = float(a.reshape(a.shape[0], -1).sum(dim=0).max()) if a.numel() else 0.0
+        if S == 0.0:
+            return 0
+        if not math.isfinite(S):                       # (finite entries whose sum overflows)
+            return -1000
+        f, k = math.frexp(S)                           # S = f 2^k, 0.5 <= f < 1: floor(62 - k - log2 f), exactly
+        return max(-1000, min(1000, 62 - k + (1 if f == 0.5 else 0)))
+
+    def spread(self, q, x, order=4, out=None, scale_exp=None, factor=1.0, acc=None, skipped=None):
+        """Particle to grid, the transpose of `interpolate`: out = this rank's block of factor * sum_p w(x_p) q_p with the
+        order-2 (trilinear) or order-4 (cubic B-spline) weights of `interpolate`.  q is a contiguous double device tensor
+        [P][m], m <= 4, or [P] for a scalar; x a contiguous double device tensor [P][3] as in `interpolate`; x and q are THE
+        SAME ON EVERY RANK (particles are replicated).  out is a real tensor or DistArray of shape fft.shape(False) or [m] +
+        that shape in the transform's precision (default: a new tensor); it is OVERWRITTEN.  Returns out.  There is no rank
+        reduction: each rank deposits on the stencil points its block owns, the blocks are disjoint, and the distributed
+        field is complete without a halo exchange.  A rank without a block zero-fills out and launches nothing.
+
+        The sum is EXACT in the sense that matters for repeatability: each contribution w q 2^scale_exp is rounded once to a
+        64-bit integer and added by an integer atomic (the definition, operation by operation: include/gfft.h,
+        gfft_ps_spread), so the result does not depend on the order of the adds, on the order of the particles or on the
+        number of ranks, and a numpy restatement reproduces it bit for bit.  acc is the int64 workspace [m] + the local
+        physical shape (default: allocated and zeroed here); a caller's acc is ADDED TO and then cleared, so it is zeroed
+        once by its owner and comes back zero.  The wrapper passes the one host quotient factor / 2^scale_exp to
+        gfft_ps_spread_finish, which converts, multiplies and narrows once.
+
+        scale_exp=None takes `spread_scale_exp(q)` (one reduction; it synchronises): weights are non-negative and sum to
+        one, so no accumulator can leave int64, and a single contribution among 2^20 equal ones is resolved to about 2^-42
+        of itself.  (A lone particle that carries all of a power-of-two S lands ON the 2^62 guard and is skipped: pass
+        scale_exp one lower.)  A particle whose position is not finite or beyond 2^51 cells, or one of whose q 2^scale_exp is
+        not finite or reaches 2^62, deposits nothing for any component; `skipped` (int64 [1], ADDED TO) counts them, the
+        same on every rank that owns a block.  With scale_exp, acc and out all given nothing synchronises or allocates and the
+        call can be captured into a graph.
+
+        The adjoint chain: scale_axes(fft.forward(spread(q, x, 4)), bspline_vectors(4)) is the exact transpose of
+        interpolate(fft.backward(scale_axes(f_hat, bspline_vectors(4))), x, 4) -- the type-1 / type-2 pair of a non-uniform
+        transform, `scale_axes` being the deconvolution."""
+        assert order in (2, 4), 'order = 2 or 4'
+        assert isinstance(q, torch.Tensor) and q.dtype == torch.float64 and q.dim() in (1, 2) and q.is_contiguous(), \
+            'q is a contiguous double tensor [P][m] or [P]'
+        m = 1 if q.dim() == 1 else int(q.shape[1])
+        assert 1 <= m <= 4, 'at most 4 components per call'
+        P = int(q.shape[0])
+        assert isinstance(x, torch.Tensor) and x.dtype == torch.float64 and tuple(x.shape) == (P, 3) and x.is_contiguous(), \
+            'x is a contiguous double tensor [P][3], one row per row of q'
+        assert x.device == q.device, 'x and q live on different devices'
+        factor = float(factor)
+        assert math.isfinite(factor), 'factor must be finite'
+        rdt = self.K[0].dtype
+        if out is None:
+            out = torch.empty(self.pshape if q.dim() == 1 else (m,) + self.pshape, dtype=rdt, device=q.device)
+        to, mo, precision = self._real_field(out)
+        assert mo == m, 'out holds %d components, q %d' % (mo, m)
+        assert to.device == q.device, 'out and q live on different devices'
+        if acc is not None:
+            assert isinstance(acc, torch.Tensor) and acc.dtype == torch.int64 and tuple(acc.shape) == (m,) + self.pshape and \
+                acc.is_contiguous() and acc.device == q.device, 'acc is a contiguous int64 tensor [m] + the local physical shape'
+        if skipped is not None:
+            assert isinstance(skipped, torch.Tensor) and skipped.dtype == torch.int64 and tuple(skipped.shape) == (1,) and \
+                skipped.device == q.device, 'skipped is an int64 tensor [1]'
+        if scale_exp is None:
+            scale_exp = self.spread_scale_exp(q)
+        assert isinstance(scale_exp, (int, np.integer)) and not isinstance(scale_exp, bool) and abs(int(scale_exp)) <= 1000, \
+            'scale_exp is an integer, |scale_exp| <= 1000'
+        scale_exp = int(scale_exp)
+        if min(self.pshape) == 0:                      # a rank without a block owns no stencil point
+            to.zero_()
+            return out
+        if acc is None:
+            acc = torch.zeros((m,) + self.pshape, dtype=torch.int64, device=q.device)
+        eng = _lib.engine()
+        eng.ps_spread(acc, m, self.pshape, self.pstart, self._N, self.inv_dx, x, q, P, order, scale_exp,
+                      self._spread_skipped if skipped is None else skipped)
+        eng.ps_spread_finish(to, acc, acc.numel(), factor / math.ldexp(1.0, scale_exp), True, precision)
+        return out
 
     def _same_precision(self, precision):
         # the kernels read K (and W) in the field's precision: a field of the other one would get garbage wavenumbers
