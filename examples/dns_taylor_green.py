@@ -62,6 +62,14 @@ coefficients (`scale_axes(U_hat, bspline_vectors(4))` and three more backward tr
 with dealias='2/3' the coordinates of 1000 cubic tracers (seed 7) add up to PARTICLE_CHECK below (measured on one MI355X; the
 reference has no particles).
 
+`structure=(axis, per_octave)` (or `(axis, per_octave, every)`) reads the two-point statistics of the velocity along a grid axis
+this rank holds whole: `SpectralOps.structure_functions(U, axis, spectral.log_separations(N, per_octave), lcomp=axis)` on the U the
+step leaves in physical space -- one read of U for all separations -- and `spectral.structure_moments`.  Every `every` steps
+(default: after the last step only) it prints the longitudinal S_2(r), the 4/5-law ratio -S_3L / (eps r) with eps = 2 nu sum k^2
+E(k) from `SpectralOps.spectrum`, and the flatness of the longitudinal increment at the smallest separation.  The Taylor-Green
+vortex at 64^3 after ten steps is a smooth laminar flow: the ratio is far from 4/5 and the flatness is that of a few Fourier
+modes; the diagnostic is there for the forced runs this example grows into.  Off by default; it touches no other output.
+
   python examples/dns_taylor_green.py                         # 1 GPU
   torchrun --nproc-per-node 2 examples/dns_taylor_green.py    # one rank per GPU
 """
@@ -85,7 +93,7 @@ PDF_BINS, PDF_R, PDF_Q, PDF_SIGMAS = 128, 4.0, 6.0, 6.0     # solve(pdfs=True): 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
           transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
-          scalar=None, integrator='rk4', gradients=False, pdfs=False, particles=None):
+          scalar=None, integrator='rk4', gradients=False, pdfs=False, particles=None, structure=None):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -129,8 +137,15 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     step stays capturable), on the fused=False path by torch index expressions over the same weights (the A/B baseline) -- and
     the positions take the stages of `spectral.rk_stage` (dt= included) beside the velocity's.  Positions are not wrapped.
     A dict passed as `stats` receives 'particles' (numpy [P][3]) and 'particle_velocity' (the last interpolated velocities).
-    The velocity, and so the returned energy, is unchanged."""
+    The velocity, and so the returned energy, is unchanged.
+    structure=(axis, per_octave) or (axis, per_octave, every) (fused path): the structure functions of the velocity along grid
+    axis `axis` (whole on this rank: 1 or 2 on several ranks) at `spectral.log_separations(N, per_octave)`, every `every` steps
+    (default nsteps: the final state only), from the U the step leaves in physical space.  A dict passed as `stats` receives
+    'structure', a list with one dict per evaluation: 'step', 'r' (the separations in length units), 'moments' (the
+    `spectral.structure_moments` with the longitudinal component labelled), 'eps' (2 nu sum k^2 E(k) of `SpectralOps.spectrum`)
+    and 'four_fifths' (-S_3L / (eps r) per separation).  It reads U and U_hat only; every other output is unchanged."""
     from mpi4py_fft_amd import PFFT, _lib, newDistArray, spectral
+    assert structure is None or fused, 'structure needs the fused path'
     assert not pdfs or (gradients and fused), 'pdfs needs gradients=True and the fused path'
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -394,6 +409,30 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             else:
                 bwd(uh[i], u[i])
 
+    sf_log = []
+
+    def structure_diag(n):
+        """after step n (1-based): the structure functions of U along the chosen axis, when the interval says so"""
+        if structure is None:
+            return
+        axis, per_octave = int(structure[0]), int(structure[1])
+        every = int(structure[2]) if len(structure) > 2 else nsteps
+        if n % every and n != nsteps:
+            return
+        seps = spectral.log_separations(N[axis], per_octave)
+        sf = ops.structure_functions(U, axis, seps, lcomp=axis)              # rank-reduced; one read of U for all separations
+        mo = spectral.structure_moments(sf, N[0] * N[1] * N[2], axis=axis)
+        eps = 2.0 * nu * float(ops.spectrum(U_hat)[1].sum())
+        r = np.array(seps) * (L[axis] / N[axis])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            ratio = -mo.S[:, axis, 2] / (eps * r)
+        sf_log.append(dict(step=n, r=r, moments=mo, eps=eps, four_fifths=ratio))
+        if verbose and world.Get_rank() == 0:
+            print('  structure functions along axis %d after step %d: eps = %.6e, flatness of the longitudinal increment at r = %.4f: %.4f'
+                  % (axis, n, eps, r[0], mo.flatness[0, axis]))
+            for k in range(len(seps)):
+                print('    r = %8.4f  S_2L = %.6e  -S_3L / (eps r) = % .4e' % (r[k], mo.S[k, axis, 1], ratio[k]))
+
     if graph:
         # One RK4 step is ~130 small kernels at 64^3: launch bound.  Every kernel of this package
         # is enqueued on torch's current stream and nothing allocates or synchronises after the
@@ -426,11 +465,15 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             dt_dev.zero_()
         torch.cuda.synchronize()
         t0 = time.time()
-        for _ in range(nsteps):
+        for n in range(nsteps):
             g.replay()
+            structure_diag(n + 1)
     else:
-        for _ in range(nsteps):
+        for n in range(nsteps):
             step()
+            structure_diag(n + 1)
+    if structure is not None and stats is not None:
+        stats.update(structure=sf_log)
     if adaptive:
         st = ops.stats(U)                                     # rank-reduced; one read of U, no temporaries
         energy = float(sum(st[2 + 6 * c + 3] for c in range(3))) / (2.0 * N[0] * N[1] * N[2])
@@ -638,6 +681,12 @@ if __name__ == '__main__':
         sg = {}
         solve(w, verbose=True, particles=(1000, 4, 7), dealias='2/3', stats=sg, graph=True)
         assert np.array_equal(sg['particles'], sp['particles'])
+    ss = {}
+    es = solve(w, verbose=True, structure=(2, 2), dealias='2/3', stats=ss)            # two-point statistics along z: one read of U
+    assert abs(es - DEALIASED_ENERGY) <= 1e-9 and len(ss['structure']) == 1, (es, ss)
+    mo = ss['structure'][0]['moments']
+    # (the vortex is 2 pi-periodic in z in a box of 4 pi: at the largest separation, N / 2 points = 2 pi, the increments vanish to rounding)
+    assert mo.longitudinal == 2 and np.all(mo.S[:-1, :2, 1] > 0) and np.all(np.isfinite(ss['structure'][0]['four_fifths'])), mo
     if len(sys.argv) > 1:                       # e.g. `dns_taylor_green.py 8` for 256^3 timings
         for f in (True, False):
             solve(w, M=int(sys.argv[1]), nsteps=5, verbose=True, fused=f)

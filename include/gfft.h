@@ -708,6 +708,56 @@ int gfft_ps_spread(int64_t *d_acc /* [ncomp][n[0]][n[1]][n[2]], ADDED to */, int
 int gfft_ps_spread_finish(void *d_out /* [count] real of `precision` */, int64_t *d_acc /* [count] */, int64_t count,
                           double factor, int clear, int precision, void *stream);
 
+/* ---- two-point statistics in physical space: structure functions along a grid axis ----------
+ *   gfft_ps_structure   the power sums of the increments of a real field over a list of separations along one periodic axis,
+ *                    the field read from memory ONCE for all separations.  d_u = real [ncomp][n[0]][n[1]][n[2]], contiguous, of
+ *                    `precision`: a block that spans the WHOLE periodic axis `axis` (n[axis] is that axis's period; the other
+ *                    two axes may be any part of the grid); sep[0 .. nsep - 1] (host) = the separations in grid points, 0 <=
+ *                    sep[k] < n[axis]; lcomp = the component that serves as the longitudinal velocity of the mixed moment,
+ *                    or -1 for none; d_out = double [nsep][ncomp][GFFT_PS_SF_NVAL], OVERWRITTEN.
+ *                    THE DEFINITION, for every point x of the block, separation k and component c, in double, every value
+ *                    converted before any arithmetic:
+ *                      a  = (double)u[c][x]
+ *                      b  = (double)u[c][x'],   x' = x with index[axis] replaced by (index[axis] + sep[k]) mod n[axis]
+ *                      d  = b - a
+ *                      d2 = d*d    d3 = d2*d    d4 = d2*d2    d5 = d4*d    d6 = d3*d3
+ *                      ad = fabs(d)    ad3 = d2*ad
+ *                      mx = dl*d2      dl = the d of component lcomp at the same x and k
+ *                                      (lcomp = -1: the entry is +0.0 and nothing is formed)
+ *                      out[k][c][GFFT_PS_SF_D1 ... GFFT_PS_SF_MIX] = the sums over x of  d, d2, d3, d4, d5, d6, ad, ad3, mx
+ *                    With u a velocity and c = lcomp = axis, D3 carries the 4/5 law; summed over c, MIX is <du_L |du|^2> of
+ *                    the 4/3 law; with c a scalar it is <du_L dtheta^2> of Yaglom's law.  Whether a product is contracted
+ *                    into its accumulation is not part of the definition: a sum lies within (count + 16) 2^-53 M of the
+ *                    exact one, count = n[0] n[1] n[2] and M the same expression over |a|, |b| with the subtraction turned
+ *                    into an addition.  THE SUMMATION ORDER is fixed, so the result repeats bit for bit for the same array,
+ *                    geometry (n, axis, ncomp, nsep, precision) and 16-byte alignment of d_u.  The lines of `axis` are
+ *                    cut into tiles of whole lines (axis 2: consecutive lines; axis 0 or 1: for one index of the axes in
+ *                    front, a power-of-two run of consecutive columns of the axes behind), tile t served by workgroup
+ *                    t mod nwg of 256 lanes; a tile's points are numbered p in its staging order (axis 2: memory order;
+ *                    else [index along axis][column]); per tile and separation
+ *                      1. lane l adds its points p = l, l + 256, ... in that order, from +0.0;
+ *                      2. the 64 lanes of a wave combine by the butterfly lane ^ 32, 16, 8, 4, 2, 1;
+ *                      3. the 4 waves add in wave order, and the result is added to the workgroup's running sum, tile
+ *                         after tile in the order t = w, w + nwg, ...;
+ *                    and last, per (k, c, value), lane l of one workgroup adds the workgroups' sums w = l, l + 256, ... in that
+ *                    order, then 2. and 3.  No floating-point atomics.
+ *                    A NaN (or an infinity, whose difference with itself is NaN) reaches exactly the sums it enters: the
+ *                    sums of its own component at every separation, and the MIX entries of every component if it lies in
+ *                    component lcomp.  sep = 0 gives zeros for a finite field (d = a - a).  A block with count == 0 gives
+ *                    zeros and launches only the final combination.  Every index that reaches a load has gone through the
+ *                    integer wrap.  The workgroups' sums live in the stream's shared scratch (at most 4 MiB): the first
+ *                    call allocates, later ones only enqueue, so a captured call allocates nothing.
+ *                    GFFT_ERR_INVALID (before a device is touched) for a null pointer, ncomp < 1, nsep < 1, an axis
+ *                    outside 0 .. 2, a negative n, a sep outside [0, n[axis]), lcomp outside [-1, ncomp), precision;
+ *                    GFFT_ERR_UNSUPPORTED for ncomp > 4, nsep > 64, n[axis] > 4096 (a workgroup stages whole lines of all
+ *                    components in LDS: 128 KiB at 4096 x 4 doubles) and a block of more than 2^40 points.  Only enqueues. */
+enum { GFFT_PS_SF_D1 = 0, GFFT_PS_SF_D2 = 1, GFFT_PS_SF_D3 = 2, GFFT_PS_SF_D4 = 3, GFFT_PS_SF_D5 = 4, GFFT_PS_SF_D6 = 5,
+       GFFT_PS_SF_ABS1 = 6, GFFT_PS_SF_ABS3 = 7, GFFT_PS_SF_MIX = 8, GFFT_PS_SF_NVAL = 9 };
+enum { GFFT_PS_SF_MAX_SEP = 64, GFFT_PS_SF_MAX_AXIS = 4096 };
+int gfft_ps_structure(const void *d_u /* [ncomp][n[0]][n[1]][n[2]] real */, int ncomp, const int64_t n[3], int axis,
+                      int nsep, const int32_t *sep /* host */, int lcomp /* -1: none */,
+                      double *d_out /* [nsep][ncomp][GFFT_PS_SF_NVAL], overwritten */, int precision, void *stream);
+
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:
  *   gfft_comm_create / gfft_comm_split  <- MPI_Cart_create + MPI_Cart_sub   mpi4py_fft/pencil.py:64-93

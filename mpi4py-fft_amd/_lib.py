@@ -25,6 +25,9 @@ PS_PDF_TAIL = 3                         # behind the bins of a 1-D histogram: [b
 PS_Q_NONE = -1                          # gfft_ps_gradient_pdf's quantities, named as in gfft_ps_gradient_stats
 PS_Q_SS, PS_Q_WW, PS_Q_DIV, PS_Q_Q, PS_Q_R, PS_Q_SSS, PS_Q_WSW, PS_Q_COUNT = range(8)
 PS_PDF_MAX_BINS, PS_PDF_MAX_JOINT = 4096, 16384      # bins of a 1-D table (per component) and of a joint one
+PS_SF_NVAL = 9                          # gfft_ps_structure's output: double[nsep][ncomp][PS_SF_NVAL], indexed by the names below
+SF_D1, SF_D2, SF_D3, SF_D4, SF_D5, SF_D6, SF_ABS1, SF_ABS3, SF_MIX = range(PS_SF_NVAL)
+PS_SF_MAX_SEP, PS_SF_MAX_AXIS = 64, 4096             # separations per call; the longest axis a workgroup stages
 
 _lib = None
 
@@ -104,6 +107,7 @@ def _declare(lib):
                                           c.c_double, c.c_double, c.c_int, c.c_int, c.c_int, c.c_int, c.c_double, vp, c.c_int, vp]),
         'gfft_ps_gradient': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_int64, c.c_int64, c.c_int64, c.c_int, vp]),
         'gfft_ps_gradient_stats': (c.c_int, [vp, c.c_int64, vp, c.c_int, vp]),
+        'gfft_ps_structure': (c.c_int, [vp, c.c_int, i64p, c.c_int, c.c_int, c.POINTER(c.c_int32), c.c_int, vp, c.c_int, vp]),
         'gfft_ps_histogram': (c.c_int, [vp, c.c_int, c.c_int64, c.POINTER(c.c_double), c.POINTER(c.c_double), c.c_int, vp,
                                         c.c_int, vp]),
         'gfft_ps_gradient_pdf': (c.c_int, [vp, c.c_int64, c.c_int, c.c_double, c.c_double, c.c_int, c.c_int, c.c_double,
@@ -581,6 +585,16 @@ class HipEngine:
         self.require_device(ta)
         self.require_device(tout)
         check(lib().gfft_ps_gradient_stats(ta.data_ptr(), int(count), tout.data_ptr(), precision, current_stream()))
+
+    def ps_structure(self, tu, ncomp, n, axis, seps, lcomp, tout, precision):
+        """gfft_ps_structure: tu = real [ncomp] + n, a block that spans the whole periodic axis `axis`; seps = host integers in
+        [0, n[axis]); lcomp = the longitudinal component of the mixed moment or -1; tout = double[len(seps)][ncomp][PS_SF_NVAL]
+        on the device, overwritten with the power sums of the increments."""
+        self.require_device(tu)
+        self.require_device(tout)
+        sp = (ctypes.c_int32 * len(seps))(*[int(r) for r in seps])
+        check(lib().gfft_ps_structure(tu.data_ptr(), int(ncomp), _i64(n), int(axis), len(seps), sp, int(lcomp), tout.data_ptr(),
+                                      precision, current_stream()))
 
     def ps_histogram(self, tu, ncomp, count, lo, hi, nbins, tout, precision):
         """gfft_ps_histogram: tu = real [ncomp][count]; lo, hi = ncomp host floats each; tout = int64[ncomp][nbins + PS_PDF_TAIL]

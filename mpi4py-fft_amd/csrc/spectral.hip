@@ -15,7 +15,9 @@
 //     and ps_interp_kernel (a gather: order^2 lanes per particle, trilinear or cubic B-spline, periodic, block by block);
 //   * its transpose, particle to grid: ps_spread_kernel (a scatter with the same weights, every contribution rounded once to
 //     64-bit fixed point and added by an integer atomic: order-independent to the last bit) and ps_spread_finish_kernel
-//     (pointwise: the integers to reals, and the accumulator cleared).
+//     (pointwise: the integers to reals, and the accumulator cleared);
+//   * two-point statistics: ps_structure_kernel (the power sums of the increments along a grid axis at up to 64 separations:
+//     tiles of whole lines staged once in LDS, the separations looped over the staged tile; fixed-order sums, sf_reduce_kernel).
 #include "../../include/gfft.h"
 #include "gfft_internal.h"
 
@@ -602,6 +604,8 @@ ps_spectrum_sum_kernel(const double *__restrict__ slabs, int nwg, int n, double 
 // ps_histogram_kernel<double, 2, NC = 1 ... 4> 54, 58, 60, 64 and <float, 4, NC> the same (8 waves per SIMD), one element per lane 54 ... 64;
 // ps_gradient_pdf_kernel<double, 2, 1-D / joint> 78 / 84 (6 / 5 waves per SIMD) and <float, 4, .> 92 / 98 (5 / 4 waves), <., 1, .> 58 / 62 (8 waves);
 // pd_sum_kernel 48 (8 waves).
+// ps_structure_kernel<double, 2, NC = 1 ... 4> 56, 76, 96, 117 and <float, 4, NC> 56, 76, 94, 116 (8, 6, 5, 4 waves per SIMD by registers;
+// its LDS tile allows 2 workgroups = 2 waves per SIMD), one element per staging load 54 / 74 / 94 / 115 and 54 / 74 / 94 / 114; sf_reduce_kernel 9.
 constexpr int ST_MAX_COMP = 4;
 constexpr int ST_HEAD = GFFT_PS_STATS_HEAD, ST_PER_COMP = GFFT_PS_STATS_PER_COMP;
 enum { ST_MAX0 = 0, ST_MAX = 1, ST_MIN = 2, ST_SUM = 3 };
@@ -683,12 +687,14 @@ ps_stats_kernel(const real *__restrict__ u, int64_t count, int64_t chunk, st_sca
 // out[i] = the nwg workgroup values of slot i combined in the fixed order above; workgroup i of the launch owns value i
 // (nwg == 0, an empty block: the identities 0, -inf, +inf, 0).  At most 8 dependent loads per lane, not 2048.
 // (KIND: the kind map of the caller's values -- st_kind here, gs_kind for the gradient statistics)
+// (stride: the slots of one value in the slabs -- SP_MAX_WG, or what ps_structure_kernel's launch used)
 template <int (*KIND)(int)>
-__device__ __forceinline__ void st_reduce_value(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+__device__ __forceinline__ void st_reduce_value(const double *__restrict__ slabs, int nwg, double *__restrict__ out,
+                                                int stride = SP_MAX_WG) {
   __shared__ double part[PS_THREADS / 64];
   const int i = blockIdx.x, kind = KIND(i);
   double r = st_identity(kind);
-  for (int w = threadIdx.x; w < nwg; w += PS_THREADS) r = st_combine(kind, r, slabs[(int64_t)i * SP_MAX_WG + w]);
+  for (int w = threadIdx.x; w < nwg; w += PS_THREADS) r = st_combine(kind, r, slabs[(int64_t)i * stride + w]);
   r = st_wave(kind, r);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r;
   __syncthreads();
@@ -1856,6 +1862,273 @@ int ps_shell(const char *fn, bool bad, const void *d_a_hat, const void *d_b_hat,
   return GFFT_OK;
 }
 
+// ---- structure functions: the power sums of the increments u(x + r e_axis) - u(x), every separation from one read of u -----
+// Definition, summation order and properties: include/gfft.h (gfft_ps_structure).  A workgroup takes tiles of WHOLE lines of
+// `axis`, all NC components, staged once in LDS in the field's precision; the separations are the OUTER loop over the staged
+// tile, so the field leaves HBM once per call and every partner is an LDS read.  Tiles (sf_geometry):
+//   axis 2      W consecutive lines -- one contiguous run of W L elements per component, LDS point p = its offset in the run;
+//   axis 0, 1   for one index of the axes in front, W = 2^w <= 256 adjacent columns of the axes behind: L rows of W
+//               contiguous elements, LDS point p = row W + column (a ragged last tile leaves its missing columns unused).
+// Either way consecutive lanes read consecutive LDS words for x and, but for the one place where the line wraps, for its
+// partner: no bank conflicts.  A lane walks p = lane, lane + 256, ... and carries its index along the axis with it
+// (+ 256 mod L, or + 256 / W): no division in the loop, and the partner is p + ((i + s) mod L - i) x (1 or W), the wrap an
+// integer compare on an index < 2 L.  A tile holds SF_TILE_BYTES (two workgroups per CU) or one line if that is longer,
+// fewer where the block is small (sf_geometry), never fewer than SF_MIN_POINTS points: the reduction after each separation
+// is paid per tile.  As 9 NC plain butterflies it cost more than the tile's arithmetic (256^3, m = 3, fp64, 14 separations:
+// 2.29 ms); sf_wave_sums forms the same sums with a fifth of the exchanges (0.95 ms).  NC is a template parameter so that the
+// 9 NC accumulators of a lane are registers; the per-separation results accumulate in LDS (nsep x 9 NC doubles), thread v
+// owning value v, and go to slot [k][c][value][workgroup] of the slabs at the end; sf_reduce_kernel is st_reduce_value over
+// all nsep x 9 NC values.  At most sf_max_wg workgroups (512 = the two per CU that fit; fewer beyond 1024 values per
+// workgroup: the slabs stay within 4 MiB); they take the tiles t = w, w + nwg, ...
+// Measured (tools/structure_probe.py; 256^3, m = 3): one separation reads the field at 0.40 - 0.53 (fp64) and
+// 0.31 - 0.35 (fp32) of the copy's rate (2 waves per SIMD; staging and arithmetic overlap only between the two workgroups of a
+// CU); at 14 separations the pass (1.0 - 1.1 ms in fp64) is bound by the fp64 arithmetic and the LDS reads at that occupancy,
+// not by HBM.  Tiles of 32 KiB on 1024 workgroups and of 48 KiB on 768 were measured too (the kernel alone, back to back): no
+// faster at 14 separations (0.98 - 1.14 and 0.95 - 0.97 ms against 0.87 - 0.95), and the smaller tile's 32-byte rows along
+// axis 0 and 1 cost 70 % at one separation.
+// (Registers: in the list above ps_stats_kernel; no instantiation spills or uses scratch.)
+constexpr int SF_NVAL = GFFT_PS_SF_NVAL, SF_MAX_COMP = 4, SF_MAX_SEP = GFFT_PS_SF_MAX_SEP, SF_MAX_AXIS = GFFT_PS_SF_MAX_AXIS;
+constexpr int SF_TILE_BYTES = 64 * 1024, SF_MIN_POINTS = 1024;
+constexpr int SF_MAX_WG = 512, SF_SLAB_VALUES = 1024;
+constexpr size_t SF_MAX_LDS = 156 * 1024;            // dynamic; 2 x 4 x 36 doubles of static LDS beside it
+static_assert((size_t)SF_MAX_AXIS * SF_MAX_COMP * sizeof(double) + (size_t)SF_MAX_SEP * SF_MAX_COMP * SF_NVAL * sizeof(double) <= SF_MAX_LDS,
+              "the longest line of four doubles and the running sums fit");
+
+struct sf_seps { int32_t v[SF_MAX_SEP]; };           // by value in the launch
+
+struct sf_geom {
+  int L;               // n[axis]
+  int rows;            // 0: axis 2, a tile is one contiguous run; 1: axis 0 or 1, a tile is L rows of W columns
+  int V;               // elements per staging load: those of 16 bytes, or 1
+  int W;               // lines (axis 2) or columns (axis 0, 1: a power of two) of a full tile
+  int row_shift;       // staging: point p lies in row p >> row_shift (axis 2: one row, shift 30)
+  int pstride;         // LDS points between components (a multiple of 4)
+  int istride;         // LDS points between neighbours along the axis: 1 or W
+  int istep;           // a lane's index along the axis grows by this (mod L) per step of 256 points
+  int nwg;
+  int64_t nb;          // axis 0, 1: column tiles per index of the axes in front
+  int64_t lines;       // axis 2: lines of the block; axis 0, 1: columns per index of the axes in front
+  int64_t row_stride;  // axis 0, 1: elements between neighbours along the axis
+  int64_t count;       // elements between components
+  int64_t ntiles;
+  size_t lds;
+};
+
+inline int sf_max_wg(int nvalues) {
+  return nvalues <= SF_SLAB_VALUES ? SF_MAX_WG : (int)((int64_t)SF_MAX_WG * SF_SLAB_VALUES / nvalues);
+}
+
+sf_geom sf_geometry(const int64_t n[3], int axis, int ncomp, int nsep, int precision, bool aligned16) {
+  sf_geom g = {};
+  g.L = (int)n[axis];
+  g.count = n[0] * n[1] * n[2];
+  if (!g.count) return g;
+  const int wide = 16 / precision, max_wg = sf_max_wg(nsep * ncomp * SF_NVAL);
+  const int64_t cap = SF_TILE_BYTES / (ncomp * precision);      // points per component in SF_TILE_BYTES
+  int64_t points;
+  if (axis == 2) {
+    const int64_t lines = n[0] * n[1];
+    // a small block: no more lines than hand every workgroup a tile, but SF_MIN_POINTS points; always one whole line
+    const int64_t spread = (lines + max_wg - 1) / max_wg, least = (SF_MIN_POINTS + g.L - 1) / g.L;
+    int64_t W = cap / g.L;
+    if (W > (spread > least ? spread : least)) W = spread > least ? spread : least;
+    if (W > lines) W = lines;
+    if (W < 1) W = 1;
+    g.V = ps_lane_width(g.L, wide, aligned16);
+    g.rows = 0, g.W = (int)W, g.row_shift = 30, g.istride = 1, g.istep = PS_THREADS % g.L;
+    g.nb = 1, g.lines = lines, g.row_stride = 0;
+    g.ntiles = (lines + W - 1) / W;
+    points = W * g.L;
+  } else {
+    const int64_t inner = axis == 1 ? n[2] : n[1] * n[2], outer = axis == 1 ? n[0] : 1;
+    int W = PS_THREADS, lg = 8;
+    while (W > 1 && ((int64_t)W * g.L > cap || W / 2 >= inner)) W >>= 1, --lg;
+    while (W > 16 && (int64_t)(W / 2) * g.L >= SF_MIN_POINTS && outer * ((inner + W - 1) / W) < max_wg) W >>= 1, --lg;
+    g.V = W >= wide ? ps_lane_width(inner, wide, aligned16) : 1;
+    g.rows = 1, g.W = W, g.row_shift = lg, g.istride = W, g.istep = PS_THREADS / W;
+    g.nb = (inner + W - 1) / W, g.lines = inner, g.row_stride = inner;
+    g.ntiles = outer * g.nb;
+    points = (int64_t)W * g.L;
+  }
+  g.pstride = (int)((points + 3) & ~(int64_t)3);
+  g.nwg = (int)(g.ntiles < max_wg ? g.ntiles : max_wg);
+  g.lds = (size_t)ncomp * g.pstride * precision + (size_t)nsep * ncomp * SF_NVAL * sizeof(double);
+  return g;
+}
+
+__host__ __device__ constexpr int sf_kind(int) { return ST_SUM; }
+
+// The butterfly of st_wave for N sums at once.  At the step with the partner lane ^ m a lane keeps the half of its values that
+// bit m of its number selects and hands the partner the other half: what a lane forms is own + partner's, the very a + b both
+// partners of the plain butterfly form, so every sum is the plain butterfly's to the last bit -- but N values padded to
+// P = 2^p cost about P exchanges, not 6 N (27 values: 32 against 162).  sf_fold: one such step over the LIVE values left, H of
+// them kept; afterwards v[0] is the value number `idx` of the lane, summed over the masks taken so far.
+template <int H, int LIVE, int N>
+__device__ __forceinline__ void sf_fold(double (&v)[N], int lane, int m, int &idx) {
+  if constexpr (H >= 1) {
+    constexpr int KEPT = LIVE < H ? LIVE : H;
+    const bool up = (lane & m) != 0;
+#pragma unroll
+    for (int j = 0; j < KEPT; ++j) {
+      const double hi = j + H < LIVE ? v[j + H] : 0.0;
+      const double keep = up ? hi : v[j], give = up ? v[j] : hi;
+      v[j] = keep + __shfl_xor(give, m);
+    }
+    if (up) idx += H;
+    sf_fold<H / 2, KEPT, N>(v, lane, m >> 1, idx);
+  }
+}
+
+// the wave's sums of v[0 ... N - 1]: afterwards value number `idx` (if < N) stands in every lane that returns it -- the lanes
+// that differ only in the bits `low` -- summed by lane ^ 32, 16, 8, 4, 2, 1 in that order
+template <int N>
+__device__ __forceinline__ double sf_wave_sums(double (&v)[N], int lane, int &idx, int &low) {
+  constexpr int P = N <= 16 ? 16 : N <= 32 ? 32 : 64;
+  static_assert(N <= 64, "one value per lane at the most");
+  idx = 0;
+  sf_fold<P / 2, N, N>(v, lane, 32, idx);
+  double r = v[0];
+#pragma unroll
+  for (int m = 32 / P; m >= 1; m >>= 1) r += __shfl_xor(r, m);
+  low = 64 / P - 1;
+  return r;
+}
+
+template <typename real, int V, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_structure_kernel(const real *__restrict__ u, sf_geom g, sf_seps seps, int nsep, int lcomp, double *__restrict__ slabs) {
+  constexpr int NVAL = SF_NVAL * NC;
+  extern __shared__ __attribute__((aligned(16))) unsigned char sf_lds[];
+  __shared__ double sf_part[2][PS_THREADS / 64][NVAL];
+  real *tile = reinterpret_cast<real *>(sf_lds);                                   // [NC][pstride]
+  double *acc = reinterpret_cast<double *>(sf_lds + (size_t)NC * g.pstride * sizeof(real));   // [nsep][NVAL], thread v owns value v
+  const int tid = threadIdx.x, L = g.L, ps = g.pstride;
+  const bool rows = g.rows != 0;                             // axis 0 or 1
+  const int rmask = (1 << g.row_shift) - 1;
+  const int i0 = rows ? tid >> g.row_shift : tid % L;        // the lane's first index along the axis, the same in every tile
+  for (int i = tid; i < nsep * NVAL; i += PS_THREADS) acc[i] = 0.0;
+  for (int64_t t = blockIdx.x; t < g.ntiles; t += gridDim.x) {
+    // the tile: its first element, its valid columns per staging row, its LDS points
+    int64_t base;
+    int ncol, plimit;
+    if (rows) {
+      const int64_t o = t / g.nb, j0 = (t - o * g.nb) * g.W;
+      base = o * L * g.row_stride + j0;
+      ncol = (int)(g.lines - j0 < g.W ? g.lines - j0 : g.W);
+      plimit = L << g.row_shift;
+    } else {
+      const int64_t l0 = t * g.W;
+      base = l0 * L;
+      ncol = (int)(g.lines - l0 < g.W ? g.lines - l0 : g.W) * L;
+      plimit = ncol;
+    }
+    const int cmask = rows ? rmask : 0, cvalid = rows ? ncol : 1;      // point p is one of the block iff (p & cmask) < cvalid
+    __syncthreads();                                         // the tile before is done with
+    for (int p = tid * V; p < plimit; p += PS_THREADS * V) {
+      const int row = p >> g.row_shift, col = p & rmask;
+      if (col < ncol) {                                      // (ncol, col and every base are multiples of V: all V or none)
+        const real *src = u + base + row * g.row_stride + col;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          *reinterpret_cast<st_load<real, V> *>(tile + c * ps + p) = *reinterpret_cast<const st_load<real, V> *>(src + c * g.count);
+      }
+    }
+    __syncthreads();
+    for (int k = 0; k < nsep; ++k) {
+      const int s = seps.v[k];
+      double val[NVAL];
+#pragma unroll
+      for (int i = 0; i < NVAL; ++i) val[i] = 0.0;
+      int ia = i0;
+      for (int p = tid; p < plimit; p += PS_THREADS) {
+        if ((p & cmask) < cvalid) {
+          int ib = ia + s;
+          if (ib >= L) ib -= L;                              // the integer wrap: 0 <= ia, s < L
+          const int q = p + (ib - ia) * g.istride;
+          double d[NC], dl = 0.0;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const double a = tile[c * ps + p], b = tile[c * ps + q];       // converted before any arithmetic
+            d[c] = b - a;
+            if (c == lcomp) dl = d[c];
+          }
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            double *v = val + SF_NVAL * c;
+            const double d1 = d[c], d2 = d1 * d1, d3 = d2 * d1, d4 = d2 * d2, ad = fabs(d1);
+            v[GFFT_PS_SF_D1] += d1;
+            v[GFFT_PS_SF_D2] += d2;
+            v[GFFT_PS_SF_D3] += d3;
+            v[GFFT_PS_SF_D4] += d4;
+            v[GFFT_PS_SF_D5] += d4 * d1;
+            v[GFFT_PS_SF_D6] += d3 * d3;
+            v[GFFT_PS_SF_ABS1] += ad;
+            v[GFFT_PS_SF_ABS3] += d2 * ad;
+            if (lcomp >= 0) v[GFFT_PS_SF_MIX] += dl * d2;
+          }
+        }
+        ia += g.istep;
+        if (ia >= L) ia -= L;
+      }
+      double(&part)[PS_THREADS / 64][NVAL] = sf_part[k & 1];   // two buffers: one barrier per separation
+      int slot, low;
+      const double w = sf_wave_sums(val, tid & 63, slot, low);
+      if (slot < NVAL && (tid & low) == 0) part[tid >> 6][slot] = w;
+      __syncthreads();
+      if (tid < NVAL) {
+        double r = part[0][tid];
+        for (int w = 1; w < PS_THREADS / 64; ++w) r += part[w][tid];
+        acc[k * NVAL + tid] += r;
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nsep * NVAL; i += PS_THREADS) slabs[(int64_t)i * gridDim.x + blockIdx.x] = acc[i];
+}
+
+__global__ void __launch_bounds__(PS_THREADS)
+sf_reduce_kernel(const double *__restrict__ slabs, int nwg, double *__restrict__ out) {
+  st_reduce_value<sf_kind>(slabs, nwg, out, nwg);
+}
+
+inline size_t sf_scratch_bytes(int nvalues) { return (size_t)sf_max_wg(nvalues) * nvalues * sizeof(double); }
+
+template <typename real, int V, int NC>
+hipError_t sf_launch(const void *u, const sf_geom &g, const sf_seps &seps, int nsep, int lcomp, double *slabs, hipStream_t s) {
+  // beyond 64 KiB of dynamic LDS a kernel has to be told once per device
+  static bool attr_set[kMaxDevices] = {};
+  const int dev = current_device();
+  if (g.lds > 48 * 1024 && !attr_set[dev]) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&ps_structure_kernel<real, V, NC>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)SF_MAX_LDS);
+    if (e != hipSuccess) return e;
+    attr_set[dev] = true;
+  }
+  return ps_launch(ps_structure_kernel<real, V, NC>, g.nwg, g.lds, s, u, g, seps, nsep, lcomp, slabs);
+}
+
+template <typename real, int V>
+hipError_t sf_launch_nc(int ncomp, const void *u, const sf_geom &g, const sf_seps &seps, int nsep, int lcomp, double *slabs, hipStream_t s) {
+  return ncomp == 1 ? sf_launch<real, V, 1>(u, g, seps, nsep, lcomp, slabs, s)
+       : ncomp == 2 ? sf_launch<real, V, 2>(u, g, seps, nsep, lcomp, slabs, s)
+       : ncomp == 3 ? sf_launch<real, V, 3>(u, g, seps, nsep, lcomp, slabs, s)
+                    : sf_launch<real, V, 4>(u, g, seps, nsep, lcomp, slabs, s);
+}
+
+// 1 <= ncomp <= SF_MAX_COMP, 1 <= nsep <= SF_MAX_SEP, 0 <= sep < n[axis] <= SF_MAX_AXIS; `slabs` = sf_scratch_bytes of stream-ordered scratch
+hipError_t launch_ps_structure(const void *u, int ncomp, const int64_t n[3], int axis, const sf_seps &seps, int nsep, int lcomp,
+                               double *out, double *slabs, int precision, hipStream_t s) {
+  const sf_geom g = sf_geometry(n, axis, ncomp, nsep, precision, (uintptr_t)u % 16 == 0);
+  const hipError_t e = !g.nwg ? hipSuccess : by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    constexpr int W = 16 / sizeof(real);
+    return g.V == W ? sf_launch_nc<real, W>(ncomp, u, g, seps, nsep, lcomp, slabs, s)
+                    : sf_launch_nc<real, 1>(ncomp, u, g, seps, nsep, lcomp, slabs, s);
+  });
+  if (e != hipSuccess) return e;
+  return ps_launch(sf_reduce_kernel, nsep * ncomp * SF_NVAL, 0, s, slabs, g.nwg, out);
+}
+
 }  // namespace
 
 }  // namespace gfft
@@ -2105,6 +2378,33 @@ int gfft_ps_gradient_stats(const void *d_A, int64_t count, double *d_out, int pr
   rc = scratch_get((hipStream_t)stream, ST_SCRATCH_BYTES, &slabs);
   if (rc) return rc;
   HIP_TRY(launch_ps_gradient_stats(d_A, count, d_out, static_cast<double *>(slabs), precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_structure(const void *d_u, int ncomp, const int64_t n[3], int axis, int nsep, const int32_t *sep, int lcomp,
+                      double *d_out, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_spectrum)
+  if (!d_u || !n || !sep || !d_out || ncomp < 1 || nsep < 1 || axis < 0 || axis > 2 || n[0] < 0 || n[1] < 0 || n[2] < 0 ||
+      lcomp < -1 || lcomp >= ncomp || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_structure: bad argument");
+  static_assert(SF_MAX_COMP == 4 && SF_MAX_SEP == 64 && SF_MAX_AXIS == 4096, "the messages name the limits");
+  if (ncomp > SF_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_structure: more than 4 components");
+  if (nsep > SF_MAX_SEP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_structure: more than 64 separations");
+  sf_seps seps = {};
+  for (int k = 0; k < nsep; ++k) {
+    if (sep[k] < 0 || sep[k] >= n[axis]) return fail(GFFT_ERR_INVALID, "gfft_ps_structure: a separation must lie in [0, n[axis])");
+    seps.v[k] = sep[k];
+  }
+  if (n[axis] > SF_MAX_AXIS) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_structure: axis longer than 4096 (a workgroup stages whole lines)");
+  if ((double)n[0] * (double)n[1] * (double)n[2] > 0x1p40) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_structure: more than 2^40 points");
+  int rc = check_device();
+  if (rc) return rc;
+  // the workgroups' sums live in the stream's shared scratch: the first call allocates, later ones only enqueue
+  void *slabs = nullptr;
+  rc = scratch_get((hipStream_t)stream, sf_scratch_bytes(nsep * ncomp * SF_NVAL), &slabs);
+  if (rc) return rc;
+  HIP_TRY(launch_ps_structure(d_u, ncomp, n, axis, seps, nsep, lcomp, d_out, static_cast<double *>(slabs), precision,
+                              (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -91,6 +91,18 @@ and the distributions those moments compress -- integer counts from one read, ex
                                 without fused multiply-adds so that the counts equal a numpy restatement exactly
     pdf(counts, range), joint_pdf(counts, ranges, bins)   bin centres, the density and the shares outside the range
 
+and the two-point statistics in physical space -- the structure functions S_p(r) = <(u(x + r e_a) - u(x))^p>, of which only
+p = 2 can be had from the transforms: the exact laws a run is validated against (4/5, 4/3, Yaglom) and the exponents and
+increment flatness by which intermittency is reported; every separation from ONE read of the field:
+
+    structure_functions(u, axis, seps, lcomp)   per separation and component the sums of d, ..., d^6, |d|, |d|^3 and d_l d^2 of
+                                the increments along a grid axis this rank holds whole (m <= 4 components, up to 64
+                                separations, axis <= 4096): whole lines staged once in LDS, the separations looped over them;
+                                bit for bit repeatable, added over the ranks in rank order
+    log_separations(N, per_octave)   1, 2, 3, 4, 6, 8, 12, ... <= N // 2
+    structure_moments(sf, npoints, axis)   S_1 ... S_6, <|d|>, <|d|^3>, increment skewness and flatness, the mixed moment, and
+                                which component is longitudinal
+
 and the fields where no grid point is -- tracer particles, probes, a line or a plane that is not a grid plane: B-spline
 interpolation (van Hinsberg et al. 2012), whose coefficients cost a spectral code one pointwise pass:
 
@@ -910,6 +922,60 @@ class SpectralOps:
         _lib.engine().ps_timestep(st, cfl, dt_min, dt_max, out)
         return out
 
+    def whole_axes(self):
+        """The axes of the physical grid that this rank holds whole: all three on one rank, 1 and 2 on a slab grid, 2 on a
+        pencil grid."""
+        return [a for a in range(3) if self.pshape[a] == self._N[a]]
+
+    def structure_functions(self, u, axis, seps, lcomp=None, out=None, reduce=True):
+        """The power sums of the increments d = u_c(x + r e_axis) - u_c(x) of a real physical-space field, for every
+        separation r of `seps` (grid points, 0 <= r < N[axis], at most 64) from ONE read of the field: float64 [nsep][m][9],
+        indexed by `_lib.SF_*`,
+            [0 ... 5] sum d, d^2, d^3, d^4, d^5, d^6   [6] sum |d|   [7] sum |d|^3   [8] sum d_l d^2, d_l the increment of
+        component `lcomp` at the same point (lcomp None: zeros).  With u a velocity and lcomp = axis, [axis][2] is the sum
+        behind the 4/5 law, [8] summed over the components that behind the 4/3 law, and [8] of a scalar carried as a fourth
+        component that behind Yaglom's law (`structure_moments` divides by the number of points and forms the ratios;
+        include/gfft.h has the exact expressions).  u is as in `stats`: [m] + fft.shape(False), m <= 4, or a scalar field.
+        Every value is converted to double first; a NaN reaches exactly the sums of its own component (and the [8] of every
+        component if it lies in `lcomp`).
+
+        The axis must be whole on this rank (`whole_axes`): all three axes on one rank, axes 1 and 2 on a slab grid, axis
+        2 on a pencil grid, and at most 4096 points long.  Increments across rank boundaries need halos or a transposed copy
+        of the field; that is not done here.
+
+        `reduce` and `out` as in `stats`: reduce=True adds the ranks of the grid on the host in rank order, one grid axis
+        after the other, so every rank holds identical bits, which synchronises; reduce=False only enqueues and returns the
+        device tensor (`out`, a contiguous double tensor [nsep][m][9], or a new one), so it can be captured after one call
+        outside the capture.  The result repeats bit for bit from one call to the next: the summation order is fixed."""
+        t, ncomp, precision = self._real_field(u)
+        axis = int(axis)
+        assert 0 <= axis <= 2, axis
+        assert self.pshape[axis] == self._N[axis], \
+            'structure_functions needs an axis that is whole on this rank: axis %d is split, the whole axes of this grid are %s' % (
+                axis, self.whole_axes())
+        seps = [int(r) for r in seps]
+        assert 1 <= len(seps) <= _lib.PS_SF_MAX_SEP, 'structure_functions takes 1 ... %d separations' % _lib.PS_SF_MAX_SEP
+        assert all(0 <= r < self._N[axis] for r in seps), 'a separation must lie in [0, %d)' % self._N[axis]
+        lcomp = -1 if lcomp is None else int(lcomp)
+        assert -1 <= lcomp < ncomp, lcomp
+        shape = (len(seps), ncomp, _lib.PS_SF_NVAL)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=t.device)
+        assert tuple(out.shape) == shape and out.dtype == torch.float64 and out.is_contiguous()
+        _lib.engine().ps_structure(t, ncomp, self.pshape, axis, seps, lcomp, out, precision)
+        return self._reduce_sums(out) if reduce else out
+
+    def _reduce_sums(self, out):
+        """`_reduce_stats` for a table of sums only"""
+        vals = out.cpu().numpy()                       # (waits for the kernels)
+        _lib.check_async()
+        for c in self.comms:                           # one grid axis after the other: the same order on every rank
+            parts = c.allgather_obj(vals)
+            vals = parts[0].copy()
+            for p in parts[1:]:
+                vals = vals + p
+        return vals
+
 
 # Classical RK4 on v = exp(lambda t) u_hat, lambda = nu |K|^2, written for u_hat itself; E = exp(-lambda h / 2).  Rows
 # (cb, ca, q0, qd, q1, qa) of `SpectralOps.rk_stage_if`; u0 = u1 = u_n before row 1, which turns u1 into E^2 u_n; row 4 is
@@ -990,6 +1056,49 @@ def gradient_moments(gs, npoints, nu=None):
             dissipation_flatness=float((s[_lib.GS_SS2] / n) / (ss * ss)), enstrophy_flatness=float((s[_lib.GS_WW2] / n) / (ww * ww)),
             strain_enstrophy_correlation=float((s[_lib.GS_SSWW] / n) / (ss * ww)),
             betchov=float(np.float64(s[_lib.GS_WSW]) / (-4.0 / 3.0 * s[_lib.GS_SSS])), div_rms=float(np.sqrt(s[_lib.GS_DIV2] / n)))
+
+
+def log_separations(N, per_octave=2):
+    """The separations of a structure function on a periodic axis of N points: the increasing integers 1, 2, 3, 4, 6, 8, 12,
+    ... <= N // 2: `per_octave` evenly spaced per factor of two, 2^k (1 + i / per_octave) for i < per_octave, rounded half up
+    and deduplicated.  Plain Python integers."""
+    N, per_octave = int(N), int(per_octave)
+    assert per_octave >= 1
+    top, out, octave = N // 2, [], 1
+    while octave <= top:
+        for i in range(per_octave):
+            r = (2 * octave * (per_octave + i) + per_octave) // (2 * per_octave)       # floor(octave (1 + i / p) + 1 / 2)
+            if r <= top and (not out or r > out[-1]):
+                out.append(r)
+        octave *= 2
+    return out
+
+
+StructureMoments = collections.namedtuple('StructureMoments', 'S abs1 abs3 skewness flatness mixed longitudinal transverse')
+StructureMoments.__doc__ = """What `structure_moments` returns, every array [nsep][m] but S: S = [nsep][m][6], S[..., p - 1] = <d^p> for
+p = 1 ... 6; abs1 = <|d|>, abs3 = <|d|^3>; skewness = S_3 / S_2^(3/2) and flatness = S_4 / S_2^2 of the increments (0 and 3 for a
+Gaussian); mixed = <d_l d^2>; longitudinal = the index of the component along the axis and transverse = the others, or None
+without an axis or with fewer than three components."""
+
+
+def structure_moments(sf, npoints, axis=None):
+    """The structure functions from `SpectralOps.structure_functions` (rank-reduced) and the GLOBAL number of points, as a
+    `StructureMoments`.  With axis = a and m >= 3 component a is labelled longitudinal: S[k, a, 2] / (eps r_k) -> -4/5 in an
+    inertial range, and mixed[k, :3].sum() / (eps r_k) -> -4/3 when the table was formed with lcomp = a.  A ratio whose
+    denominator vanishes (r = 0) is nan or inf, as in `moments`.  Host numpy."""
+    s = np.asarray(sf, dtype=np.float64)
+    assert s.ndim == 3 and s.shape[2] == _lib.PS_SF_NVAL, s.shape
+    m = s / float(npoints)
+    S = m[..., _lib.SF_D1:_lib.SF_D6 + 1]
+    s2 = S[..., 1]
+    lon = tra = None
+    if axis is not None and s.shape[1] >= 3:
+        lon = int(axis)
+        assert 0 <= lon <= 2, axis
+        tra = [c for c in range(3) if c != lon]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return StructureMoments(S=S, abs1=m[..., _lib.SF_ABS1], abs3=m[..., _lib.SF_ABS3], skewness=S[..., 2] / s2 ** 1.5,
+                                flatness=S[..., 3] / (s2 * s2), mixed=m[..., _lib.SF_MIX], longitudinal=lon, transverse=tra)
 
 
 Pdf = collections.namedtuple('Pdf', 'centres density below above nan')
