@@ -108,7 +108,23 @@ int gfft_plan_create_r2r(gfft_plan *plan, int ndims, const int64_t *sizes, int n
 /* out = scale * DFT(in).  d_in == d_out is allowed for C2C and real-to-real plans.  Every
  * out-of-place execution PRESERVES its input -- part of the contract: multi-axis C2R (where FFTW
  * destroys the input) routes its complex passes through the workspace, and the Python host relies
- * on it when it reads a caller's array in place (Transform.__call__). */
+ * on it when it reads a caller's array in place (Transform.__call__).
+ * Footprint: an execution reads nothing outside the plan's input array that any output depends on and writes
+ * nothing outside its output array (and the library's own workspace): tests/test_gpu_guard_*.py hold both.
+ * Base alignment: d_in and d_out must each be aligned as ONE ELEMENT of their array -- `precision` bytes for a
+ * real array, 2 * precision for a complex one -- and need no more: a view that starts at any element of a larger
+ * allocation is a valid argument and gives the bits of an aligned one.  (Every kernel addresses its arrays
+ * element by element; the compiler widens accesses only where the hardware takes them at any alignment.)  One
+ * exception: a REAL plan that runs a fused pass pair (gfft_plan_create_guru2_real where it has fused kernels; the
+ * [r2c rows -> strided] / [strided -> c2r rows] pairs of a multi-axis gfft_plan_create plan, option fuse2_kinds
+ * bits 32 / 64) streams its real side as complex pairs: that side must be aligned to 2 * precision bytes, whether
+ * or not the pair is still fused.  GFFT_ERR_INVALID, with the requirement in gfft_last_error(), otherwise; nothing
+ * is enqueued.
+ * In place (d_in == d_out): real r2c / c2r plans refuse it.  So does a complex plan whose two sides are laid out
+ * differently -- one side re-laid-out by gfft_plan_set_split / gfft_plan_set_tiles / gfft_plan_set_flat with a body
+ * width, blocks on one side of a guru plan, a fused truncation / zero padding (gfft_plan_set_truncation,
+ * gfft_plan_create_guru_padded) --: a workgroup loads a whole tile before it stores it, which makes in-place
+ * execution safe exactly when every tile writes the addresses it read.  GFFT_ERR_INVALID; nothing is enqueued. */
 int gfft_execute(gfft_plan plan, const void *d_in, void *d_out, double scale, void *stream);
 int gfft_plan_destroy(gfft_plan plan);
 int gfft_scratch_release(void);           /* frees the shared per-stream workspaces, pinned ones included */
@@ -269,7 +285,13 @@ int gfft_plan_cost(gfft_plan plan, double *flops, double *bytes, int *launches);
  * An array of shape `shape[ndims]` is cut along `axis` into `nparts` blocks by the reference's
  * block rule (pencil.py:5-9).  pack: block i is copied, in row-major order of the sub-block, to
  * d_packed + offset_i (offset_i = itemsize * prod(other dims) * start_i), i.e. the send buffer of
- * an all-to-all.  unpack is the inverse (receive buffer -> array).  itemsize in bytes (4,8,16). */
+ * an all-to-all.  unpack is the inverse (receive buffer -> array).  itemsize in bytes (4,8,16).
+ * Base alignment of these and of gfft_truncate / gfft_pad / gfft_scale below: every array as ONE of its items
+ * (itemsize bytes here; 2 * precision for the complex arrays of gfft_truncate / gfft_pad; precision for
+ * gfft_scale), GFFT_ERR_INVALID otherwise -- and no more: a view into a larger allocation is a valid argument.
+ * gfft_pack / gfft_unpack move 16 bytes per lane where both bases are 16-byte aligned and a row of the inner
+ * dims is a multiple of 16 bytes, one item per lane otherwise, with the same result.  The two arrays must not
+ * overlap.  Nothing outside the `prod(shape)` items of either array is read or written. */
 int gfft_pack(const void *d_array, void *d_packed, int ndims, const int64_t *shape, int axis,
               int nparts, int itemsize, void *stream);
 int gfft_unpack(const void *d_packed, void *d_array, int ndims, const int64_t *shape, int axis,

@@ -90,6 +90,31 @@ int normalise_axis(int *a, int ndims, std::vector<char> *seen) {
 // slots of the line's kernel -- R = 4 (n = 16), 8 or 16 (other powers of two), 12 / 20 (3^b 2^k / 5^c 2^k)
 int max_split_blocks(int64_t n) { return is_pow2(n) ? (n >= 32 ? 8 : 4) : 4; }
 
+// d_in == d_out: a workgroup loads its whole tile before it stores it, so a pass from the caller's input to the caller's
+// output may run in place exactly when every tile writes the addresses it read.  That holds for the natural layouts and
+// for the same re-laid-out form on both sides; it fails where gfft_plan_set_split / _set_tiles / _set_flat (body + leftover
+// columns), guru blocks or a fused truncation / zero padding give the two sides different places for the same entry.
+// (`in` is the pass that reads the caller's input, `out` the one that writes the caller's output: the same PassDesc, or the
+// two halves of a fused pair.)
+bool same_relayout(const PassDesc &in, const PassDesc &out) {
+  return in.in_lgp == out.out_lgp && in.in_jump == out.out_jump && in.in_tlg == out.out_tlg && in.in_tS == out.out_tS &&
+         in.in_ilg == out.out_ilg && in.in_iS == out.out_iS && !in.tr_dir && !out.tr_dir && !in.tr_jump && !out.tr_jump &&
+         !in.ub_p && !out.ub_p && !in.fl_bw && !out.fl_bw;
+}
+bool in_place_ok(const gfft_plan_s *pl) {
+  for (const Pass &p : pl->passes) {
+    if (p.kind == PK_FUSED2 && p.src == BUF_IN && p.dst == BUF_OUT && !same_relayout(p.d, p.d2)) return false;
+    if (p.kind == PK_FFT && p.src == BUF_IN && p.dst == BUF_OUT && (!same_relayout(p.d, p.d) || p.blocks[0] != p.blocks[1] || p.bstride[0] != p.bstride[1]))
+      return false;
+  }
+  return true;
+}
+
+std::string misaligned(const char *name, size_t need, bool as_pair) {
+  return std::string(name) + " must be aligned to " + std::to_string(need) + " bytes (" +
+         (as_pair ? "a fused real pass pair addresses its real side as complex pairs" : "one element of the array") + ")";
+}
+
 }  // namespace
 
 gfft::Options::Options() {
@@ -344,6 +369,22 @@ int gfft_execute(gfft_plan pl, const void *d_in, void *d_out, double scale, void
   if (current_device() != pl->device) return fail(GFFT_ERR_INVALID, "the plan was made on another device than the calling thread's current one");
   if ((pl->kind == GFFT_R2C || pl->kind == GFFT_C2R) && d_in == d_out)
     return fail(GFFT_ERR_INVALID, "in-place real transforms are not supported");
+  if (d_in == d_out && !in_place_ok(pl))
+    return fail(GFFT_ERR_INVALID, "in-place execution needs the same layout on both sides (this plan re-lays one side out: a tile would overwrite input that another tile has yet to read)");
+  {
+    // Base alignment (include/gfft.h).  The kernels address their arrays element by element -- cx<real> is two reals and is
+    // aligned as ONE --, so an array need only be aligned as an element of its own type.  The exceptions are the non-temporal
+    // streams (fft_pow2_impl.h ldc / stc), typed as a vector of two reals: on a complex array that is the element again; the
+    // real side of a fused real pair, which they read / write as complex pairs, must be aligned as a pair.
+    const size_t prec = (size_t)pl->precision;
+    const bool in_real = pl->kind == GFFT_R2C || pl->kind == GFFT_R2R, out_real = pl->kind == GFFT_C2R || pl->kind == GFFT_R2R;
+    bool pair = false;
+    for (const Pass &q : pl->passes) pair = pair || q.kind == PK_FUSED2;
+    const bool pair_in = pair && pl->kind == GFFT_R2C, pair_out = pair && pl->kind == GFFT_C2R;
+    const size_t a_in = (in_real && !pair_in) ? prec : 2 * prec, a_out = (out_real && !pair_out) ? prec : 2 * prec;
+    if ((uintptr_t)d_in % a_in) return fail(GFFT_ERR_INVALID, misaligned("d_in", a_in, pair_in));
+    if ((uintptr_t)d_out % a_out) return fail(GFFT_ERR_INVALID, misaligned("d_out", a_out, pair_out));
+  }
   if (!pl->fused_off && pl->async_slot < 0) {
     bool any = false;
     for (const Pass &q : pl->passes) any = any || q.kind == PK_FUSED2;
@@ -962,6 +1003,14 @@ int gfft_plan_cost(gfft_plan pl, double *flops, double *bytes, int *launches) {
   return GFFT_OK;
 }
 
+// the data-movement kernels address whole items: both arrays aligned as one (include/gfft.h)
+static int check_items(const void *a, const void *b, int itemsize) {
+  if (itemsize != 4 && itemsize != 8 && itemsize != 16) return fail(GFFT_ERR_INVALID, "itemsize must be 4, 8 or 16");
+  if (((uintptr_t)a | (uintptr_t)b) % (uintptr_t)itemsize)
+    return fail(GFFT_ERR_INVALID, "arrays must be aligned to " + std::to_string(itemsize) + " bytes (one element)");
+  return GFFT_OK;
+}
+
 static int collapse(int ndims, const int64_t *shape, int axis, int64_t *outer, int64_t *naxis, int64_t *inner) {
   if (!shape || ndims < 1 || axis < 0 || axis >= ndims) return fail(GFFT_ERR_INVALID, "bad shape/axis");
   *outer = *inner = 1;
@@ -977,6 +1026,7 @@ int gfft_pack(const void *d_array, void *d_packed, int ndims, const int64_t *sha
   int rc = collapse(ndims, shape, axis, &o, &n, &i);
   if (rc) return rc;
   if (nparts < 1 || n < nparts) return fail(GFFT_ERR_INVALID, "axis shorter than the number of parts");
+  if ((rc = check_items(d_array, d_packed, itemsize))) return rc;
   if ((rc = check_device())) return rc;
   HIP_TRY(launch_pack(d_array, d_packed, o, n, i, nparts, itemsize, false, (hipStream_t)stream));
   return GFFT_OK;
@@ -988,6 +1038,7 @@ int gfft_unpack(const void *d_packed, void *d_array, int ndims, const int64_t *s
   int rc = collapse(ndims, shape, axis, &o, &n, &i);
   if (rc) return rc;
   if (nparts < 1 || n < nparts) return fail(GFFT_ERR_INVALID, "axis shorter than the number of parts");
+  if ((rc = check_items(d_packed, d_array, itemsize))) return rc;
   if ((rc = check_device())) return rc;
   HIP_TRY(launch_pack(d_packed, d_array, o, n, i, nparts, itemsize, true, (hipStream_t)stream));
   return GFFT_OK;
@@ -999,6 +1050,7 @@ int gfft_truncate(const void *d_padded, void *d_trunc, int ndims, const int64_t 
   int rc = collapse(ndims, shape_padded, axis, &o, &n, &i);
   if (rc) return rc;
   if (n_trunc < 1 || n_trunc > n) return fail(GFFT_ERR_INVALID, "bad truncated length");
+  if ((rc = check_precision(precision)) || (rc = check_items(d_padded, d_trunc, 2 * precision))) return rc;
   if ((rc = check_device())) return rc;
   HIP_TRY(launch_trunc(d_padded, d_trunc, o, n, n_trunc, i, is_real, precision, scale, false, (hipStream_t)stream));
   return GFFT_OK;
@@ -1010,14 +1062,16 @@ int gfft_pad(const void *d_trunc, void *d_padded, int ndims, const int64_t *shap
   int rc = collapse(ndims, shape_padded, axis, &o, &n, &i);
   if (rc) return rc;
   if (n_trunc < 1 || n_trunc > n) return fail(GFFT_ERR_INVALID, "bad truncated length");
+  if ((rc = check_precision(precision)) || (rc = check_items(d_trunc, d_padded, 2 * precision))) return rc;
   if ((rc = check_device())) return rc;
   HIP_TRY(launch_trunc(d_trunc, d_padded, o, n, n_trunc, i, is_real, precision, 1.0, true, (hipStream_t)stream));
   return GFFT_OK;
 }
 
 int gfft_scale(void *d_data, int64_t count, int precision, double scale, void *stream) {
-  int rc = check_device();
-  if (rc) return rc;
+  int rc = check_precision(precision);
+  if (rc || (rc = check_items(d_data, d_data, precision))) return rc;
+  if ((rc = check_device())) return rc;
   HIP_TRY(launch_scale(d_data, count, precision, scale, (hipStream_t)stream));
   return GFFT_OK;
 }

@@ -47,6 +47,14 @@ def aligned(shape, n=32, dtype=np.dtype('d'), fill=None):
     return a
 
 
+def pair_aligned(a):
+    """The base of device array `a` is aligned as a complex pair of its precision: what gfft_execute accepts for EVERY plan
+    (include/gfft.h: one element of the array, but a complex pair on the real side of a fused real pass pair).  A real view
+    that starts at an odd element of its allocation is not; the callers that run plans directly on a caller's array copy
+    such a view into the planned array instead."""
+    return a.data_ptr % (a.itemsize * (2 if a.dtype.kind == 'f' else 1)) == 0
+
+
 def aligned_like(z, fill=None):
     return aligned(z.shape, n=get_alignment(z), dtype=z.dtype, fill=fill)
 
@@ -158,7 +166,7 @@ class FFT:
 
     def _compatible(self, a, shape, strides, dtype):
         return (isinstance(a, DeviceArray) and tuple(a.shape) == shape and a.strides == strides
-                and a.dtype == dtype and a.is_contiguous())
+                and a.dtype == dtype and a.is_contiguous() and pair_aligned(a))
 
     def __call__(self, input_array=None, output_array=None, implicit=True, normalize=False, **kw):
         """Execute.  implicit=True runs directly on the given arrays when they match the planned

@@ -21,6 +21,7 @@ from .array import DeviceArray
 from .libfft import FFT
 from .pencil import Pencil, Subcomm
 from . import comm as _comm
+from . import fftw
 
 
 class Transform:
@@ -131,10 +132,11 @@ class Transform:
 
     @staticmethod
     def _direct(arr, ref):
-        """A caller's device array that a kernel can read / write in place of the planned one."""
+        """A caller's device array that a kernel can read / write in place of the planned one (its base aligned as
+        gfft_execute asks of any plan, fftw.pair_aligned: a real view from an odd element on is copied instead)."""
         return (isinstance(arr, DeviceArray) and arr is not ref and arr.data_ptr != ref.data_ptr
                 and tuple(arr.shape) == tuple(ref.shape) and arr.dtype == ref.dtype
-                and arr.is_contiguous() and arr.device == ref.device)
+                and arr.is_contiguous() and arr.device == ref.device and fftw.pair_aligned(arr))
 
     def stage_times(self):
         """One synchronised execution on the planned arrays, timed stage by stage:

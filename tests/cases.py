@@ -272,17 +272,19 @@ def check_redistribute_chain(rng, mid=False):
     return True
 
 
-def impulse_errors(n, dt, strided, positions=None, lines=16):
+def impulse_errors(n, dt, strided, positions=None, lines=19):
     """Twiddle integrity of ONE serial plan of length n: line b of a batch holds a unit impulse at position j_b, so its
     transform is X_b[k] = exp(-2 pi i j_b k / n) -- every output a bare product of the plan's twiddle factors, of modulus
     1: a wrong table entry shows at full size in the outputs it feeds (random data dilutes it by ~1 / (3.5 sqrt(radix)),
-    below fp32 rounding for an entry off by 1e-5).  Returns (max |forward - exact|, max |backward(exact) - impulse|),
-    in units of 1 (no normalisation needed: |X| = 1, impulse height 1)."""
+    below fp32 rounding for an entry off by 1e-5).  `lines` lines, the positions taken cyclically: 19 by default, no
+    multiple of a kernel tile (T = 1 ... 16 rows, 2 ... 32 columns), so the tail tile of every kernel is among them.
+    Returns (max |forward - exact|, max |backward(exact) - impulse|), in units of 1 (no normalisation needed: |X| = 1,
+    impulse height 1)."""
     from mpi4py_fft_amd import FFT, asdevice
     cdt = 'D' if dt in 'dD' else 'F'
     if positions is None:
         positions = [1, 2, 3, 5, 7, n // 2 + 1, n - 1, n // 3 + 1, n // 4 + 1, 11 % n, n // 5 + 2, n // 7 + 3, 1, n - 2, 13 % n, n // 2 - 1]
-    positions = [int(j) % n for j in positions][:lines]
+    positions = [int(positions[b % len(positions)]) % n for b in range(lines)]
     B = len(positions)
     shape, axis = ((n, B), 0) if strided else ((B, n), 1)
     x = np.zeros(shape, dtype=cdt)
