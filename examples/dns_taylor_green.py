@@ -93,7 +93,7 @@ PDF_BINS, PDF_R, PDF_Q, PDF_SIGMAS = 128, 4.0, 6.0, 6.0     # solve(pdfs=True): 
 
 def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True, graph=False, spectrum=False,
           transfer=False, stats=None, cfl=None, device_dt=False, forcing=None, device_gain=False, dealias=None,
-          scalar=None, integrator='rk4', gradients=False, pdfs=False, particles=None, structure=None):
+          scalar=None, integrator='rk4', gradients=False, pdfs=False, particles=None, structure=None, init=None):
     """Returns the kinetic energy after `nsteps`; with spectrum=True, (energy, E) where E is the shell spectrum
     `SpectralOps.spectrum` of the final U_hat: E[0] = E(k), E[1] = k^2 E(k), shells of width min(2 pi / L).
     With transfer=True (fused path), (energy, T) where T is `SpectralOps.transfer(U_hat, N_hat)` of the final state,
@@ -143,9 +143,22 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     (default nsteps: the final state only), from the U the step leaves in physical space.  A dict passed as `stats` receives
     'structure', a list with one dict per evaluation: 'step', 'r' (the separations in length units), 'moments' (the
     `spectral.structure_moments` with the longitudinal component labelled), 'eps' (2 nu sum k^2 E(k) of `SpectralOps.spectrum`)
-    and 'four_fifths' (-S_3L / (eps r) per separation).  It reads U and U_hat only; every other output is unchanged."""
+    and 'four_fifths' (-S_3L / (eps r) per separation).  It reads U and U_hat only; every other output is unchanged.
+    init=('random', seed, k_peak, u_rms) (fused path): start from `SpectralOps.random_field` -- a random-phase solenoidal field
+    whose shell spectrum is `spectral.model_spectrum(..., 'gaussian', k_peak, u_rms)` exactly, the same on any number of ranks --
+    instead of the Taylor-Green vortex (None, the default).
+    forcing=('white', eps, blo, bhi) (fused path, not under graph=True: the scale is formed on the host): after every step
+    `SpectralOps.white_noise_force` adds a fresh random solenoidal field in shells blo..bhi that carries exactly eps h of energy
+    (stream = the step number, seed = init's seed or 0).  A dict passed as `stats` receives 'white_factor', the last scale."""
     from mpi4py_fft_amd import PFFT, _lib, newDistArray, spectral
     assert structure is None or fused, 'structure needs the fused path'
+    assert init is None or (init[0] == 'random' and len(init) == 4 and fused), "init = None or ('random', seed, k_peak, u_rms) on the fused path"
+    white = forcing is not None and forcing[0] == 'white'
+    if white:
+        assert fused and not graph and len(forcing) == 4, "forcing=('white', eps, blo, bhi) needs the fused path without graph=True"
+        w_eps, w_band, w_seed = float(forcing[1]), (int(forcing[2]), int(forcing[3])), (int(init[1]) if init is not None else 0)
+        w_step, w_factor = [0], [0.0]
+        forcing = None
     assert not pdfs or (gradients and fused), 'pdfs needs gradients=True and the fused path'
     N = [2 ** M] * 3
     L = np.array([2 * np.pi, 4 * np.pi, 4 * np.pi])
@@ -309,10 +322,16 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
     u[2] = 0
     for i in range(3):
         fwd(u[i], uh[i])
+    if init is not None:
+        ops.random_field(U_hat, spectral.model_spectrum(ops.shells(ops.default_nbins()), 'gaussian', float(init[2]), float(init[3])),
+                         seed=int(init[1]))
     if dealias and fused:
         ops.dealias(U_hat, mask)
     elif dealias:
         uh.masked_fill_(~keep, 0)
+    if init is not None:                                      # U is what the first step's controller and diagnostics read
+        for j in range(3):
+            FFT.backward(U_hat[j], U[j])
     if scalar is not None:
         th.copy_(torch.cos(X[0]) * torch.sin(X[1] / 2) * torch.cos(X[2] / 2))
         fwd(th, tht)
@@ -399,6 +418,9 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
                     torch.add(Xp0, dXp, alpha=b[rk] * dt, out=Xp)
                 Xp1.add_(dXp, alpha=a[rk] * dt)
         uh.copy_(uh1)
+        if white:                                             # dU is free between steps: the unscaled random band field
+            w_factor[0] = ops.white_noise_force(U_hat, dU, w_step[0], w_eps, h, w_band, w_seed)
+            w_step[0] += 1
         if particles is not None:
             Xp.copy_(Xp1)
         if scalar is not None:
@@ -474,6 +496,8 @@ def solve(world, M=6, nsteps=10, dt=0.01, nu=0.000625, verbose=False, fused=True
             structure_diag(n + 1)
     if structure is not None and stats is not None:
         stats.update(structure=sf_log)
+    if white and stats is not None:
+        stats.update(white_factor=w_factor[0])
     if adaptive:
         st = ops.stats(U)                                     # rank-reduced; one read of U, no temporaries
         energy = float(sum(st[2 + 6 * c + 3] for c in range(3))) / (2.0 * N[0] * N[1] * N[2])

@@ -780,6 +780,54 @@ int gfft_ps_structure(const void *d_u /* [ncomp][n[0]][n[1]][n[2]] real */, int 
                       int nsep, const int32_t *sep /* host */, int lcomp /* -1: none */,
                       double *d_out /* [nsep][ncomp][GFFT_PS_SF_NVAL], overwritten */, int precision, void *stream);
 
+/* ---- random fields: initial conditions and white-in-time forcing, keyed by the global mode index ----------
+ *   gfft_ps_random_field   fills (add == 0) or adds to (add != 0) the complex field d_out[ncomp][n[0]][n[1]][n[2]] of `precision`,
+ *                    the block start[a] .. start[a] + n[a] of a spectral array over the global physical grid N (a real
+ *                    transform stores indices 0 .. N[2]/2 of the last axis; no flag tells the layouts apart), with
+ *                    independent complex Gaussian modes of a prescribed amplitude per shell that obey u(-k) = conj u(k)
+ *                    exactly.  d_k0/1/2 = the block's wavenumber vectors in the field's precision; d_amp = device
+ *                    double[nbins] or NULL (every amplitude 1).  1 <= ncomp <= 4.
+ *                    THE DEFINITION, per stored mode with global index g = start + i, in this order:
+ *                      mirror     m = ((N0 - g0) % N0, (N1 - g1) % N1, (N2 - g2) % N2);  lin(g) = (g0 N1 + g1) N2 + g2 in
+ *                                 uint64;  c = min(lin(g), lin(m));  the mode is a MIRROR MODE iff lin(m) < lin(g)
+ *                      zeroed     g = 0; 2 g_a == N_a on any axis (a Nyquist index: K(m) != -K(g) there, and no self-
+ *                                 conjugate mode is left once these are gone); b >= nbins, b = floor(|k| / dk + 0.5) the
+ *                                 shell gfft_ps_spectrum bins by (a NaN shell too); amp[b] == 0.  A zeroed mode is stored
+ *                                 as +0, or with `add` left untouched; nothing is drawn for it
+ *                      uniforms   per component comp one Philox4x32-10 call, counter (c lo32, c hi32, stream_id lo32,
+ *                                 (stream_id >> 32) << 2 | comp), key (seed lo32, seed hi32), words r0 .. r3:
+ *                                 u1 = (((r1 << 32 | r0) >> 12) + 0.5) 2^-52, u2 the same from (r3, r2): exact doubles in (0, 1)
+ *                      Gaussians  rho = sqrt(-2 log u1);  G_comp = rho (cos 2 pi u2 + i sin 2 pi u2)   (sincospi(2 u2)), in
+ *                                 double whatever the precision; each part a standard normal
+ *                      project    (project != 0, which needs ncomp == 3) per part, in double with the block's K converted
+ *                                 first and nothing contracted:  p = ((kx G0 + ky G1) + kz G2) / |k|^2,  G_j = G_j - k_j p,
+ *                                 |k|^2 = (kx kx + ky ky) + kz kz (0 -> 1).  E |u|^2 summed over the components is then 4 amp^2
+ *                      store      each part times amp[b]; the imaginary part negated for a mirror mode; rounded ONCE to
+ *                                 `precision`; stored, or with `add` added in `precision` to what is there
+ *                    K(m) = -K(g) exactly on the surviving modes and K enters only through products of two K's, so a mirror
+ *                    mode is bit for bit the conjugate of its partner: the physical field is real, the r2c field is the
+ *                    stored half of the c2c field, and a mode's value does not depend on the block that holds it.  Against
+ *                    the exact value of the definition a part lies within 20 x 2^-53 amp ||G||_2 (log, sqrt and sincospi at
+ *                    their documented 1, 1 and 2 ulp and the roundings above; tests/random_ref.py derives it).
+ *                    Pointwise, no atomics, no scratch; an empty block launches nothing.  GFFT_ERR_INVALID (before a
+ *                    device is touched) for a null pointer (d_amp excepted), ncomp outside 1 .. 4, project with ncomp != 3,
+ *                    nbins < 1, dk <= 0, n < 0, N < 1, start < 0, start + n > N, stream_id >= 2^62, precision;
+ *                    GFFT_ERR_UNSUPPORTED for n[1] or n[2] > 2^30 and a grid of more than 2^60 points.  Only enqueues.
+ *   gfft_ps_scale_shells   the isotropic counterpart of gfft_ps_scale_axes: out[c][i0][i1][i2] = f_hat[c][i0][i1][i2] *
+ *                    (real)tab[b] with b the shell above, d_tab = device double[nbins]; the real and the imaginary part are
+ *                    each ONE multiply, bit for bit a host restatement.  A mode with b >= nbins (a NaN shell too) is stored
+ *                    as +0 whatever f_hat holds there.  d_out == d_f_hat (in place) is allowed; any other overlap is not.
+ *                    Sharp and Gaussian LES filters, a rescale to an exact spectrum.  GFFT_ERR_INVALID for a null pointer,
+ *                    ncomp < 1, nbins < 1, dk <= 0, a negative size, precision; GFFT_ERR_UNSUPPORTED for ncomp > 4 and an
+ *                    axis longer than 2^30.  Only enqueues. */
+int gfft_ps_random_field(void *d_out /* [ncomp][n[0]][n[1]][n[2]] complex */, int ncomp, const int64_t n[3],
+                         const int64_t start[3], const int64_t N[3], const void *d_k0, const void *d_k1, const void *d_k2,
+                         int project, double dk, const double *d_amp /* [nbins] or NULL */, int nbins, uint64_t seed,
+                         uint64_t stream_id /* < 2^62 */, int add, int precision, void *stream);
+int gfft_ps_scale_shells(void *d_out, const void *d_f_hat /* [ncomp][n0][n1][n2] complex */, int ncomp, const void *d_k0,
+                         const void *d_k1, const void *d_k2, double dk, const double *d_tab /* [nbins] */, int nbins,
+                         int64_t n0, int64_t n1, int64_t n2, int precision, void *stream);
+
 /* ---- the wire of a global redistribution: RCCL over xGMI -------------------------------------
  * Replaces, for device buffers, what the reference gets from MPI on its Cartesian sub-communicators:
  *   gfft_comm_create / gfft_comm_split  <- MPI_Cart_create + MPI_Cart_sub   mpi4py_fft/pencil.py:64-93

@@ -116,6 +116,10 @@ def _declare(lib):
         'gfft_ps_interp': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, c.POINTER(c.c_double), vp, c.c_int64, c.c_int, vp, c.c_int, vp]),
         'gfft_ps_spread': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, c.POINTER(c.c_double), vp, vp, c.c_int64, c.c_int, c.c_int, vp, vp]),
         'gfft_ps_spread_finish': (c.c_int, [vp, vp, c.c_int64, c.c_double, c.c_int, c.c_int, vp]),
+        'gfft_ps_random_field': (c.c_int, [vp, c.c_int, i64p, i64p, i64p, vp, vp, vp, c.c_int, c.c_double, vp, c.c_int, c.c_uint64,
+                                           c.c_uint64, c.c_int, c.c_int, vp]),
+        'gfft_ps_scale_shells': (c.c_int, [vp, vp, c.c_int, vp, vp, vp, c.c_double, vp, c.c_int, c.c_int64, c.c_int64, c.c_int64,
+                                           c.c_int, vp]),
         'gfft_debug_pass': (c.c_int, [i64p, c.c_int, c.c_int, c.c_int, c.c_int, vp, vp, vp]),
         'gfft_malloc': (c.c_int, [c.POINTER(vp), c.c_size_t]),
         'gfft_free': (c.c_int, [vp]),
@@ -595,6 +599,27 @@ class HipEngine:
         sp = (ctypes.c_int32 * len(seps))(*[int(r) for r in seps])
         check(lib().gfft_ps_structure(tu.data_ptr(), int(ncomp), _i64(n), int(axis), len(seps), sp, int(lcomp), tout.data_ptr(),
                                       precision, current_stream()))
+
+    def ps_random_field(self, tout, ncomp, n, start, N, k, project, dk, tamp, nbins, seed, stream_id, add, precision):
+        """gfft_ps_random_field: tout = complex [ncomp] + n, the block start .. start + n of a spectral array over the physical
+        grid N, filled with (add: added to by) random modes keyed by their global index; k = the block's three wavenumber
+        vectors; tamp = device double[nbins] or None (every amplitude 1); seed below 2^64, stream_id below 2^62."""
+        self.require_device(tout)
+        if tamp is not None:
+            self.require_device(tamp)
+        check(lib().gfft_ps_random_field(tout.data_ptr(), int(ncomp), _i64(n), _i64(start), _i64(N), k[0].data_ptr(), k[1].data_ptr(),
+                                         k[2].data_ptr(), int(bool(project)), float(dk), None if tamp is None else tamp.data_ptr(),
+                                         int(nbins), int(seed), int(stream_id), int(bool(add)), precision, current_stream()))
+
+    def ps_scale_shells(self, tf, tout, ncomp, k, dk, ttab, nbins, shape, precision):
+        """gfft_ps_scale_shells: tout[c] = tf[c] * (real)ttab[shell] on complex [ncomp] + shape, +0 where the shell is >= nbins;
+        ttab = device double[nbins]; tout is tf or overlaps nothing."""
+        self.require_device(tf)
+        self.require_device(tout)
+        self.require_device(ttab)
+        check(lib().gfft_ps_scale_shells(tout.data_ptr(), tf.data_ptr(), int(ncomp), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(),
+                                         float(dk), ttab.data_ptr(), int(nbins), shape[0], shape[1], shape[2], precision,
+                                         current_stream()))
 
     def ps_histogram(self, tu, ncomp, count, lo, hi, nbins, tout, precision):
         """gfft_ps_histogram: tu = real [ncomp][count]; lo, hi = ncomp host floats each; tout = int64[ncomp][nbins + PS_PDF_TAIL]

@@ -1455,6 +1455,226 @@ ps_spread_finish_kernel(real *__restrict__ out, int64_t *__restrict__ acc, int64
   }
 }
 
+// ---- random fields: a counter-based generator keyed by the GLOBAL mode index ------------------------------------------------
+// gfft_ps_random_field; the definition, operation by operation, is in include/gfft.h.  A mode's value is a function of its
+// global index, the seed and the stream alone: not of the block it lies in, of the lane that forms it or of the precision
+// before the one rounding at the store.  A mode and its mirror draw from the SAME counter (the smaller of their two linear
+// indices) and the wavenumbers enter only through products of two of them, so the mirror's value is bit for bit the conjugate.
+// Pointwise, grid-stride over the block, a lane's modes V neighbours along i2 (16 bytes per store: one mode in fp64, two in
+// fp32 where n2 is even and the base is 16-byte aligned, else one); no LDS, no atomics, no scratch.  Everything between the
+// Philox words and the store is double, and the projection is compiled without contraction: one defined sequence of roundings
+// in every instantiation, so the fp32 field is the fp64 field rounded once.
+// Without `project` the components are taken in turn (ncomp at run time, one log / sqrt / sincospi chain live); with it the
+// three of a mode are live together.  The launch is capped at RF_MAX_WG workgroups, 8 per CU: the arithmetic, not the stores,
+// is what a lane spends its time on, so a lane walks several modes rather than the grid growing with the block.
+// (Registers, hipcc -O3, gfx950: ps_random_field_kernel<double, 1, projected / plain> 66 / 78 VGPRs, <float, 1, .> 66 / 78,
+// <float, 2, .> 98 / 92 -- 7 / 6 and 4 / 5 waves per SIMD; no instantiation uses scratch or spills a VGPR; the projected ones park 42 to 57
+// scalar registers in lanes of a VGPR.  ps_scale_shells_kernel<double, 1, NC = 1 ... 4> 26, 28, 30, 34, <float, 2, NC> 32, 32, 38, 44,
+// <float, 1, NC> 26, 28, 26, 26: 8 waves per SIMD.)
+constexpr int RF_MAX_COMP = 4;
+constexpr int RF_MAX_WG = 2048;
+
+struct rf_dims { int64_t n1, n2, s0, s1, s2, N0, N1, N2; };          // block rows, block offset, global grid
+
+// counter words 2 and 3 without the component, and the key
+struct rf_key { uint32_t s_lo, s_hi4, k0, k1; };
+
+// Philox4x32-10 (Salmon et al. 2011): ten rounds, the key bumped between them
+__device__ __forceinline__ void rf_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// 52 bits of (hi, lo) as the centre of one of 2^52 equal cells of (0, 1): exact, never 0 or 1
+__device__ __forceinline__ double rf_uniform(uint32_t lo, uint32_t hi) {
+  return ((double)((((uint64_t)hi << 32) | lo) >> 12) + 0.5) * 0x1p-52;
+}
+
+// what a lane knows of a mode before it draws: whether it is stored as zero, whether it is the mirror of its pair, the
+// pair's counter, its wavenumbers and |k|^2 in double, and its amplitude
+struct rf_mode { bool zero, mirror; uint32_t c_lo, c_hi; double kx, ky, kz, kk, a; };
+
+template <typename real>
+__device__ __forceinline__ rf_mode rf_mode_of(int64_t e, const rf_dims &d, const real *__restrict__ k0, const real *__restrict__ k1,
+                                              const real *__restrict__ k2, double dk, const double *__restrict__ amp, int nbins) {
+  const int64_t row = e / d.n2;
+  const int64_t i2 = e - row * d.n2;
+  const int64_t i0 = row / d.n1;
+  const int64_t i1 = row - i0 * d.n1;
+  const uint64_t g0 = d.s0 + i0, g1 = d.s1 + i1, g2 = d.s2 + i2;
+  const uint64_t m0 = g0 ? d.N0 - g0 : 0, m1 = g1 ? d.N1 - g1 : 0, m2 = g2 ? d.N2 - g2 : 0;
+  const uint64_t lg = (g0 * d.N1 + g1) * d.N2 + g2, lm = (m0 * d.N1 + m1) * d.N2 + m2;
+  const uint64_t c = lm < lg ? lm : lg;
+  rf_mode m;
+  m.mirror = lm < lg;
+  m.c_lo = (uint32_t)c;
+  m.c_hi = (uint32_t)(c >> 32);
+  m.zero = (g0 | g1 | g2) == 0 || 2 * g0 == (uint64_t)d.N0 || 2 * g1 == (uint64_t)d.N1 || 2 * g2 == (uint64_t)d.N2;
+  m.kx = m.ky = m.kz = m.kk = 0.0;
+  m.a = 1.0;
+  if (!m.zero) {
+    m.kx = (double)k0[i0], m.ky = (double)k1[i1], m.kz = (double)k2[i2];
+    const double sh = ps_shell_of(m.kx, m.ky, m.kz, dk, m.kk);
+    if (!(sh < (double)nbins)) m.zero = true;            // (a NaN shell too)
+    else if (amp) {
+      m.a = amp[(int)sh];
+      if (m.a == 0.0) m.zero = true;
+    }
+  }
+  return m;
+}
+
+// the complex standard normal pair of (mode, component): Box-Muller on the two uniforms of one Philox call
+__device__ __forceinline__ void rf_gauss(const rf_mode &m, const rf_key &key, int comp, double &gr, double &gi) {
+  uint32_t r[4];
+  rf_philox(m.c_lo, m.c_hi, key.s_lo, key.s_hi4 | (uint32_t)comp, key.k0, key.k1, r);
+  const double u1 = rf_uniform(r[0], r[1]), u2 = rf_uniform(r[2], r[3]);
+  const double rho = sqrt(-2.0 * log(u1));
+  double s, c;
+  sincospi(2.0 * u2, &s, &c);
+  gr = rho * c;
+  gi = rho * s;
+}
+
+// G <- G - K (K . G) / |K|^2 on one part (real or imaginary) of the three components, in double, nothing contracted
+__device__ __forceinline__ void rf_project(const rf_mode &m, double &a, double &b, double &c) {
+#pragma clang fp contract(off)
+  const double kk = m.kk == 0.0 ? 1.0 : m.kk;
+  const double p = ((m.kx * a + m.ky * b) + m.kz * c) / kk;
+  a = a - m.kx * p;
+  b = b - m.ky * p;
+  c = c - m.kz * p;
+}
+
+// the store of V neighbouring modes of one component: `v` holds (re, im) per mode in double, already scaled and conjugated
+template <typename real, int V>
+__device__ __forceinline__ void rf_store(cx<real> *p, const double (&v)[2 * V], const bool (&zero)[V], bool any, bool add) {
+  using vec = st_load<real, 2 * V>;
+  vec o;
+  if (add) {
+    if (!any) return;                                    // every mode of the vector is a zeroed one: untouched
+    o = *reinterpret_cast<const vec *>(p);
+#pragma unroll
+    for (int j = 0; j < V; ++j)
+      if (!zero[j]) {
+        o.m[2 * j] = o.m[2 * j] + (real)v[2 * j];
+        o.m[2 * j + 1] = o.m[2 * j + 1] + (real)v[2 * j + 1];
+      }
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      o.m[2 * j] = zero[j] ? (real)0 : (real)v[2 * j];
+      o.m[2 * j + 1] = zero[j] ? (real)0 : (real)v[2 * j + 1];
+    }
+  }
+  *reinterpret_cast<vec *>(p) = o;
+}
+
+template <typename real, int V, bool PROJECT>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_random_field_kernel(cx<real> *__restrict__ out, int ncomp, rf_dims d, const real *__restrict__ k0, const real *__restrict__ k1,
+                       const real *__restrict__ k2, double dk, const double *__restrict__ amp, int nbins, rf_key key, int add,
+                       int64_t count) {
+  const int64_t nvec = count / V;                        // (count is a multiple of V)
+  for (int64_t i = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * PS_THREADS) {
+    const int64_t e = i * V;
+    rf_mode m[V];
+    bool zero[V], any = false;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      m[j] = rf_mode_of(e + j, d, k0, k1, k2, dk, amp, nbins);
+      zero[j] = m[j].zero;
+      any = any || !zero[j];
+    }
+    if constexpr (PROJECT) {
+      double v[3][2 * V];
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        double gr[3] = {0.0, 0.0, 0.0}, gi[3] = {0.0, 0.0, 0.0};
+        if (!zero[j]) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) rf_gauss(m[j], key, c, gr[c], gi[c]);
+          rf_project(m[j], gr[0], gr[1], gr[2]);
+          rf_project(m[j], gi[0], gi[1], gi[2]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          v[c][2 * j] = gr[c] * m[j].a;
+          v[c][2 * j + 1] = m[j].mirror ? -(gi[c] * m[j].a) : gi[c] * m[j].a;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) rf_store<real, V>(out + c * count + e, v[c], zero, any, add != 0);
+    } else {
+#pragma unroll 1
+      for (int c = 0; c < ncomp; ++c) {
+        double v[2 * V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          double gr = 0.0, gi = 0.0;
+          if (!zero[j]) rf_gauss(m[j], key, c, gr, gi);
+          v[2 * j] = gr * m[j].a;
+          v[2 * j + 1] = m[j].mirror ? -(gi * m[j].a) : gi * m[j].a;
+        }
+        rf_store<real, V>(out + c * count + e, v, zero, any, add != 0);
+      }
+    }
+  }
+}
+
+// gfft_ps_scale_shells: out[c][e] = f[c][e] * (real)tab[b], b the shell of ps_shell_of; +0 where b >= nbins (a NaN shell too).
+// The isotropic counterpart of ps_scale_axes_kernel and in its mould: V modes per lane and 16 bytes per load and store, a
+// lane reads all its values before it stores any (out may BE f).  A vector whose modes are all dropped is not loaded.
+template <typename real, int V, int NC>
+__global__ void __launch_bounds__(PS_THREADS)
+ps_scale_shells_kernel(cx<real> *out, const cx<real> *f, const real *__restrict__ k0, const real *__restrict__ k1,
+                       const real *__restrict__ k2, double dk, const double *__restrict__ tab, int nbins, int64_t n1, int64_t n2,
+                       int64_t count) {
+  using vec = st_load<real, 2 * V>;
+  const int64_t nvec = count / V;                        // (count is a multiple of V)
+  for (int64_t i = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * PS_THREADS) {
+    const int64_t e = i * V;
+    const int64_t row = e / n2, i2 = e - row * n2;
+    const int64_t i0 = row / n1;
+    const double kx = (double)k0[i0], ky = (double)k1[row - i0 * n1];
+    real g[V];
+    bool keep[V], any = false;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      double kk;
+      const double sh = ps_shell_of(kx, ky, (double)k2[i2 + j], dk, kk);
+      keep[j] = sh < (double)nbins;
+      g[j] = keep[j] ? (real)tab[(int)sh] : (real)0;
+      any = any || keep[j];
+    }
+    vec a[NC] = {};
+    if (any) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) a[c] = *reinterpret_cast<const vec *>(f + c * count + e);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      vec o;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        o.m[2 * j] = keep[j] ? a[c].m[2 * j] * g[j] : (real)0;
+        o.m[2 * j + 1] = keep[j] ? a[c].m[2 * j + 1] * g[j] : (real)0;
+      }
+      *reinterpret_cast<vec *>(out + c * count + e) = o;
+    }
+  }
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // f(real()) with the element type of `precision`: a launcher names its kernel and arguments once
 template <typename F>
@@ -2129,6 +2349,45 @@ hipError_t launch_ps_structure(const void *u, int ncomp, const int64_t n[3], int
   return ps_launch(sf_reduce_kernel, nsep * ncomp * SF_NVAL, 0, s, slabs, g.nwg, out);
 }
 
+// the grid of ps_random_field_kernel: a lane per vector of modes up to RF_MAX_WG workgroups, grid-stride beyond
+inline int rf_grid(int64_t nvec) {
+  const int64_t b = (nvec + PS_THREADS - 1) / PS_THREADS;
+  return (int)(b < RF_MAX_WG ? b : RF_MAX_WG);
+}
+
+// 1 <= ncomp <= RF_MAX_COMP (3 with project), the block inside the grid N; checked by the caller
+hipError_t launch_ps_random_field(void *out, int ncomp, const rf_dims &d, int64_t count, const void *k0, const void *k1, const void *k2,
+                                  int project, double dk, const double *amp, int nbins, const rf_key &key, int add, int precision,
+                                  hipStream_t s) {
+  if (!count) return hipSuccess;
+  const bool pair = precision == GFFT_F32 && d.n2 % 2 == 0 && (uintptr_t)out % 16 == 0;
+  auto go = [&](auto kern, int64_t nvec) {
+    return ps_launch(kern, rf_grid(nvec), 0, s, out, ncomp, d, k0, k1, k2, dk, amp, nbins, key, add, count);
+  };
+  if (pair) return project ? go(ps_random_field_kernel<float, 2, true>, count / 2) : go(ps_random_field_kernel<float, 2, false>, count / 2);
+  return by_precision(precision, [&](auto r) {
+    using real = decltype(r);
+    return project ? go(ps_random_field_kernel<real, 1, true>, count) : go(ps_random_field_kernel<real, 1, false>, count);
+  });
+}
+
+template <typename real, int V>
+auto ss_kernel(int nc) {
+  return nc == 1 ? ps_scale_shells_kernel<real, V, 1> : nc == 2 ? ps_scale_shells_kernel<real, V, 2>
+       : nc == 3 ? ps_scale_shells_kernel<real, V, 3> : ps_scale_shells_kernel<real, V, 4>;
+}
+
+// 1 <= ncomp <= SA_MAX_COMP; out == f or no overlap; the geometry of launch_ps_scale_axes
+hipError_t launch_ps_scale_shells(void *out, const void *f, int ncomp, const void *k0, const void *k1, const void *k2, double dk,
+                                  const double *tab, int nbins, int64_t n0, int64_t n1, int64_t n2, int precision, hipStream_t s) {
+  const int64_t count = n0 * n1 * n2;
+  const bool pair = precision == GFFT_F32 && n2 % 2 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)f % 16 == 0;
+  if (pair) return ps_pointwise(ss_kernel<float, 2>(ncomp), count / 2, s, out, f, k0, k1, k2, dk, tab, nbins, n1, n2, count);
+  return by_precision(precision, [&](auto r) {
+    return ps_pointwise(ss_kernel<decltype(r), 1>(ncomp), count, s, out, f, k0, k1, k2, dk, tab, nbins, n1, n2, count);
+  });
+}
+
 }  // namespace
 
 }  // namespace gfft
@@ -2471,6 +2730,47 @@ int gfft_ps_scale_axes(void *d_out, const void *d_f_hat, int ncomp, const void *
     return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scale_axes: axis longer than 2^30");
   if (int rc = check_device()) return rc;
   HIP_TRY(launch_ps_scale_axes(d_out, d_f_hat, ncomp, d_v0, d_v1, d_v2, n0, n1, n2, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_scale_shells(void *d_out, const void *d_f_hat, int ncomp, const void *d_k0, const void *d_k1, const void *d_k2, double dk,
+                         const double *d_tab, int nbins, int64_t n0, int64_t n1, int64_t n2, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_scale_axes)
+  if (!d_out || !d_f_hat || !d_k0 || !d_k1 || !d_k2 || !d_tab || ncomp < 1 || nbins < 1 || !(dk > 0) || n0 < 0 || n1 < 0 || n2 < 0 ||
+      (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_scale_shells: bad argument");
+  static_assert(SA_MAX_COMP == 4, "the message names the limit");
+  if (ncomp > SA_MAX_COMP) return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scale_shells: more than 4 components");
+  if (n0 > ((int64_t)1 << 30) || n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_scale_shells: axis longer than 2^30");
+  if (int rc = check_device()) return rc;
+  HIP_TRY(launch_ps_scale_shells(d_out, d_f_hat, ncomp, d_k0, d_k1, d_k2, dk, d_tab, nbins, n0, n1, n2, precision, (hipStream_t)stream));
+  return GFFT_OK;
+}
+
+int gfft_ps_random_field(void *d_out, int ncomp, const int64_t n[3], const int64_t start[3], const int64_t N[3], const void *d_k0,
+                         const void *d_k1, const void *d_k2, int project, double dk, const double *d_amp, int nbins, uint64_t seed,
+                         uint64_t stream_id, int add, int precision, void *stream) {
+  // (arguments first, as in gfft_ps_interp; d_amp may be NULL: every amplitude 1)
+  if (!d_out || !n || !start || !N || !d_k0 || !d_k1 || !d_k2 || nbins < 1 || !(dk > 0) || (precision != GFFT_F32 && precision != GFFT_F64))
+    return fail(GFFT_ERR_INVALID, "gfft_ps_random_field: bad argument");
+  static_assert(RF_MAX_COMP == 4, "the message names the limit");
+  if (ncomp < 1 || ncomp > RF_MAX_COMP) return fail(GFFT_ERR_INVALID, "gfft_ps_random_field: ncomp must be 1 ... 4");
+  if (project && ncomp != 3) return fail(GFFT_ERR_INVALID, "gfft_ps_random_field: the projection needs 3 components");
+  if (stream_id >> 62) return fail(GFFT_ERR_INVALID, "gfft_ps_random_field: stream_id must be below 2^62");
+  for (int a = 0; a < 3; ++a)
+    if (n[a] < 0 || N[a] < 1 || start[a] < 0 || start[a] > N[a] || n[a] > N[a] - start[a])
+      return fail(GFFT_ERR_INVALID, "gfft_ps_random_field: a block needs n >= 0, N >= 1 and 0 <= start, start + n <= N");
+  if (n[1] > ((int64_t)1 << 30) || n[2] > ((int64_t)1 << 30))
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_random_field: axis longer than 2^30");
+  // the linear index of a mode of the full grid and c * count + e of the block both stay far inside 64 bits
+  if ((double)N[0] * (double)N[1] * (double)N[2] > 0x1p60)
+    return fail(GFFT_ERR_UNSUPPORTED, "gfft_ps_random_field: a grid of more than 2^60 points");
+  if (int rc = check_device()) return rc;
+  const rf_dims d = {n[1], n[2], start[0], start[1], start[2], N[0], N[1], N[2]};
+  const rf_key key = {(uint32_t)stream_id, (uint32_t)(stream_id >> 32) << 2, (uint32_t)seed, (uint32_t)(seed >> 32)};
+  HIP_TRY(launch_ps_random_field(d_out, ncomp, d, n[0] * n[1] * n[2], d_k0, d_k1, d_k2, project != 0, dk, d_amp, nbins, key, add,
+                                 precision, (hipStream_t)stream));
   return GFFT_OK;
 }
 

@@ -118,6 +118,19 @@ interpolation (van Hinsberg et al. 2012), whose coefficients cost a spectral cod
                                 does not depend on the order of the adds, of the particles or on the cut into ranks, and a
                                 numpy restatement gives the same bits; no rank reduction: the blocks are disjoint
 
+and the way into homogeneous isotropic turbulence, which all of the above describe -- a random-phase, divergence-free field
+with a prescribed E(k) (Rogallo 1981) and white-in-time forcing in a band (Eswaran & Pope 1988), from a counter-based
+generator keyed by the global mode index: one pointwise pass, independent of the cut into ranks, Hermitian by construction:
+
+    random_solenoidal(out, seed, stream, amp)   independent complex Gaussian modes of amplitude amp[shell], projected normal
+                                to K; the mirror mode is bit for bit the conjugate, the r2c field the stored half of the c2c
+                                field, the fp32 field the fp64 field rounded once; Nyquist indices and the mean are zero
+    scale_shells(f_hat, table)  f_hat * table[shell]: the isotropic counterpart of `scale_axes` (sharp and Gaussian filters)
+    random_field(out, E, seed)  the two together: a field whose shell spectrum equals E to rounding; returns the table
+    model_spectrum(k, kind, k_peak, u_rms)   k^4 exp(-2 (k / k_p)^2) or k^4 / (1 + (k / k_p)^2)^(17/6), sum E = 3 u_rms^2 / 2
+    white_noise_force(u_hat, work, step, eps, dt, band, seed)   u_hat += f, a fresh random band field with sum |f|^2 / 2 =
+                                eps dt: the mean injection rate is eps whatever the flow does
+
 Fields are ``newDistArray(fft, rank=1)`` arrays ([3][local shape]); the wavenumbers are three
 per-axis device vectors (the sparse form of get_local_wavenumbermesh, :52-63).
 """
@@ -259,6 +272,103 @@ class SpectralOps:
         assert (no, po) == (ncomp, precision) and to.dim() == t.dim(), 'out and f_hat differ in shape or precision'
         _lib.engine().ps_scale_axes(t, to, ncomp, tuple(v), self.shape, precision)
         return out
+
+    def _shell_table(self, table, device, nbins=None):
+        """a per-shell table (numpy array, sequence or tensor) as a contiguous device double[nbins]"""
+        if isinstance(table, torch.Tensor):
+            assert table.dtype == torch.float64 and table.dim() == 1 and table.is_contiguous(), 'a shell table is a contiguous double vector'
+            assert table.device == device, 'the table and the field live on different devices'
+            t = table
+        else:
+            a = np.ascontiguousarray(np.asarray(table, dtype=np.float64))
+            assert a.ndim == 1, 'a shell table is a vector'
+            t = torch.as_tensor(a).to(device)
+        assert t.numel() >= 1 and (nbins is None or t.numel() == nbins), 'the table has one entry per shell'
+        return t
+
+    def random_solenoidal(self, out, seed, stream=0, amp=None, nbins=None, dk=None, add=False, project=True):
+        """Fills `out` (add=True: adds to it) with random Fourier modes that make a REAL physical field: independent complex
+        Gaussians of amplitude amp[b] per shell b = floor(|k| / dk + 1/2), projected onto the plane normal to K (project=True:
+        a divergence-free velocity, out = [3] + spectral shape; E sum_c |u_hat_c|^2 = 4 amp^2 per mode) or left as they are
+        (project=False: the spectral shape or [m] + it, m <= 4; E |u_hat_c|^2 = 2 amp^2).  One pointwise kernel
+        (gfft_ps_random_field, include/gfft.h): a counter-based generator (Philox4x32-10) keyed by the GLOBAL mode index,
+        `seed` (below 2^64) and `stream` (below 2^62; a step number, say), so
+          * the field does not depend on how the ranks cut the array -- a 2-rank and an 8-rank run start from the same bits;
+          * u_hat(-k) is bit for bit conj u_hat(k), in a c2c layout everywhere and in an r2c layout on its two self-mirrored
+            planes, and the r2c field is the stored half of the c2c field;
+          * the same call gives the same bits, and the fp32 field is the fp64 field rounded once (for equal wavenumbers).
+        Stored as +0 (add=True: left untouched): the mean mode, every mode with a Nyquist index on any axis (K is not odd
+        there, as `gradient` and `curl` document), shells b >= nbins and shells with amp[b] == 0.  amp is a numpy array, a
+        device double tensor or None (every amplitude 1); nbins defaults to len(amp), else to `default_nbins(dk)`.  Returns
+        out.  With amp a tensor or None nothing synchronises or allocates, so the call can be captured."""
+        t, ncomp, precision = self._field(out)
+        assert ncomp <= 4, 'at most 4 components per call'
+        assert not project or (ncomp == 3 and t.dim() == 4), 'the projection needs a [3] + spectral shape field'
+        seed, stream = int(seed), int(stream)
+        assert 0 <= seed < 1 << 64 and 0 <= stream < 1 << 62, 'seed is below 2^64 and stream below 2^62'
+        dk = self.dk if dk is None else float(dk)
+        assert dk > 0 and np.isfinite(dk)
+        tamp = None if amp is None else self._shell_table(amp, t.device, nbins)
+        nbins = int(tamp.numel()) if tamp is not None else self.default_nbins(dk) if nbins is None else int(nbins)
+        assert nbins >= 1
+        start = [int(sl.start or 0) for sl in self._slice]
+        N = list(self._N)
+        _lib.engine().ps_random_field(t, ncomp, self.shape, start, N, self.K, project, dk, tamp, nbins, seed, stream, add, precision)
+        return out
+
+    def scale_shells(self, f_hat, table, out=None, dk=None):
+        """out = f_hat * table[b], b = floor(|k| / dk + 1/2) the shell `spectrum` bins by: the isotropic counterpart of
+        `scale_axes` in one pass -- a sharp or Gaussian LES filter, a rescale to an exact spectrum.  f_hat is the spectral shape
+        or [m] + it, m <= 4; table is a numpy array or a device double tensor with one entry per shell, converted to the
+        field's precision on the device; each part of each value is one multiply, bit for bit a numpy restatement.  A mode
+        whose shell lies beyond the table is stored as +0 whatever it held.  out defaults to f_hat (in place) and otherwise
+        has its shape and overlaps nothing.  Returns out.  With a tensor table nothing synchronises or allocates."""
+        t, ncomp, precision = self._field(f_hat)
+        assert ncomp <= 4, 'at most 4 components per call'
+        dk = self.dk if dk is None else float(dk)
+        assert dk > 0 and np.isfinite(dk)
+        tab = self._shell_table(table, t.device)
+        if out is None:
+            out = f_hat
+        to, no, po = self._field(out)
+        assert (no, po) == (ncomp, precision) and to.dim() == t.dim(), 'out and f_hat differ in shape or precision'
+        _lib.engine().ps_scale_shells(t, to, ncomp, self.K, dk, tab, int(tab.numel()), self.shape, precision)
+        return out
+
+    def random_field(self, out, E, seed, stream=0, dk=None):
+        """A random solenoidal velocity whose shell spectrum IS `E` (Rogallo 1981): `random_solenoidal` at unit amplitude over
+        len(E) shells, its `spectrum` (added over the ranks, the same bits on every rank), the table sqrt(E[b] / E_have[b])
+        (0 where a shell holds no mode), and `scale_shells` in place with that table.  The spectrum of the result equals E
+        to rounding in every shell that holds a mode; E of an empty shell (shell 0, or one beyond the grid) is unreachable
+        and ignored.  out = [3] + spectral shape.  Synchronises (the spectrum is read on the host).  Returns the table."""
+        E = np.asarray(E, dtype=np.float64)
+        assert E.ndim == 1 and len(E) >= 1 and np.isfinite(E).all() and (E >= 0).all(), 'E = a finite, non-negative value per shell'
+        nbins = len(E)
+        self.random_solenoidal(out, seed, stream, None, nbins, dk)
+        have = self.spectrum(out, nbins=nbins, dk=dk)[0]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            table = np.where(have == 0, 0.0, np.sqrt(E / have))
+        self.scale_shells(out, table, dk=dk)
+        return table
+
+    def white_noise_force(self, u_hat, work, step, eps, dt, band, seed):
+        """One step of white-in-time random forcing in the shells band = (blo, bhi) (Eswaran & Pope 1988, without the
+        Ornstein-Uhlenbeck memory): u_hat += f with f a fresh random solenoidal field in the band -- `random_solenoidal(work,
+        seed, stream=step)`, an indicator amplitude -- scaled so that sum w |f|^2 / 2 = eps dt exactly.  The energy grows by
+        eps dt + <u . f>, and the cross term has zero mean because f is independent of u: the mean injection rate is eps
+        whatever the flow does.  `work` has u_hat's shape and is overwritten with the unscaled f.  The scale comes from the
+        rank-reduced `spectrum(work)` on the host, so the call synchronises; a device-resident factor, which a captured step
+        would need, is out of scope here.  Returns the factor sqrt(eps dt / E_f) (0 where the band holds no mode)."""
+        blo, bhi = int(band[0]), int(band[1])
+        eps, dt = float(eps), float(dt)
+        assert 0 <= blo <= bhi and np.isfinite(eps) and eps >= 0 and np.isfinite(dt) and dt >= 0
+        amp = np.zeros(bhi + 1)
+        amp[blo:] = 1.0
+        self.random_solenoidal(work, seed, stream=step, amp=amp)
+        ef = float(self.spectrum(work, nbins=bhi + 1)[0][blo:].sum())
+        factor = math.sqrt(eps * dt / ef) if ef > 0 else 0.0
+        rk_stage(None, None, u_hat, work, 0.0, factor)
+        return factor
 
     def bspline_vectors(self, order=4):
         """The prefilter of B-spline interpolation of `order` as three vectors for `scale_axes`, over this rank's spectral block,
@@ -1136,6 +1246,26 @@ def joint_pdf(counts, ranges, bins):
     with np.errstate(divide='ignore', invalid='ignore'):
         density = c[:nbx * nby].reshape(nbx, nby) / (n * wx * wy)
     return JointPdf(xlo + (np.arange(nbx) + 0.5) * wx, ylo + (np.arange(nby) + 0.5) * wy, density, int(c[nbx * nby]), int(c[nbx * nby + 1]))
+
+
+def model_spectrum(k, kind, k_peak, u_rms):
+    """A model E(k) on the shell centres `k` (`SpectralOps.shells`), the target of `SpectralOps.random_field`:
+        'gaussian'   E ~ k^4 exp(-2 (k / k_peak)^2)                the usual start of decaying turbulence; peaks at k_peak
+        'karman'     E ~ k^4 / (1 + (k / k_peak)^2)^(17/6)         von Karman: k^4 below k_peak, k^(-5/3) above
+    normalised so that sum E = 3 u_rms^2 / 2 over the shells given (the sum `SpectralOps.energy` reports).  Host numpy."""
+    k = np.asarray(k, dtype=np.float64)
+    k_peak, u_rms = float(k_peak), float(u_rms)
+    assert k.ndim == 1 and k_peak > 0 and u_rms >= 0 and (k >= 0).all()
+    x = k / k_peak
+    if kind == 'gaussian':
+        E = k ** 4 * np.exp(-2.0 * x * x)
+    elif kind == 'karman':
+        E = k ** 4 / (1.0 + x * x) ** (17.0 / 6.0)
+    else:
+        raise AssertionError("kind = 'gaussian' or 'karman'")
+    total = E.sum()
+    assert total > 0, 'no shell carries energy'
+    return E * (1.5 * u_rms * u_rms / total)
 
 
 def flux(T):
